@@ -153,6 +153,13 @@ def check(rc, what):
         raise RuntimeError("%s failed: %s" % (what, _ERR.get(rc, "error %d" % rc)))
 
 
+def call(name, device, *args):
+    """Entry point `name` on `device`, ordered on its current stream (appended as the last argument); raises on a
+    nonzero return code."""
+    with torch.cuda.device(device):
+        check(getattr(lib(), name)(*args, cur_stream(device)), name)
+
+
 def require_gpu(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:

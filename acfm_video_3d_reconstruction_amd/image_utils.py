@@ -23,9 +23,7 @@ def compute_dt(mask, norm=True):
     nb = _lib.lib().acfm_edt_workspace_bytes(N, H, W)
     ws = torch.empty(nb, dtype=torch.uint8, device=m.device)
     divisor = max(H, W) if norm else 1
-    with torch.cuda.device(m.device):
-        _lib.check(_lib.lib().acfm_edt(_lib.ptr(m), N, H, W, int(divisor), _lib.ptr(out), _lib.ptr(ws), nb,
-                                       _lib.cur_stream(m.device)), "acfm_edt")
+    _lib.call("acfm_edt", m.device, _lib.ptr(m), N, H, W, int(divisor), _lib.ptr(out), _lib.ptr(ws), nb)
     return out[0] if mask.dim() == 2 else out
 
 
@@ -48,8 +46,6 @@ def compute_boundaries(masks):
     cap = H * W
     out = torch.empty((N, cap, 3), dtype=torch.float32, device=m.device)
     counts = torch.empty((N,), dtype=torch.int32, device=m.device)
-    with torch.cuda.device(m.device):
-        _lib.check(_lib.lib().acfm_boundaries(_lib.ptr(m), N, H, W, cap, _lib.ptr(out), _lib.ptr(counts),
-                                              _lib.cur_stream(m.device)), "acfm_boundaries")
+    _lib.call("acfm_boundaries", m.device, _lib.ptr(m), N, H, W, cap, _lib.ptr(out), _lib.ptr(counts))
     max_bd = int(counts.max().item())
     return out[:, :max_bd].contiguous()

@@ -3,6 +3,7 @@
 torch is used here for device memory, streams and autograd bookkeeping only; every op body
 is one or more stream-ordered calls into libacfm_hip.so."""
 import ctypes
+import dataclasses
 import math
 import threading
 
@@ -159,27 +160,40 @@ def _cover_taken(device, tune):
     return 2 if (tune is not None and tune.flags & 4) else 1
 
 
+@dataclasses.dataclass
+class _Setup:
+    """An entry of _SETUP."""
+    key: tuple
+    inputs: tuple          # (v, c, f): kept alive, so that their addresses in the key cannot be recycled
+    ws: torch.Tensor
+    nbytes: int
+    blur: float
+    tune: object
+    prefill: tuple = None  # the texture-output buffers the silhouette render pre-filled: handed out once (_take_prefill)
+
+
 def _remember_setup(v, c, f, H, offset_z, ws, nb, blur, tune, prefill=None):
     if _SHARE[0]:
-        ent = (_setup_key(v, c, f, H, offset_z), ws, nb, float(blur), (v, c, f), tune, [prefill])
+        ent = _Setup(_setup_key(v, c, f, H, offset_z), (v, c, f), ws, nb, float(blur), tune, prefill)
         with _LOCK:
             _SETUP[v.device] = ent
 
 
-def _take_prefill(holder, N, H):
+def _take_prefill(ent, N, H):
     """The texture-output buffers (imgs, sil, pix_to_face, texel_idx) that the silhouette render of a shared setup
     pre-filled on the empty blocks -- handed out once -- or None."""
     with _LOCK:
-        pf, holder[0] = holder[0], None
+        pf, ent.prefill = ent.prefill, None
     return pf if (pf is not None and tuple(pf[0].shape) == (N, 3, H, H)) else None
 
 
 def _shared_setup(v, c, f, H, offset_z):
-    """-> (ws, nbytes, blur, tuning, prefill holder) of a silhouette render of exactly these inputs, or None."""
+    """-> (ws, nbytes, blur, tuning, prefill holder: the _Setup) of a silhouette render of exactly these inputs, or
+    None."""
     with _LOCK:
         ent = _SETUP.get(v.device) if _SHARE[0] else None
-    if ent is not None and ent[0] == _setup_key(v, c, f, H, offset_z):
-        return ent[1], ent[2], ent[3], ent[5], ent[6]
+    if ent is not None and ent.key == _setup_key(v, c, f, H, offset_z):
+        return ent.ws, ent.nbytes, ent.blur, ent.tune, ent
     return None
 
 
@@ -191,9 +205,7 @@ class _Project(torch.autograd.Function):
         v, c = _f32c(verts), _f32c(cams)
         N, V, _ = v.shape
         out = torch.empty_like(v)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_project(_lib.ptr(v), _lib.ptr(c), N, V, float(offset_z),
-                                               _lib.ptr(out), _lib.cur_stream(v.device)), "acfm_project")
+        _lib.call("acfm_project", v.device, _lib.ptr(v), _lib.ptr(c), N, V, float(offset_z), _lib.ptr(out))
         ctx.save_for_backward(v, c)
         return out
 
@@ -204,11 +216,8 @@ class _Project(torch.autograd.Function):
         g = _f32c(g)
         gv = torch.empty_like(v) if ctx.needs_input_grad[0] else None
         gc = torch.empty_like(c) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_project_backward(_lib.ptr(v), _lib.ptr(c), _lib.ptr(g), N, V,
-                                                        _lib.ptr(gv), _lib.ptr(gc),
-                                                        _lib.cur_stream(v.device)),
-                       "acfm_project_backward")
+        _lib.call("acfm_project_backward", v.device, _lib.ptr(v), _lib.ptr(c), _lib.ptr(g), N, V, _lib.ptr(gv),
+                  _lib.ptr(gc))
         return gv, gc, None
 
 
@@ -219,9 +228,7 @@ class _ProjectXY(torch.autograd.Function):
         v, c = _f32c(verts), _f32c(cams)
         N, V, _ = v.shape
         out = torch.empty((N, V, 2), dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_project_xy(_lib.ptr(v), _lib.ptr(c), N, V, float(offset_z),
-                                                  _lib.ptr(out), _lib.cur_stream(v.device)), "acfm_project_xy")
+        _lib.call("acfm_project_xy", v.device, _lib.ptr(v), _lib.ptr(c), N, V, float(offset_z), _lib.ptr(out))
         ctx.save_for_backward(v, c)
         return out
 
@@ -232,11 +239,8 @@ class _ProjectXY(torch.autograd.Function):
         g = _f32c(g)
         gv = torch.empty_like(v) if ctx.needs_input_grad[0] else None
         gc = torch.empty_like(c) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_project_xy_backward(_lib.ptr(v), _lib.ptr(c), _lib.ptr(g), N, V,
-                                                           _lib.ptr(gv), _lib.ptr(gc),
-                                                           _lib.cur_stream(v.device)),
-                       "acfm_project_xy_backward")
+        _lib.call("acfm_project_xy_backward", v.device, _lib.ptr(v), _lib.ptr(c), _lib.ptr(g), N, V, _lib.ptr(gv),
+                  _lib.ptr(gc))
         return gv, gc, None
 
 
@@ -262,10 +266,7 @@ class _DeformApply(torch.autograd.Function):
         if p.shape != (V, Kh):
             raise ValueError("P must be [V,K_h] = [%d,%d], got %s" % (V, Kh, tuple(p.shape)))
         out = torch.empty((N, V, 3), dtype=torch.float32, device=m.device)
-        with torch.cuda.device(m.device):
-            _lib.check(_lib.lib().acfm_deform_apply(_lib.ptr(m), _lib.ptr(p), _lib.ptr(d), N, V, Kh,
-                                                    _lib.ptr(out), _lib.cur_stream(m.device)),
-                       "acfm_deform_apply")
+        _lib.call("acfm_deform_apply", m.device, _lib.ptr(m), _lib.ptr(p), _lib.ptr(d), N, V, Kh, _lib.ptr(out))
         ctx.save_for_backward(p, d)
         return out
 
@@ -278,23 +279,20 @@ class _DeformApply(torch.autograd.Function):
         gm = torch.empty((V, 3), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
         gp = torch.empty_like(p) if ctx.needs_input_grad[1] else None
         gd = torch.empty_like(d) if ctx.needs_input_grad[2] else None
-        with torch.cuda.device(g.device):
-            _lib.check(_lib.lib().acfm_deform_apply_backward(
-                _lib.ptr(p), _lib.ptr(d), _lib.ptr(g), N, V, Kh, _lib.ptr(gd), _lib.ptr(gm), None,
-                _lib.cur_stream(g.device)), "acfm_deform_apply_backward")
-            if gp is not None:
-                # dL/dP = sum_n g_n delta_n^T feeds the solve's backward, which amplifies its rounding by the conditioning
-                # of the system: summed in double and rounded once (acfm_deform_presolve_sums_f64), so that the value does
-                # not depend on how the frames are grouped; a frame-sharded step (sharding.SharedShapeExchange) takes the
-                # unrounded doubles for its exchange buffer
-                sink = _PRESOLVE_SINKS.get(p.data_ptr())
-                if sink is not None:       # (G [V,K_h], sum g [V,3]): float64 views INSIDE the exchange buffer
-                    g64, m64 = sink.presolve_buffer(V, Kh, g.device)
-                else:
-                    g64, m64 = torch.empty((V, Kh), dtype=torch.float64, device=g.device), None
-                _lib.check(_lib.lib().acfm_deform_presolve_sums_f64(
-                    _lib.ptr(d), _lib.ptr(g), N, V, Kh, _lib.ptr(g64), _lib.ptr(m64), _lib.ptr(gp), _lib.cur_stream(g.device)),
-                    "acfm_deform_presolve_sums_f64")
+        _lib.call("acfm_deform_apply_backward", g.device, _lib.ptr(p), _lib.ptr(d), _lib.ptr(g), N, V, Kh, _lib.ptr(gd),
+                  _lib.ptr(gm), None)
+        if gp is not None:
+            # dL/dP = sum_n g_n delta_n^T feeds the solve's backward, which amplifies its rounding by the conditioning
+            # of the system: summed in double and rounded once (acfm_deform_presolve_sums_f64), so that the value does
+            # not depend on how the frames are grouped; a frame-sharded step (sharding.SharedShapeExchange) takes the
+            # unrounded doubles for its exchange buffer
+            sink = _PRESOLVE_SINKS.get(p.data_ptr())
+            if sink is not None:       # (G [V,K_h], sum g [V,3]): float64 views INSIDE the exchange buffer
+                g64, m64 = sink.presolve_buffer(V, Kh, g.device)
+            else:
+                g64, m64 = torch.empty((V, Kh), dtype=torch.float64, device=g.device), None
+            _lib.call("acfm_deform_presolve_sums_f64", g.device, _lib.ptr(d), _lib.ptr(g), N, V, Kh, _lib.ptr(g64),
+                      _lib.ptr(m64), _lib.ptr(gp))
         return gm, gp, gd
 
 
@@ -382,19 +380,16 @@ class _DeformSolve(torch.autograd.Function):
         nbytes = lib.acfm_deform_solve_workspace_bytes(V, Kh)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
         P = torch.empty((V, Kh), dtype=torch.float32, device=b.device)
-        with torch.cuda.device(b.device):
-            st = _lib.cur_stream(b.device)
-            _lib.check(lib.acfm_deform_solve(_lib.ptr(l), _lib.ptr(b), V, Kh, _lib.ptr(P), _lib.ptr(ws), nbytes, st),
-                       "acfm_deform_solve")
-            if check:
-                info = ctypes.c_int(0)
-                _lib.check(lib.acfm_deform_solve_info(_lib.ptr(ws), nbytes, V, ctypes.byref(info), st),
-                           "acfm_deform_solve_info")
-                msg = decode_solve_info(info.value)
-                if msg:
-                    raise RuntimeError(msg)
-            elif not capturing:
-                off = lib.acfm_deform_solve_info_offset(V)
+        _lib.call("acfm_deform_solve", b.device, _lib.ptr(l), _lib.ptr(b), V, Kh, _lib.ptr(P), _lib.ptr(ws), nbytes)
+        if check:
+            info = ctypes.c_int(0)
+            _lib.call("acfm_deform_solve_info", b.device, _lib.ptr(ws), nbytes, V, ctypes.byref(info))
+            msg = decode_solve_info(info.value)
+            if msg:
+                raise RuntimeError(msg)
+        elif not capturing:
+            off = lib.acfm_deform_solve_info_offset(V)
+            with torch.cuda.device(b.device):
                 host = torch.empty(1, dtype=torch.int32, pin_memory=True)
                 host.copy_(ws[off:off + 4].view(torch.int32), non_blocking=True)
                 ev = torch.cuda.Event()
@@ -412,10 +407,8 @@ class _DeformSolve(torch.autograd.Function):
             return None, None, None
         g = _f32c(g)
         gl = torch.empty((V, Kh), dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            _lib.check(_lib.lib().acfm_deform_solve_backward(_lib.ptr(g), V, Kh, _lib.ptr(ctx.ws), ctx.ws.numel(),
-                                                             _lib.ptr(gl), _lib.cur_stream(g.device)),
-                       "acfm_deform_solve_backward")
+        _lib.call("acfm_deform_solve_backward", g.device, _lib.ptr(g), V, Kh, _lib.ptr(ctx.ws), ctx.ws.numel(),
+                  _lib.ptr(gl))
         return None, gl, None
 
 
@@ -443,10 +436,8 @@ class _CameraPipeline(torch.autograd.Function):
             raise ValueError("camera rows %d must be a multiple of the %d frames (transforms %s)"
                              % (R, N, tuple(tr.shape)))
         out = torch.empty((R, 7), dtype=torch.float32, device=e.device)
-        with torch.cuda.device(e.device):
-            _lib.check(_lib.lib().acfm_camera_pipeline(_lib.ptr(e), _lib.ptr(mf), _lib.ptr(tr), R, N, float(decay),
-                                                       _lib.ptr(out), _lib.cur_stream(e.device)),
-                       "acfm_camera_pipeline")
+        _lib.call("acfm_camera_pipeline", e.device, _lib.ptr(e), _lib.ptr(mf), _lib.ptr(tr), R, N, float(decay),
+                  _lib.ptr(out))
         ctx.save_for_backward(e, mf, tr)
         ctx.decay = float(decay)
         return out
@@ -457,10 +448,8 @@ class _CameraPipeline(torch.autograd.Function):
         R, N = e.numel() // 7, mf.numel()
         g = _f32c(g)
         ge = torch.empty_like(e)
-        with torch.cuda.device(e.device):
-            _lib.check(_lib.lib().acfm_camera_pipeline_backward(
-                _lib.ptr(e), _lib.ptr(mf), _lib.ptr(tr), _lib.ptr(g), R, N, ctx.decay, _lib.ptr(ge),
-                _lib.cur_stream(e.device)), "acfm_camera_pipeline_backward")
+        _lib.call("acfm_camera_pipeline_backward", e.device, _lib.ptr(e), _lib.ptr(mf), _lib.ptr(tr), _lib.ptr(g), R, N,
+                  ctx.decay, _lib.ptr(ge))
         return ge, None, None, None
 
 
@@ -490,10 +479,8 @@ class _CameraPipelineTables(torch.autograd.Function):
                              % (N, mf.numel(), tuple(tr.shape), G, len(ts)))
         out = torch.empty((R, 7), dtype=torch.float32, device=ts[0].device)
         ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        with torch.cuda.device(out.device):
-            _lib.check(_lib.lib().acfm_camera_pipeline_tables(
-                ptrs, len(ts), F, _lib.ptr(fi), _lib.ptr(sel) if sel is not None else None, _lib.ptr(mf), _lib.ptr(tr),
-                R, N, float(decay), _lib.ptr(out), _lib.cur_stream(out.device)), "acfm_camera_pipeline_tables")
+        _lib.call("acfm_camera_pipeline_tables", out.device, ptrs, len(ts), F, _lib.ptr(fi), _lib.ptr(sel), _lib.ptr(mf),
+                  _lib.ptr(tr), R, N, float(decay), _lib.ptr(out))
         ctx.save_for_backward(fi, mf, tr, *ts) if sel is None else ctx.save_for_backward(fi, mf, tr, sel, *ts)
         ctx.cfg = (float(decay), R, N, F, len(ts), sel is not None)
         return out
@@ -510,10 +497,8 @@ class _CameraPipelineTables(torch.autograd.Function):
         outs = [torch.empty((F, 7), dtype=torch.float32, device=g.device) if need[i] else None for i in range(nt)]
         ptrs = (ctypes.c_void_p * nt)(*[t.data_ptr() for t in ts])
         gptrs = (ctypes.c_void_p * nt)(*[(o.data_ptr() if o is not None else None) for o in outs])
-        with torch.cuda.device(g.device):
-            _lib.check(_lib.lib().acfm_camera_pipeline_tables_backward(
-                ptrs, nt, F, _lib.ptr(fi), _lib.ptr(sel) if sel is not None else None, _lib.ptr(mf), _lib.ptr(tr),
-                _lib.ptr(g), R, N, decay, gptrs, _lib.cur_stream(g.device)), "acfm_camera_pipeline_tables_backward")
+        _lib.call("acfm_camera_pipeline_tables_backward", g.device, ptrs, nt, F, _lib.ptr(fi), _lib.ptr(sel), _lib.ptr(mf),
+                  _lib.ptr(tr), _lib.ptr(g), R, N, decay, gptrs)
         return (None,) * 6 + tuple(outs)
 
 
@@ -544,9 +529,7 @@ def camera_mirror(cams):
     _lib.require_gpu(cams)
     c = _f32c(cams.detach()).reshape(-1, 7)
     out = torch.empty_like(c)
-    with torch.cuda.device(c.device):
-        _lib.check(_lib.lib().acfm_camera_mirror(_lib.ptr(c), c.shape[0], _lib.ptr(out), _lib.cur_stream(c.device)),
-                   "acfm_camera_mirror")
+    _lib.call("acfm_camera_mirror", c.device, _lib.ptr(c), c.shape[0], _lib.ptr(out))
     return out
 
 
@@ -557,9 +540,7 @@ class _CameraNormalize(torch.autograd.Function):
         r = _f32c(raw)
         N = r.numel() // 7
         out = torch.empty_like(r)
-        with torch.cuda.device(r.device):
-            _lib.check(_lib.lib().acfm_camera_normalize(_lib.ptr(r), N, _lib.ptr(out), _lib.cur_stream(r.device)),
-                       "acfm_camera_normalize")
+        _lib.call("acfm_camera_normalize", r.device, _lib.ptr(r), N, _lib.ptr(out))
         ctx.save_for_backward(r)
         return out
 
@@ -568,10 +549,7 @@ class _CameraNormalize(torch.autograd.Function):
         (r,) = ctx.saved_tensors
         g = _f32c(g)
         gr = torch.empty_like(r)
-        with torch.cuda.device(r.device):
-            _lib.check(_lib.lib().acfm_camera_normalize_backward(_lib.ptr(r), _lib.ptr(g), r.numel() // 7, _lib.ptr(gr),
-                                                                 _lib.cur_stream(r.device)),
-                       "acfm_camera_normalize_backward")
+        _lib.call("acfm_camera_normalize_backward", r.device, _lib.ptr(r), _lib.ptr(g), r.numel() // 7, _lib.ptr(gr))
         return gr
 
 
@@ -598,11 +576,8 @@ class _OFLoss(torch.autograd.Function):
                                 None if mk is None else tuple(mk.shape), B, T))
         loss = torch.empty((B, T - 1), dtype=torch.float32, device=p.device)
         cnt = torch.empty((B, T - 1), dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().acfm_of_loss_shared(_lib.ptr(p), _lib.ptr(fl), _lib.ptr(mk) if mk is not None else None,
-                                                      _lib.ptr(vi), B, T, V, H, W, clips, int(bool(flip_t)),
-                                                      _lib.ptr(loss), _lib.ptr(cnt), _lib.cur_stream(p.device)),
-                       "acfm_of_loss_shared")
+        _lib.call("acfm_of_loss_shared", p.device, _lib.ptr(p), _lib.ptr(fl), _lib.ptr(mk), _lib.ptr(vi), B, T, V, H, W,
+                  clips, int(bool(flip_t)), _lib.ptr(loss), _lib.ptr(cnt))
         ctx.save_for_backward(p, fl, vi, cnt) if mk is None else ctx.save_for_backward(p, fl, vi, cnt, mk)
         ctx.dims = (B, T, V, H, W, clips, int(bool(flip_t)), mk is not None)
         return loss
@@ -614,11 +589,8 @@ class _OFLoss(torch.autograd.Function):
         mk = ctx.saved_tensors[4] if has_m else None
         g = _f32c(g)
         gp = torch.empty_like(p)
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().acfm_of_loss_shared_backward(
-                _lib.ptr(p), _lib.ptr(fl), _lib.ptr(mk) if mk is not None else None, _lib.ptr(vi), _lib.ptr(cnt),
-                _lib.ptr(g), B, T, V, H, W, clips, flip_t, _lib.ptr(gp), _lib.cur_stream(p.device)),
-                "acfm_of_loss_shared_backward")
+        _lib.call("acfm_of_loss_shared_backward", p.device, _lib.ptr(p), _lib.ptr(fl), _lib.ptr(mk), _lib.ptr(vi),
+                  _lib.ptr(cnt), _lib.ptr(g), B, T, V, H, W, clips, flip_t, _lib.ptr(gp))
         return gp, None, None, None, None, None, None
 
 
@@ -645,9 +617,7 @@ def correlation(f1, f2, max_displacement):
     N, C, H, W = a.shape
     md = int(max_displacement)
     out = torch.empty((N, (2 * md + 1) ** 2, H, W), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.lib().acfm_correlation_forward(_lib.ptr(a), _lib.ptr(b), N, C, H, W, md, _lib.ptr(out),
-                                                       _lib.cur_stream(a.device)), "acfm_correlation_forward")
+    _lib.call("acfm_correlation_forward", a.device, _lib.ptr(a), _lib.ptr(b), N, C, H, W, md, _lib.ptr(out))
     return out
 
 
@@ -765,11 +735,9 @@ def _lazy_pix_to_face(plane0, vis, v, f, c, H, K, blur, sigma, offset_z):
         kth = torch.empty((N, H, H), dtype=torch.int64, device=v.device)
         vis2 = torch.empty((N, V), dtype=torch.uint8, device=v.device)
         ws, nb = _workspace(N, V, F, H, v.device)          # its own workspace: the render's is still the backward's
-        with torch.no_grad(), torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_sil_forward(
-                _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), N, V, F, H, K, K, float(blur), float(sigma), float(offset_z),
-                _lib.ptr(mask), _lib.ptr(full), _lib.ptr(kth), _lib.ptr(vis2), _lib.ptr(ws), nb,
-                _lib.tuning_ptr(tune), _lib.cur_stream(v.device)), "acfm_sil_forward")
+        _lib.call("acfm_sil_forward", v.device, _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), N, V, F, H, K, K, float(blur),
+                  float(sigma), float(offset_z), _lib.ptr(mask), _lib.ptr(full), _lib.ptr(kth), _lib.ptr(vis2),
+                  _lib.ptr(ws), nb, _lib.tuning_ptr(tune))
         return full
 
     return LazyPixToFace(plane0, K, make_full, vis)
@@ -902,121 +870,12 @@ class LazyGrad(torch.Tensor):
 
 # ------------------------------------------------------------------------------ silhouette
 class _SilRender(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, verts, faces, cams, img_size, K, blur, sigma, offset_z, k_out, f16=False):
-        _lib.require_gpu(verts, faces, cams)
-        v, c = _f32c(verts), _f32c(cams)
-        N, V, _ = v.shape
-        f = expand_faces(faces, N)
-        F, H = f.shape[1], int(img_size)
-        if f16 and k_out != 1:
-            raise ValueError("storage='f16' writes the int32 nearest-face plane only (k_out = 1)")
-        mask = torch.empty((N, H, H), dtype=torch.float16 if f16 else torch.float32, device=v.device)
-        p2f = torch.empty((N, H, H, k_out), dtype=torch.int32 if f16 else torch.int64, device=v.device)
-        kth = torch.empty((N, H, H), dtype=torch.int64, device=v.device)  # u64 keys, opaque
-        vis = torch.empty((N, V), dtype=torch.uint8, device=v.device)
-        ws, nb = _workspace(N, V, F, H, v.device)
-        tune = _cover_tuning(v.device, _lib.tuning()[1])
-        if f16:
-            tune = _lib.with_f16(tune, True)
-        tp = _lib.tuning_ptr(tune)
-        # a texture render of this prediction is expected (the cover flag is on while they do follow): its constant
-        # outputs on the empty blocks are stored by THIS kernel, behind the walk, into buffers that render then adopts
-        # (acfm_sil_forward_prefill / acfm_tex_forward ws_ready = 3: -20 us of the texture kernel's 36)
-        prefill = None
-        if PREFILL_TEX[0] and tune is not None and (tune.flags & 4) and not f16 and _SHARE[0]:
-            prefill = (torch.empty((N, 3, H, H), dtype=torch.float32, device=v.device),
-                       torch.empty((N, H, H), dtype=torch.float32, device=v.device),
-                       torch.empty((N, H, H, 1), dtype=torch.int64, device=v.device),
-                       torch.empty((N, H, H), dtype=torch.int32, device=v.device))
-        # NeuralRenderer.project_points of these very vertices and cameras (main.py:715, predictor.py:319: the boundary
-        # loss's input) comes out of the face setup (AcfmSilExtras.proj_xy) and its gradient goes back through THIS
-        # operator's one projection backward: no second projection kernel either way, no sum of two vertex / camera
-        # gradients afterwards (k_project, k_project_bwd and two torch adds less per step)
-        proj = torch.empty((N, V, 2), dtype=torch.float32, device=v.device)
-        exp, _ex_keep = _lib.sil_extras(proj_xy=proj, prefill=prefill)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_sil_forward_ex(
-                _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), N, V, F, H, K, int(k_out), float(blur), float(sigma),
-                float(offset_z), _lib.ptr(mask), _lib.ptr(p2f), _lib.ptr(kth), _lib.ptr(vis),
-                _lib.ptr(ws), nb, tp, exp, _lib.cur_stream(v.device)), "acfm_sil_forward_ex")
-        _remember_setup(v, c, f, H, offset_z, ws, nb, blur, tune, prefill)
-        ctx.save_for_backward(v, f, c, mask, kth)
-        ctx.cfg = (H, float(blur), float(sigma), float(offset_z))
-        ctx.ws = (ws, nb, tune)  # face records + tile schedule: reused by backward (no second setup)
-        ctx.mark_non_differentiable(p2f, vis)
-        ctx.set_materialize_grads(False)  # no zero-filled [N,H,H,K] int64 "gradient" for pix_to_face
-        return mask, p2f, vis, proj
+    """Soft silhouette render (acfm_sil_forward_ex / acfm_sil_backward_ex); fused=True: the render and its [N,4]
+    silhouette-loss vector against gt / edt as one operator (acfm_sil_loss_forward_ex / acfm_sil_loss_backward_ex),
+    the mask then carries no gradient.  -> (losses or None, mask, pix_to_face, vis, proj)."""
 
     @staticmethod
-    def backward(ctx, gmask, _gp2f, _gvis, gproj):
-        v, f, c, mask, kth = ctx.saved_tensors
-        H, blur, sigma, offset_z = ctx.cfg
-        N, V, _ = v.shape
-        F = f.shape[1]
-        if gmask is None and gproj is None:
-            return (None,) * 10
-        gv = torch.empty_like(v) if ctx.needs_input_grad[0] else None
-        gc = torch.empty_like(c) if ctx.needs_input_grad[2] else None
-        gp = _f32c(gproj) if gproj is not None else None
-        if gmask is None:        # only the projection was used: its own backward
-            with torch.cuda.device(v.device):
-                _lib.check(_lib.lib().acfm_project_xy_backward(_lib.ptr(v), _lib.ptr(c), _lib.ptr(gp), N, V, _lib.ptr(gv),
-                                                               _lib.ptr(gc), _lib.cur_stream(v.device)),
-                           "acfm_project_xy_backward")
-            return (gv, None, gc) + (None,) * 7
-        ws, nb, tune = ctx.ws
-        exp, _ex_keep = _lib.sil_extras(grad_proj_xy=gp)
-        pay = gmask.take("mask_losses", mask) if type(gmask) is LazyGrad else None
-        if pay is not None:      # the silhouette losses' gradient, still unformed: the backward kernel forms it per pixel
-            _m, lg, le, rb, go = pay
-            with torch.cuda.device(v.device):
-                _lib.check(_lib.lib().acfm_sil_loss_backward_ex(
-                    _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), _lib.ptr(mask), _lib.ptr(kth), _lib.ptr(lg), _lib.ptr(le), rb,
-                    _lib.ptr(go), N, V, F, H, blur, sigma, offset_z, _lib.ptr(gv), _lib.ptr(gc), _lib.ptr(ws), nb, 1,
-                    _lib.tuning_ptr(tune), exp, _lib.cur_stream(v.device)), "acfm_sil_loss_backward_ex")
-            return (gv, None, gc) + (None,) * 7
-        g = _f32c(gmask)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_sil_backward_ex(
-                _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), _lib.ptr(mask), _lib.ptr(kth), _lib.ptr(g), N,
-                V, F, H, blur, sigma, offset_z, _lib.ptr(gv), _lib.ptr(gc), _lib.ptr(ws), nb, 1,
-                _lib.tuning_ptr(tune), exp, _lib.cur_stream(v.device)), "acfm_sil_backward_ex")
-        return (gv, None, gc) + (None,) * 7
-
-
-def _proj_key(verts, cams):
-    return (verts.data_ptr(), verts._version, tuple(verts.shape), str(verts.dtype), cams.data_ptr(), cams._version,
-            tuple(cams.shape), str(cams.dtype))
-
-
-def sil_render(verts, faces, cams, img_size, K=SIL_K, blur=SIL_BLUR, sigma=SIL_SIGMA, offset_z=0.0,
-               k_out=None, storage="f32"):
-    """Soft silhouette: -> (mask [N,H,H] f32, pix_to_face [N,H,H,k_out] i64), k_out = K (default,
-    what PyTorch3D returns) or 1 (nearest-face plane only; K faces are still blended).
-    The visible-vertex bitmap the raster kernel produces on the side (vertices of every
-    nearest face, = what bds_loss / optical_flow_loss derive from pix_to_face[..., 0]) rides
-    along on the pix_to_face tensor object as `._acfm_vis`."""
-    f16 = _is_f16(storage)   # "f16": mask [N,H,H] float16, pix_to_face [N,H,H,1] int32 (BASELINE config 5); fp32 arithmetic
-    lazy = k_out == "lazy" and not f16 and K > 1
-    mask, p2f, vis, proj = _SilRender.apply(verts, faces, cams, img_size, K, blur, sigma, offset_z,
-                                            1 if (f16 or lazy) else (K if k_out in (None, "lazy") else int(k_out)), f16)
-    if lazy:   # k_out="lazy": [N,H,H,K] whose slots 1.. are rendered on first use (LazyPixToFace)
-        p2f = _lazy_pix_to_face(p2f, vis, _f32c(verts), expand_faces(faces, verts.shape[0]), _f32c(cams),
-                                int(img_size), int(K), blur, sigma, offset_z)
-    else:
-        p2f._acfm_vis = vis
-    # the (x, y) projection of these vertices under these cameras, an output of the render's autograd node: rides on
-    # the pix_to_face object like the visibility bitmap (NeuralRenderer.project_points picks it up)
-    p2f._acfm_proj = (_proj_key(verts, cams), proj)
-    return mask, p2f
-
-
-class _SilRenderLosses(torch.autograd.Function):
-    """acfm_sil_loss_forward / _backward: soft silhouette render + the [N,4] silhouette-loss vector as one operator."""
-
-    @staticmethod
-    def forward(ctx, verts, faces, cams, gt, edt, img_size, K, blur, sigma, offset_z, k_out, f16=False):
+    def forward(ctx, verts, faces, cams, gt, edt, img_size, K, blur, sigma, offset_z, k_out, f16, fused):
         _lib.require_gpu(verts, faces, cams, gt, edt)
         v, c = _f32c(verts), _f32c(cams)
         N, V, _ = v.shape
@@ -1034,57 +893,110 @@ class _SilRenderLosses(torch.autograd.Function):
             raise ValueError("sil_render_losses: gt and edt must have the same batch")
         mask = torch.empty((N, H, H), dtype=torch.float16 if f16 else torch.float32, device=v.device)
         p2f = torch.empty((N, H, H, k_out), dtype=torch.int32 if f16 else torch.int64, device=v.device)
-        kth = torch.empty((N, H, H), dtype=torch.int64, device=v.device)
+        kth = torch.empty((N, H, H), dtype=torch.int64, device=v.device)  # u64 keys, opaque
         vis = torch.empty((N, V), dtype=torch.uint8, device=v.device)
-        losses = torch.empty((N, 4), dtype=torch.float32, device=v.device)
+        losses = torch.empty((N, 4), dtype=torch.float32, device=v.device) if fused else None
         ws, nb = _workspace(N, V, F, H, v.device)
         tune = _cover_tuning(v.device, _lib.tuning()[1])
         if f16:
             tune = _lib.with_f16(tune, True)
         tp = _lib.tuning_ptr(tune)
-        proj = torch.empty((N, V, 2), dtype=torch.float32, device=v.device)      # (see _SilRender.forward)
-        exp, _ex_keep = _lib.sil_extras(proj_xy=proj)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_sil_loss_forward_ex(
-                _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), _lib.ptr(g), _lib.ptr(e), RB, N, V, F, H, K, int(k_out),
-                float(blur), float(sigma), float(offset_z), _lib.ptr(mask), _lib.ptr(p2f), _lib.ptr(kth),
-                _lib.ptr(vis), _lib.ptr(losses), _lib.ptr(ws), nb, tp, exp, _lib.cur_stream(v.device)),
-                "acfm_sil_loss_forward_ex")
-        _remember_setup(v, c, f, H, offset_z, ws, nb, blur, tune)
+        # a texture render of this prediction is expected (the cover flag is on while they do follow): its constant
+        # outputs on the empty blocks are stored by THIS kernel, behind the walk, into buffers that render then adopts
+        # (acfm_sil_forward_prefill / acfm_tex_forward ws_ready = 3: -20 us of the texture kernel's 36)
+        prefill = None
+        if not fused and PREFILL_TEX[0] and tune is not None and (tune.flags & 4) and not f16 and _SHARE[0]:
+            prefill = (torch.empty((N, 3, H, H), dtype=torch.float32, device=v.device),
+                       torch.empty((N, H, H), dtype=torch.float32, device=v.device),
+                       torch.empty((N, H, H, 1), dtype=torch.int64, device=v.device),
+                       torch.empty((N, H, H), dtype=torch.int32, device=v.device))
+        # NeuralRenderer.project_points of these very vertices and cameras (main.py:715, predictor.py:319: the boundary
+        # loss's input) comes out of the face setup (AcfmSilExtras.proj_xy) and its gradient goes back through THIS
+        # operator's one projection backward: no second projection kernel either way, no sum of two vertex / camera
+        # gradients afterwards (k_project, k_project_bwd and two torch adds less per step)
+        proj = torch.empty((N, V, 2), dtype=torch.float32, device=v.device)
+        exp, _ex_keep = _lib.sil_extras(proj_xy=proj, prefill=prefill)
+        P = _lib.ptr
+        if fused:
+            _lib.call("acfm_sil_loss_forward_ex", v.device, P(v), P(f), P(c), P(g), P(e), RB, N, V, F, H, K, int(k_out),
+                      float(blur), float(sigma), float(offset_z), P(mask), P(p2f), P(kth), P(vis), P(losses), P(ws), nb,
+                      tp, exp)
+        else:
+            _lib.call("acfm_sil_forward_ex", v.device, P(v), P(f), P(c), N, V, F, H, K, int(k_out), float(blur),
+                      float(sigma), float(offset_z), P(mask), P(p2f), P(kth), P(vis), P(ws), nb, tp, exp)
+        _remember_setup(v, c, f, H, offset_z, ws, nb, blur, tune, prefill)
         ctx.save_for_backward(v, f, c, mask, kth, g, e)
         ctx.cfg = (H, float(blur), float(sigma), float(offset_z), RB)
-        ctx.ws = (ws, nb, tune)
-        ctx.mark_non_differentiable(mask, p2f, vis)
-        ctx.set_materialize_grads(False)
+        ctx.ws = (ws, nb, tune)  # face records + tile schedule: reused by backward (no second setup)
+        ctx.mark_non_differentiable(*((mask, p2f, vis) if fused else (p2f, vis)))
+        ctx.set_materialize_grads(False)  # no zero-filled [N,H,H,K] int64 "gradient" for pix_to_face
         return losses, mask, p2f, vis, proj
 
     @staticmethod
-    def backward(ctx, glosses, _gm, _gp, _gv, gproj):
+    def backward(ctx, glosses, gmask, _gp2f, _gvis, gproj):
         v, f, c, mask, kth, g, e = ctx.saved_tensors
         H, blur, sigma, offset_z, RB = ctx.cfg
         N, V, _ = v.shape
         F = f.shape[1]
-        none = (None,) * 12
-        if glosses is None and gproj is None:
+        none = (None,) * 13
+        if glosses is None and gmask is None and gproj is None:
             return none
         gv = torch.empty_like(v) if ctx.needs_input_grad[0] else None
         gc = torch.empty_like(c) if ctx.needs_input_grad[2] else None
         gp = _f32c(gproj) if gproj is not None else None
-        if glosses is None:      # only the projection was used: its own backward
-            with torch.cuda.device(v.device):
-                _lib.check(_lib.lib().acfm_project_xy_backward(_lib.ptr(v), _lib.ptr(c), _lib.ptr(gp), N, V, _lib.ptr(gv),
-                                                               _lib.ptr(gc), _lib.cur_stream(v.device)),
-                           "acfm_project_xy_backward")
+        P = _lib.ptr
+        if glosses is None and gmask is None:      # only the projection was used: its own backward
+            _lib.call("acfm_project_xy_backward", v.device, P(v), P(c), P(gp), N, V, P(gv), P(gc))
             return (gv, None, gc) + none[3:]
-        go = _f32c(glosses)
         ws, nb, tune = ctx.ws
         exp, _ex_keep = _lib.sil_extras(grad_proj_xy=gp)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_sil_loss_backward_ex(
-                _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), _lib.ptr(mask), _lib.ptr(kth), _lib.ptr(g), _lib.ptr(e), RB,
-                _lib.ptr(go), N, V, F, H, blur, sigma, offset_z, _lib.ptr(gv), _lib.ptr(gc), _lib.ptr(ws), nb, 1,
-                _lib.tuning_ptr(tune), exp, _lib.cur_stream(v.device)), "acfm_sil_loss_backward_ex")
+        if glosses is not None:       # the fused operator
+            pay = (mask, g, e, RB, _f32c(glosses))
+        else:                         # the silhouette losses' gradient, still unformed: the kernel forms it per pixel
+            pay = gmask.take("mask_losses", mask) if type(gmask) is LazyGrad else None
+        if pay is not None:
+            _m, lg, le, rb, go = pay
+            _lib.call("acfm_sil_loss_backward_ex", v.device, P(v), P(f), P(c), P(mask), P(kth), P(lg), P(le), rb, P(go),
+                      N, V, F, H, blur, sigma, offset_z, P(gv), P(gc), P(ws), nb, 1, _lib.tuning_ptr(tune), exp)
+        else:
+            gm = _f32c(gmask)
+            _lib.call("acfm_sil_backward_ex", v.device, P(v), P(f), P(c), P(mask), P(kth), P(gm), N, V, F, H, blur,
+                      sigma, offset_z, P(gv), P(gc), P(ws), nb, 1, _lib.tuning_ptr(tune), exp)
         return (gv, None, gc) + none[3:]
+
+
+def _proj_key(verts, cams):
+    return (verts.data_ptr(), verts._version, tuple(verts.shape), str(verts.dtype), cams.data_ptr(), cams._version,
+            tuple(cams.shape), str(cams.dtype))
+
+
+def _sil_apply(verts, faces, cams, gt, edt, img_size, K, blur, sigma, offset_z, k_out, storage, fused):
+    """_SilRender with the k_out / lazy resolution of both wrappers; -> (losses or None, mask, pix_to_face)."""
+    f16 = _is_f16(storage)
+    lazy = k_out == "lazy" and not f16 and K > 1
+    losses, mask, p2f, vis, proj = _SilRender.apply(verts, faces, cams, gt, edt, img_size, K, blur, sigma, offset_z,
+                                                    1 if (f16 or lazy) else (K if k_out in (None, "lazy") else int(k_out)),
+                                                    f16, fused)
+    if lazy:   # k_out="lazy": [N,H,H,K] whose slots 1.. are rendered on first use (LazyPixToFace)
+        p2f = _lazy_pix_to_face(p2f, vis, _f32c(verts), expand_faces(faces, verts.shape[0]), _f32c(cams),
+                                int(img_size), int(K), blur, sigma, offset_z)
+    else:
+        p2f._acfm_vis = vis
+    # the (x, y) projection of these vertices under these cameras, an output of the render's autograd node: rides on
+    # the pix_to_face object like the visibility bitmap (NeuralRenderer.project_points picks it up)
+    p2f._acfm_proj = (_proj_key(verts, cams), proj)
+    return losses, mask, p2f
+
+
+def sil_render(verts, faces, cams, img_size, K=SIL_K, blur=SIL_BLUR, sigma=SIL_SIGMA, offset_z=0.0,
+               k_out=None, storage="f32"):
+    """Soft silhouette: -> (mask [N,H,H] f32, pix_to_face [N,H,H,k_out] i64), k_out = K (default,
+    what PyTorch3D returns) or 1 (nearest-face plane only; K faces are still blended).
+    The visible-vertex bitmap the raster kernel produces on the side (vertices of every
+    nearest face, = what bds_loss / optical_flow_loss derive from pix_to_face[..., 0]) rides
+    along on the pix_to_face tensor object as `._acfm_vis`.
+    storage="f16": mask [N,H,H] float16, pix_to_face [N,H,H,1] int32 (BASELINE config 5); fp32 arithmetic."""
+    return _sil_apply(verts, faces, cams, None, None, img_size, K, blur, sigma, offset_z, k_out, storage, False)[1:]
 
 
 def sil_render_losses(verts, faces, cams, img_size, gt=None, edt=None, K=SIL_K, blur=SIL_BLUR, sigma=SIL_SIGMA,
@@ -1093,19 +1005,9 @@ def sil_render_losses(verts, faces, cams, img_size, gt=None, edt=None, K=SIL_K, 
     sil_render + mask_losses): -> (losses [N,4] = (mean|m-gt|, sum m*gt, sum(m+gt-m*gt), mean edt*m), mask [N,H,H],
     pix_to_face [N,H,H,k_out]).  Gradients flow from `losses` to verts / cams; `mask` is returned for inspection and
     carries none (use sil_render when the mask itself feeds further differentiable code).  gt / edt: [N,...] or
-    [N/G,...] shared by the G hypotheses of a frame."""
-    f16 = _is_f16(storage)   # "f16": mask and the references are held in float16, the loss sums stay float32
-    lazy = k_out == "lazy" and not f16 and K > 1
-    losses, mask, p2f, vis, proj = _SilRenderLosses.apply(verts, faces, cams, gt, edt, img_size, K, blur, sigma, offset_z,
-                                                          1 if (f16 or lazy) else (K if k_out in (None, "lazy") else int(k_out)),
-                                                          f16)
-    if lazy:
-        p2f = _lazy_pix_to_face(p2f, vis, _f32c(verts), expand_faces(faces, verts.shape[0]), _f32c(cams),
-                                int(img_size), int(K), blur, sigma, offset_z)
-    else:
-        p2f._acfm_vis = vis
-    p2f._acfm_proj = (_proj_key(verts, cams), proj)
-    return losses, mask, p2f
+    [N/G,...] shared by the G hypotheses of a frame.  storage="f16": the mask and the references are held in float16,
+    the loss sums stay float32."""
+    return _sil_apply(verts, faces, cams, gt, edt, img_size, K, blur, sigma, offset_z, k_out, storage, True)
 
 
 # ------------------------------------------------------------------------------ hard raster
@@ -1119,10 +1021,8 @@ def hard_raster(verts_proj, faces, img_size):
     p2f = torch.empty((N, H, H, 1), dtype=torch.int64, device=v.device)
     vis = torch.empty((N, V), dtype=torch.uint8, device=v.device)
     ws, nb = _workspace(N, V, F, H, v.device)
-    with torch.cuda.device(v.device):
-        _lib.check(_lib.lib().acfm_hard_raster(_lib.ptr(v), _lib.ptr(f), N, V, F, H, _lib.ptr(p2f),
-                                               _lib.ptr(vis), _lib.ptr(ws), nb, _lib.tuning()[0],
-                                               _lib.cur_stream(v.device)), "acfm_hard_raster")
+    _lib.call("acfm_hard_raster", v.device, _lib.ptr(v), _lib.ptr(f), N, V, F, H, _lib.ptr(p2f), _lib.ptr(vis),
+              _lib.ptr(ws), nb, _lib.tuning()[0])
     p2f._acfm_vis = vis
     return p2f
 
@@ -1134,9 +1034,13 @@ TEX_BWD_GATHER = True
 
 
 class _TexRender(torch.autograd.Function):
+    """Atlas-textured render (acfm_tex_forward); fused=True: the render and its masked MSE against ref_img / ref_mask
+    as one operator (acfm_tex_mse_forward / acfm_tex_mse_backward_faces), the image then carries no gradient.
+    -> (loss or None, imgs, sil, pix_to_face)."""
+
     @staticmethod
-    def forward(ctx, verts, faces, cams, atlas, img_size, sigma, gamma, offset_z, f16=False):
-        _lib.require_gpu(verts, faces, cams, atlas)
+    def forward(ctx, verts, faces, cams, atlas, ref_img, ref_mask, img_size, sigma, gamma, offset_z, f16, fused):
+        _lib.require_gpu(verts, faces, cams, atlas, ref_img, ref_mask)
         v, c, a = _f32c(verts), _f32c(cams), _real(atlas, f16)   # (a float32 atlas is cast per call: hold it in half to spare that)
         N, V, _ = v.shape
         f = expand_faces(faces, N)
@@ -1146,16 +1050,26 @@ class _TexRender(torch.autograd.Function):
             raise ValueError("atlas must be [N,F,R,R,3] (or [N/G,F,R,R,3], shared by G hypotheses), got %s for "
                              "N=%d F=%d" % (tuple(a.shape), N, F))
         R = a.shape[2]
+        ri = rm = loss = None
+        RB = 0
+        if fused:
+            if R > 8:
+                raise ValueError("tex_render_mse: atlas resolution R <= 8 (use tex_render + tex_mse beyond)")
+            ri, rm = _real(ref_img, f16), _real(ref_mask, f16)
+            RB = _ref_batch(N, ri, "tex_render_mse")
+            if ri.shape[1:] != (3, H, H) or rm.reshape(-1, H, H).shape[0] != RB:
+                raise ValueError("ref_img [N or N/G,3,H,H] and ref_mask [same batch,H,H]")
+            rm = rm.reshape(RB, H, H)
+            loss = torch.empty((N,), dtype=torch.float32, device=v.device)
         rdt = torch.float16 if f16 else torch.float32
         shared = _shared_setup(v, c, f, H, offset_z)
-        holder = None
         if shared is not None:      # the workspace (and the tuning it was carved with) of the silhouette render
-            ws, nb, ws_blur, tune, holder = shared
+            ws, nb, ws_blur, tune, ent = shared
+            ws_ready = _cover_taken(v.device, tune)
         else:
             ws, nb = _workspace(N, V, F, H, v.device)
-            ws_blur, tune = 0.0, _lib.tuning()[1]
-        ws_ready = _cover_taken(v.device, tune) if shared is not None else 0
-        pf = _take_prefill(holder, N, H) if (ws_ready == 2 and not f16) else None
+            ws_blur, tune, ws_ready, ent = 0.0, _lib.tuning()[1], 0, None
+        pf = _take_prefill(ent, N, H) if (ws_ready == 2 and not f16) else None
         if pf is not None:
             imgs, sil, p2f, tidx = pf          # their empty blocks were stored by the silhouette render
             ws_ready = 3
@@ -1165,56 +1079,56 @@ class _TexRender(torch.autograd.Function):
             p2f = torch.empty((N, H, H, 1), dtype=torch.int32 if f16 else torch.int64, device=v.device)
             tidx = torch.empty((N, H, H), dtype=torch.int32, device=v.device)
         tune = _lib.with_f16(tune, f16)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_tex_forward(
-                _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), _lib.ptr(a), N, V, F, H, R, float(sigma),
-                float(gamma), float(offset_z), _lib.ptr(imgs), _lib.ptr(sil), _lib.ptr(p2f),
-                _lib.ptr(tidx), _lib.ptr(ws), nb, ws_ready, float(ws_blur), NA,
-                _lib.tuning_ptr(tune), _lib.cur_stream(v.device)), "acfm_tex_forward")
-        ctx.save_for_backward(tidx, imgs)   # (imgs: to recognise a LazyGrad of this very image, at this version, in the backward)
-        ctx.cfg = (N, F, H, R, NA, V)
-        ctx.adt = atlas.dtype
-        ctx.tune, ctx.f16 = tune, f16
+        P = _lib.ptr
+        if fused:
+            _lib.call("acfm_tex_mse_forward", v.device, P(v), P(f), P(c), P(a), P(ri), P(rm), RB, N, V, F, H, R,
+                      float(sigma), float(gamma), float(offset_z), P(imgs), P(sil), P(p2f), P(tidx), P(loss), P(ws), nb,
+                      ws_ready, float(ws_blur), NA, _lib.tuning_ptr(tune))
+        else:
+            _lib.call("acfm_tex_forward", v.device, P(v), P(f), P(c), P(a), N, V, F, H, R, float(sigma), float(gamma),
+                      float(offset_z), P(imgs), P(sil), P(p2f), P(tidx), P(ws), nb, ws_ready, float(ws_blur), NA,
+                      _lib.tuning_ptr(tune))
+        ctx.save_for_backward(tidx, imgs, ri, rm)   # (imgs: to recognise a LazyGrad of this very image, at this version)
+        ctx.cfg = (N, F, H, R, NA, V, RB)
+        ctx.adt, ctx.tune, ctx.f16 = atlas.dtype, tune, f16
         ctx.ws = (ws, nb, float(ws_blur))   # face boxes: the gather form of the atlas gradient walks them
-        ctx.mark_non_differentiable(sil, p2f)
+        ctx.mark_non_differentiable(*((imgs, sil, p2f) if fused else (sil, p2f)))
         ctx.set_materialize_grads(False)
-        return imgs, sil, p2f
+        return loss, imgs, sil, p2f
 
     @staticmethod
-    def backward(ctx, gimgs, _gs, _gp):
-        tidx, imgs = ctx.saved_tensors
-        N, F, H, R, NA, V = ctx.cfg
-        ga = None
-        pay = None
-        if ctx.needs_input_grad[3] and type(gimgs) is LazyGrad and TEX_BWD_GATHER and R <= 8 and not ctx.f16:
+    def backward(ctx, gloss, gimgs, _gs, _gp):
+        tidx, imgs, ri, rm = ctx.saved_tensors
+        N, F, H, R, NA, V, RB = ctx.cfg
+        none = (None,) * 12
+        if not ctx.needs_input_grad[3]:
+            return none
+        if gloss is not None:       # the fused operator
+            pay = (imgs, ri, rm, RB, _f32c(gloss))
+        elif type(gimgs) is LazyGrad and TEX_BWD_GATHER and R <= 8 and not ctx.f16:
             pay = gimgs.take("tex_mse", imgs)
-        if pay is not None:      # the texture MSE's gradient, still unformed: the atlas-gradient kernel forms it per pixel
+        else:
+            pay = None
+        ws, nb, ws_blur = ctx.ws
+        P = _lib.ptr
+        ga = None
+        if pay is not None:      # the texture MSE's gradient (a LazyGrad still unformed): the kernel forms it per pixel
             t0, ri, rm, rb, go = pay
             ga = torch.empty((NA, F, R, R, 3), dtype=torch.float32, device=t0.device)
-            ws, nb, ws_blur = ctx.ws
-            with torch.cuda.device(t0.device):
-                _lib.check(_lib.lib().acfm_tex_mse_backward_faces(
-                    _lib.ptr(t0), _lib.ptr(ri), _lib.ptr(rm), rb, _lib.ptr(go), _lib.ptr(tidx), _lib.ptr(ws), nb,
-                    ws_blur, N, V, F, H, R, NA, _lib.ptr(ga), _lib.tuning_ptr(ctx.tune), _lib.cur_stream(t0.device)),
-                    "acfm_tex_mse_backward_faces")
-        elif ctx.needs_input_grad[3] and gimgs is not None:
+            _lib.call("acfm_tex_mse_backward_faces", t0.device, P(t0), P(ri), P(rm), rb, P(go), P(tidx), P(ws), nb,
+                      ws_blur, N, V, F, H, R, NA, P(ga), _lib.tuning_ptr(ctx.tune))
+        elif gimgs is not None:
             g = _f32c(gimgs)
             ga = torch.empty((NA, F, R, R, 3), dtype=torch.float32, device=g.device)
-            ws, nb, ws_blur = ctx.ws
-            with torch.cuda.device(g.device):
-                if TEX_BWD_GATHER and R <= 8:
-                    _lib.check(_lib.lib().acfm_tex_backward_faces(
-                        _lib.ptr(g), _lib.ptr(tidx), _lib.ptr(ws), nb, ws_blur, N, V, F, H, R, NA,
-                        _lib.ptr(ga), _lib.cur_stream(g.device)), "acfm_tex_backward_faces")
-                else:
-                    _lib.check(_lib.lib().acfm_tex_backward(_lib.ptr(g), _lib.ptr(tidx), N, F, H, R, NA,
-                                                            _lib.ptr(ga), _lib.cur_stream(g.device)),
-                               "acfm_tex_backward")
+            if TEX_BWD_GATHER and R <= 8:
+                _lib.call("acfm_tex_backward_faces", g.device, P(g), P(tidx), P(ws), nb, ws_blur, N, V, F, H, R, NA, P(ga))
+            else:
+                _lib.call("acfm_tex_backward", g.device, P(g), P(tidx), N, F, H, R, NA, P(ga))
         # geometry / camera: integer texel lookup and K=1 blending send (numerically) no
         # gradient -- |d rgb / d dist| <= 1e-6 |texel| from the delta=1e-10 term.
         if ga is not None and ctx.adt != torch.float32:
             ga = ga.to(ctx.adt)
-        return None, None, None, ga, None, None, None, None, None
+        return none[:3] + (ga,) + none[4:]
 
 
 def tex_render(verts, faces, cams, atlas, img_size, sigma=1e-4, gamma=1e-4, offset_z=0.0, storage="f32"):
@@ -1222,81 +1136,8 @@ def tex_render(verts, faces, cams, atlas, img_size, sigma=1e-4, gamma=1e-4, offs
     atlas [N,F,R,R,3], or [N/G,F,R,R,3] when G hypotheses of every frame share the frame's
     texture (mesh n samples atlas n % (N/G); equivalent to atlas.repeat(G,1,1,1,1) without the
     copies, gradients of the G renders summed)."""
-    return _TexRender.apply(verts, faces, cams, atlas, img_size, sigma, gamma, offset_z, _is_f16(storage))
-
-
-class _TexRenderMSE(torch.autograd.Function):
-    """acfm_tex_mse_forward / acfm_tex_mse_backward_faces: atlas render + masked MSE against reference images as one op."""
-
-    @staticmethod
-    def forward(ctx, verts, faces, cams, atlas, ref_img, ref_mask, img_size, sigma, gamma, offset_z, f16=False):
-        _lib.require_gpu(verts, faces, cams, atlas, ref_img, ref_mask)
-        v, c, a = _f32c(verts), _f32c(cams), _real(atlas, f16)
-        ri, rm = _real(ref_img, f16), _real(ref_mask, f16)
-        N, V, _ = v.shape
-        f = expand_faces(faces, N)
-        F, H = f.shape[1], int(img_size)
-        NA = a.shape[0] if a.dim() == 5 else 0
-        if a.dim() != 5 or NA == 0 or N % NA != 0 or a.shape[1] != F or a.shape[2] != a.shape[3] or a.shape[4] != 3:
-            raise ValueError("atlas must be [N,F,R,R,3] (or [N/G,F,R,R,3]), got %s for N=%d F=%d" % (tuple(a.shape), N, F))
-        R = a.shape[2]
-        if R > 8:
-            raise ValueError("tex_render_mse: atlas resolution R <= 8 (use tex_render + tex_mse beyond)")
-        RB = _ref_batch(N, ri, "tex_render_mse")
-        if ri.shape[1:] != (3, H, H) or rm.reshape(-1, H, H).shape[0] != RB:
-            raise ValueError("ref_img [N or N/G,3,H,H] and ref_mask [same batch,H,H]")
-        rm = rm.reshape(RB, H, H)
-        rdt = torch.float16 if f16 else torch.float32
-        loss = torch.empty((N,), dtype=torch.float32, device=v.device)
-        shared = _shared_setup(v, c, f, H, offset_z)
-        holder = None
-        if shared is not None:
-            ws, nb, ws_blur, tune, holder = shared
-        else:
-            ws, nb = _workspace(N, V, F, H, v.device)
-            ws_blur, tune = 0.0, _lib.tuning()[1]
-        ws_ready = _cover_taken(v.device, tune) if shared is not None else 0
-        pf = _take_prefill(holder, N, H) if (ws_ready == 2 and not f16) else None
-        if pf is not None:
-            imgs, sil, p2f, tidx = pf
-            ws_ready = 3
-        else:
-            imgs = torch.empty((N, 3, H, H), dtype=rdt, device=v.device)
-            sil = torch.empty((N, H, H), dtype=rdt, device=v.device)
-            p2f = torch.empty((N, H, H, 1), dtype=torch.int32 if f16 else torch.int64, device=v.device)
-            tidx = torch.empty((N, H, H), dtype=torch.int32, device=v.device)
-        tune = _lib.with_f16(tune, f16)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_tex_mse_forward(
-                _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), _lib.ptr(a), _lib.ptr(ri), _lib.ptr(rm), RB, N, V, F, H, R,
-                float(sigma), float(gamma), float(offset_z), _lib.ptr(imgs), _lib.ptr(sil), _lib.ptr(p2f),
-                _lib.ptr(tidx), _lib.ptr(loss), _lib.ptr(ws), nb, ws_ready, float(ws_blur), NA,
-                _lib.tuning_ptr(tune), _lib.cur_stream(v.device)), "acfm_tex_mse_forward")
-        ctx.save_for_backward(tidx, imgs, ri, rm)
-        ctx.cfg = (N, F, H, R, NA, V, RB)
-        ctx.adt, ctx.tune = atlas.dtype, tune
-        ctx.ws = (ws, nb, float(ws_blur))
-        ctx.mark_non_differentiable(imgs, sil, p2f)
-        ctx.set_materialize_grads(False)
-        return loss, imgs, sil, p2f
-
-    @staticmethod
-    def backward(ctx, gloss, _gi, _gs, _gp):
-        tidx, imgs, ri, rm = ctx.saved_tensors
-        N, F, H, R, NA, V, RB = ctx.cfg
-        ga = None
-        if ctx.needs_input_grad[3] and gloss is not None:
-            g = _f32c(gloss)
-            ga = torch.empty((NA, F, R, R, 3), dtype=torch.float32, device=g.device)
-            ws, nb, ws_blur = ctx.ws
-            with torch.cuda.device(g.device):
-                _lib.check(_lib.lib().acfm_tex_mse_backward_faces(
-                    _lib.ptr(imgs), _lib.ptr(ri), _lib.ptr(rm), RB, _lib.ptr(g), _lib.ptr(tidx), _lib.ptr(ws), nb,
-                    ws_blur, N, V, F, H, R, NA, _lib.ptr(ga), _lib.tuning_ptr(ctx.tune), _lib.cur_stream(g.device)),
-                    "acfm_tex_mse_backward_faces")
-            if ctx.adt != torch.float32:
-                ga = ga.to(ctx.adt)
-        return (None, None, None, ga) + (None,) * 7
+    return _TexRender.apply(verts, faces, cams, atlas, None, None, img_size, sigma, gamma, offset_z, _is_f16(storage),
+                            False)[1:]
 
 
 def tex_render_mse(verts, faces, cams, atlas, ref_img, ref_mask, img_size, sigma=1e-4, gamma=1e-4, offset_z=0.0,
@@ -1304,8 +1145,8 @@ def tex_render_mse(verts, faces, cams, atlas, ref_img, ref_mask, img_size, sigma
     """Atlas-textured render and its masked MSE against reference images as ONE operator (opt-in; the drop-in pair is
     tex_render + tex_mse): -> (loss [N] = mean over (3,H,W) of (tex*mask - img*mask)^2, imgs [N,3,H,H] (no gradient),
     sil, pix_to_face).  Gradient flows from `loss` to the atlas.  ref_img / ref_mask: [N,...] or [N/G,...]."""
-    return _TexRenderMSE.apply(verts, faces, cams, atlas, ref_img, ref_mask, img_size, sigma, gamma, offset_z,
-                               _is_f16(storage))
+    return _TexRender.apply(verts, faces, cams, atlas, ref_img, ref_mask, img_size, sigma, gamma, offset_z,
+                            _is_f16(storage), True)
 
 
 def vertex_color_render(verts, faces, cams, verts_rgb, img_size, sigma=1e-4, gamma=1e-4, offset_z=0.0):
@@ -1323,11 +1164,9 @@ def vertex_color_render(verts, faces, cams, verts_rgb, img_size, sigma=1e-4, gam
     p2f = torch.empty((N, H, H, 1), dtype=torch.int64, device=v.device)
     nb = _lib.lib().acfm_raster_workspace_bytes(N, V, F, H) + 4 * N * H * H
     ws = torch.empty(nb, dtype=torch.uint8, device=v.device)
-    with torch.cuda.device(v.device):
-        _lib.check(_lib.lib().acfm_vertex_color_forward(
-            _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), _lib.ptr(col), N, V, F, H, float(sigma), float(gamma),
-            float(offset_z), _lib.ptr(imgs), _lib.ptr(sil), _lib.ptr(p2f), _lib.ptr(ws), nb, 0, 0.0,
-            _lib.tuning()[0], _lib.cur_stream(v.device)), "acfm_vertex_color_forward")
+    _lib.call("acfm_vertex_color_forward", v.device, _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), _lib.ptr(col), N, V, F, H,
+              float(sigma), float(gamma), float(offset_z), _lib.ptr(imgs), _lib.ptr(sil), _lib.ptr(p2f), _lib.ptr(ws),
+              nb, 0, 0.0, _lib.tuning()[0])
     return imgs, sil, p2f
 
 
@@ -1358,10 +1197,7 @@ class _MaskLosses(torch.autograd.Function):
         if g is not None and e is not None and g.shape[0] != e.shape[0]:
             raise ValueError("mask_losses: gt and edt must have the same batch")
         out = torch.empty((N, 4), dtype=torch.float32, device=m.device)
-        with torch.cuda.device(m.device):
-            _lib.check(_lib.lib().acfm_mask_losses(_lib.ptr(m), _lib.ptr(g), _lib.ptr(e), N, HW, RB,
-                                                   _lib.ptr(out), _lib.cur_stream(m.device)),
-                       "acfm_mask_losses")
+        _lib.call("acfm_mask_losses", m.device, _lib.ptr(m), _lib.ptr(g), _lib.ptr(e), N, HW, RB, _lib.ptr(out))
         ctx.save_for_backward(m, g, e)
         ctx.rb = RB
         return out
@@ -1376,11 +1212,8 @@ class _MaskLosses(torch.autograd.Function):
 
         def make():
             gm = torch.empty_like(m)
-            with torch.cuda.device(m.device):
-                _lib.check(_lib.lib().acfm_mask_losses_backward(_lib.ptr(m), _lib.ptr(g), _lib.ptr(e),
-                                                                _lib.ptr(go), N, HW, rb, _lib.ptr(gm),
-                                                                _lib.cur_stream(m.device)),
-                           "acfm_mask_losses_backward")
+            _lib.call("acfm_mask_losses_backward", m.device, _lib.ptr(m), _lib.ptr(g), _lib.ptr(e), _lib.ptr(go), N, HW,
+                      rb, _lib.ptr(gm))
             return gm
         if LAZY_GRADS[0] and m.dim() >= 2:
             return LazyGrad(m, "mask_losses", (m, g, e, rb, go), make), None, None
@@ -1404,9 +1237,7 @@ class _TexMSE(torch.autograd.Function):
         if t.shape[1:] != i.shape[1:] or t.shape[1] != 3 or t[0, 0].numel() != HW or m.shape[0] != RB:
             raise ValueError("tex [N,3,H,W], img [N or N/G,3,H,W] and mask [same batch as img,H,W]")
         out = torch.empty((N,), dtype=torch.float32, device=t.device)
-        with torch.cuda.device(t.device):
-            _lib.check(_lib.lib().acfm_tex_mse(_lib.ptr(t), _lib.ptr(i), _lib.ptr(m), N, HW, RB, _lib.ptr(out),
-                                               _lib.cur_stream(t.device)), "acfm_tex_mse")
+        _lib.call("acfm_tex_mse", t.device, _lib.ptr(t), _lib.ptr(i), _lib.ptr(m), N, HW, RB, _lib.ptr(out))
         ctx.save_for_backward(t, i, m)
         ctx.rb = RB
         return out
@@ -1421,10 +1252,8 @@ class _TexMSE(torch.autograd.Function):
 
         def make():
             gt = torch.empty_like(t)
-            with torch.cuda.device(t.device):
-                _lib.check(_lib.lib().acfm_tex_mse_backward(_lib.ptr(t), _lib.ptr(i), _lib.ptr(m), _lib.ptr(g),
-                                                            N, HW, rb, _lib.ptr(gt), _lib.cur_stream(t.device)),
-                           "acfm_tex_mse_backward")
+            _lib.call("acfm_tex_mse_backward", t.device, _lib.ptr(t), _lib.ptr(i), _lib.ptr(m), _lib.ptr(g), N, HW, rb,
+                      _lib.ptr(gt))
             return gt
         if LAZY_GRADS[0]:
             return LazyGrad(t, "tex_mse", (t, i, m, rb, g), make), None, None
@@ -1451,9 +1280,7 @@ class _Combine(torch.autograd.Function):
         ctx.args = ((ctypes.c_int * len(cols))(*cols), (ctypes.c_float * len(weights))(*[float(w) for w in weights]),
                     len(ts), N, [t.shape for t in terms])
         ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        with torch.cuda.device(total.device):
-            _lib.check(_lib.lib().acfm_combine_losses(ptrs, ctx.args[0], ctx.args[1], len(ts), N, _lib.ptr(total),
-                                                      _lib.cur_stream(total.device)), "acfm_combine_losses")
+        _lib.call("acfm_combine_losses", total.device, ptrs, ctx.args[0], ctx.args[1], len(ts), N, _lib.ptr(total))
         return total
 
     @staticmethod
@@ -1464,10 +1291,7 @@ class _Combine(torch.autograd.Function):
         outs = [torch.empty((N, cols[i]), dtype=torch.float32, device=g.device) if need[i] else None
                 for i in range(nt)]
         ptrs = (ctypes.c_void_p * nt)(*[(o.data_ptr() if o is not None else None) for o in outs])
-        with torch.cuda.device(g.device):
-            _lib.check(_lib.lib().acfm_combine_losses_backward(_lib.ptr(g), ptrs, cols, w, nt, N,
-                                                               _lib.cur_stream(g.device)),
-                       "acfm_combine_losses_backward")
+        _lib.call("acfm_combine_losses_backward", g.device, _lib.ptr(g), ptrs, cols, w, nt, N)
         return (None,) + tuple(o.reshape(shapes[i]) if o is not None else None for i, o in enumerate(outs))
 
 
@@ -1496,10 +1320,8 @@ class _HypTotal(torch.autograd.Function):
         ag = (ctypes.c_int * nt)(*[int(x) for x in aux_group])
         aw = (ctypes.c_float * nt)(*[float(x) for x in aux_weights])
         ptrs = (ctypes.c_void_p * nt)(*[t.data_ptr() for t in ts])
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().acfm_hypothesis_total(ptrs, w, ag, aw, nt, G, N, _lib.ptr(total), _lib.ptr(probs),
-                                                        _lib.ptr(aux[0]), _lib.ptr(aux[1]), _lib.ptr(out),
-                                                        _lib.cur_stream(dev)), "acfm_hypothesis_total")
+        _lib.call("acfm_hypothesis_total", dev, ptrs, w, ag, aw, nt, G, N, _lib.ptr(total), _lib.ptr(probs),
+                  _lib.ptr(aux[0]), _lib.ptr(aux[1]), _lib.ptr(out))
         ctx.args = (w, nt, G, N, [t.shape for t in terms])
         ctx.save_for_backward(probs)
         ctx.mark_non_differentiable(total, probs, aux, out)
@@ -1513,10 +1335,7 @@ class _HypTotal(torch.autograd.Function):
         need = ctx.needs_input_grad[5:]
         outs = [torch.empty((G, N), dtype=torch.float32, device=g.device) if need[i] else None for i in range(nt)]
         ptrs = (ctypes.c_void_p * nt)(*[(o.data_ptr() if o is not None else None) for o in outs])
-        with torch.cuda.device(g.device):
-            _lib.check(_lib.lib().acfm_hypothesis_total_backward(_lib.ptr(g), _lib.ptr(probs), w, nt, G, N, ptrs,
-                                                                 _lib.cur_stream(g.device)),
-                       "acfm_hypothesis_total_backward")
+        _lib.call("acfm_hypothesis_total_backward", g.device, _lib.ptr(g), _lib.ptr(probs), w, nt, G, N, ptrs)
         return (None,) * 5 + tuple(o.reshape(shapes[i]) if o is not None else None for i, o in enumerate(outs))
 
 
@@ -1541,12 +1360,10 @@ class _TexCycle(torch.autograd.Function):
         if x.dim() != 5 or x.shape[2] != x.shape[3] or x.shape[4] != 3 or x.shape[0] % int(T) != 0 or x.shape[2] < 2:
             raise ValueError("texture_cycle: atlases [B*T,F,R,R,3] with R >= 2, got %s (T = %d)" % (tuple(x.shape), T))
         B, F, R = x.shape[0] // int(T), x.shape[1], x.shape[2]
-        lib = _lib.lib()
-        scratch = torch.empty(lib.acfm_texture_cycle_scratch_floats(B, int(T), F, R), dtype=torch.float32, device=x.device)
+        scratch = torch.empty(_lib.lib().acfm_texture_cycle_scratch_floats(B, int(T), F, R), dtype=torch.float32,
+                              device=x.device)
         loss = torch.empty((), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.acfm_texture_cycle(_lib.ptr(x), B, int(T), F, R, _lib.ptr(scratch), _lib.ptr(loss),
-                                              _lib.cur_stream(x.device)), "acfm_texture_cycle")
+        _lib.call("acfm_texture_cycle", x.device, _lib.ptr(x), B, int(T), F, R, _lib.ptr(scratch), _lib.ptr(loss))
         ctx.save_for_backward(x, scratch)
         ctx.cfg = (B, int(T), F, R, textures.dtype)
         return loss
@@ -1557,10 +1374,8 @@ class _TexCycle(torch.autograd.Function):
         B, T, F, R, dt = ctx.cfg
         g = _f32c(go).reshape(1)
         gx = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().acfm_texture_cycle_backward(_lib.ptr(x), _lib.ptr(scratch), _lib.ptr(g), B, T, F, R,
-                                                              _lib.ptr(gx), _lib.cur_stream(x.device)),
-                       "acfm_texture_cycle_backward")
+        _lib.call("acfm_texture_cycle_backward", x.device, _lib.ptr(x), _lib.ptr(scratch), _lib.ptr(g), B, T, F, R,
+                  _lib.ptr(gx))
         return (gx if dt == torch.float32 else gx.to(dt)), None
 
 
@@ -1586,10 +1401,7 @@ def visible_vertices(pix_to_face, faces, nv):
     HW = p[0].numel() // K
     f = expand_faces(faces, N)
     vis = torch.empty((N, nv), dtype=torch.uint8, device=p.device)
-    with torch.cuda.device(p.device):
-        _lib.check(_lib.lib().acfm_visible_vertices(_lib.ptr(p), _lib.ptr(f), N, nv, f.shape[1], HW, K,
-                                                    _lib.ptr(vis), _lib.cur_stream(p.device)),
-                   "acfm_visible_vertices")
+    _lib.call("acfm_visible_vertices", p.device, _lib.ptr(p), _lib.ptr(f), N, nv, f.shape[1], HW, K, _lib.ptr(vis))
     return vis
 
 
@@ -1603,10 +1415,8 @@ class _BdsLoss(torch.autograd.Function):
         RB = _ref_batch(N, b, "bds_loss")
         loss = torch.empty((N,), dtype=torch.float32, device=v.device)
         arg = torch.empty((N, P), dtype=torch.int32, device=v.device)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_bds_loss(_lib.ptr(v), _lib.ptr(b), _lib.ptr(vis.contiguous()), N,
-                                                V, P, RB, _lib.ptr(loss), _lib.ptr(arg),
-                                                _lib.cur_stream(v.device)), "acfm_bds_loss")
+        _lib.call("acfm_bds_loss", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vis.contiguous()), N, V, P, RB,
+                  _lib.ptr(loss), _lib.ptr(arg))
         ctx.save_for_backward(v, b, arg)
         ctx.rb = RB
         return loss
@@ -1618,11 +1428,8 @@ class _BdsLoss(torch.autograd.Function):
         P = b.shape[1]
         g = _f32c(gl)
         gv = torch.empty_like(v)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_bds_loss_backward(_lib.ptr(v), _lib.ptr(b), _lib.ptr(arg),
-                                                         _lib.ptr(g), N, V, P, ctx.rb, _lib.ptr(gv),
-                                                         _lib.cur_stream(v.device)),
-                       "acfm_bds_loss_backward")
+        _lib.call("acfm_bds_loss_backward", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(arg), _lib.ptr(g), N, V, P,
+                  ctx.rb, _lib.ptr(gv))
         return gv, None, None
 
 
@@ -1639,9 +1446,7 @@ def cot_laplacian(verts, faces):
     f = faces.detach().to(torch.int64).contiguous()
     V, F = v.shape[0], f.shape[0]
     L = torch.empty((V, V), dtype=torch.float32, device=v.device)
-    with torch.cuda.device(v.device):
-        _lib.check(_lib.lib().acfm_cot_laplacian(_lib.ptr(v), _lib.ptr(f), V, F, _lib.ptr(L),
-                                                 _lib.cur_stream(v.device)), "acfm_cot_laplacian")
+    _lib.call("acfm_cot_laplacian", v.device, _lib.ptr(v), _lib.ptr(f), V, F, _lib.ptr(L))
     return L
 
 
@@ -1655,11 +1460,8 @@ class _LaplacianSmoothing(torch.autograd.Function):
         n = _lib.lib().acfm_laplacian_smoothing_state_floats(P, F)
         state = torch.empty(n, dtype=torch.float32, device=v.device)
         loss = torch.empty((), dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_laplacian_smoothing(_lib.ptr(v), _lib.ptr(c), _lib.ptr(w), P, F,
-                                                           int(method), int(vpm), int(fpm), _lib.ptr(loss),
-                                                           _lib.ptr(state), _lib.cur_stream(v.device)),
-                       "acfm_laplacian_smoothing")
+        _lib.call("acfm_laplacian_smoothing", v.device, _lib.ptr(v), _lib.ptr(c), _lib.ptr(w), P, F, int(method),
+                  int(vpm), int(fpm), _lib.ptr(loss), _lib.ptr(state))
         ctx.save_for_backward(c, state)
         ctx.cfg = (P, F, int(method), int(vpm), int(fpm))
         return loss
@@ -1670,11 +1472,8 @@ class _LaplacianSmoothing(torch.autograd.Function):
         P, F, method, vpm, fpm = ctx.cfg
         g = _f32c(go).reshape(1)
         gv = torch.empty((P, 3), dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            _lib.check(_lib.lib().acfm_laplacian_smoothing_backward(_lib.ptr(c), _lib.ptr(state), _lib.ptr(g),
-                                                                    P, F, method, vpm, fpm, _lib.ptr(gv),
-                                                                    _lib.cur_stream(g.device)),
-                       "acfm_laplacian_smoothing_backward")
+        _lib.call("acfm_laplacian_smoothing_backward", g.device, _lib.ptr(c), _lib.ptr(state), _lib.ptr(g), P, F,
+                  method, vpm, fpm, _lib.ptr(gv))
         return gv, None, None, None, None, None
 
 
@@ -1695,10 +1494,8 @@ class _EdgeRigidity(torch.autograd.Function):
         if e.shape != et.shape:
             raise ValueError("meshes and template must have the same number of edges")
         loss = torch.empty((), dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            _lib.check(_lib.lib().acfm_edge_rigidity(_lib.ptr(v), _lib.ptr(e), _lib.ptr(vt), _lib.ptr(et),
-                                                     e.shape[0], _lib.ptr(loss), _lib.cur_stream(v.device)),
-                       "acfm_edge_rigidity")
+        _lib.call("acfm_edge_rigidity", v.device, _lib.ptr(v), _lib.ptr(e), _lib.ptr(vt), _lib.ptr(et), e.shape[0],
+                  _lib.ptr(loss))
         ctx.save_for_backward(v, e, vt, et)
         ctx.vpm = int(vpm)
         return loss
@@ -1709,11 +1506,8 @@ class _EdgeRigidity(torch.autograd.Function):
         g = _f32c(go).reshape(1)
         gv = torch.empty_like(v) if ctx.needs_input_grad[0] else None
         gvt = torch.empty_like(vt) if ctx.needs_input_grad[2] else None
-        with torch.cuda.device(g.device):
-            _lib.check(_lib.lib().acfm_edge_rigidity_backward(
-                _lib.ptr(v), _lib.ptr(e), _lib.ptr(vt), _lib.ptr(et), e.shape[0], v.shape[0], vt.shape[0],
-                ctx.vpm, _lib.ptr(g), _lib.ptr(gv), _lib.ptr(gvt), _lib.cur_stream(g.device)),
-                "acfm_edge_rigidity_backward")
+        _lib.call("acfm_edge_rigidity_backward", g.device, _lib.ptr(v), _lib.ptr(e), _lib.ptr(vt), _lib.ptr(et),
+                  e.shape[0], v.shape[0], vt.shape[0], ctx.vpm, _lib.ptr(g), _lib.ptr(gv), _lib.ptr(gvt))
         return gv, None, gvt, None, None
 
 
