@@ -65,6 +65,10 @@ SIGNATURES = {
     "acfm_sil_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _f, _f, _vp,
                                     _vp, _vp, _sz, _i, _vp, _vp]),
     "acfm_hard_raster": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "acfm_rasterize_fragments_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "acfm_rasterize_fragments": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "acfm_rasterize_fragments_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp,
+                                               _sz, _i, _vp, _vp]),
     "acfm_tex_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp,
                               _vp, _sz, _i, _f, _i, _vp, _vp]),
     "acfm_vertex_color_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz,

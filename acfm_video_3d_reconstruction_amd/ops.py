@@ -1027,6 +1027,73 @@ def hard_raster(verts_proj, faces, img_size):
     return p2f
 
 
+# ------------------------------------------------------------------------------ rasterizer fragments
+FRAGMENT_K = (1, 2, 4, 8, 10, 20, 32)
+
+
+class _Fragments(torch.autograd.Function):
+    """PyTorch3D rasterize_meshes over NDC / view-space vertices (acfm_rasterize_fragments /
+    acfm_rasterize_fragments_backward) -> (pix_to_face, zbuf, bary_coords, dists); gradients to verts_ndc only."""
+
+    @staticmethod
+    def forward(ctx, verts_ndc, faces, H, K, blur, clip):
+        _lib.require_gpu(verts_ndc, faces)
+        v = _f32c(verts_ndc)
+        N, V, _ = v.shape
+        f = expand_faces(faces, N)
+        F = f.shape[1]
+        dev = v.device
+        p2f = torch.empty((N, H, H, K), dtype=torch.int64, device=dev)
+        zbuf = torch.empty((N, H, H, K), dtype=torch.float32, device=dev)
+        bary = torch.empty((N, H, H, K, 3), dtype=torch.float32, device=dev)
+        dists = torch.empty((N, H, H, K), dtype=torch.float32, device=dev)
+        nb = _lib.lib().acfm_rasterize_fragments_workspace_bytes(N, V, F, H)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        tune = _lib.tuning()[1]
+        P = _lib.ptr
+        _lib.call("acfm_rasterize_fragments", dev, P(v), P(f), N, V, F, H, K, float(blur), int(clip), P(p2f), P(zbuf),
+                  P(bary), P(dists), P(ws), nb, _lib.tuning_ptr(tune))
+        ctx.save_for_backward(v, f, p2f)
+        ctx.cfg = (H, K, float(blur), int(clip))
+        ctx.ws = (ws, nb, tune)   # face records of the forward: the backward sets nothing up again
+        ctx.mark_non_differentiable(p2f)
+        ctx.set_materialize_grads(False)   # an unused output sends no gradient: that path is skipped, nothing read
+        return p2f, zbuf, bary, dists
+
+    @staticmethod
+    def backward(ctx, _gp2f, gzbuf, gbary, gdists):
+        none = (None,) * 5
+        if not ctx.needs_input_grad[0] or (gzbuf is None and gbary is None and gdists is None):
+            return (None,) + none
+        v, f, p2f = ctx.saved_tensors
+        H, K, blur, clip = ctx.cfg
+        ws, nb, tune = ctx.ws
+        N, V, _ = v.shape
+        gz, gb, gd = (_f32c(g) if g is not None else None for g in (gzbuf, gbary, gdists))
+        gv = torch.empty_like(v)
+        P = _lib.ptr
+        _lib.call("acfm_rasterize_fragments_backward", v.device, P(v), P(f), P(p2f), P(gz), P(gb), P(gd), N, V,
+                  f.shape[1], H, K, blur, clip, P(gv), P(ws), nb, 1, _lib.tuning_ptr(tune))
+        return (gv,) + none
+
+
+def rasterize_fragments(verts_ndc, faces, image_size, faces_per_pixel, blur_radius=0.0, clip_barycentric_coords=False):
+    """PyTorch3D 0.3.0 rasterize_meshes (naive path) of verts_ndc [N,V,3] = (NDC x, NDC y, view z), faces [F,3] or
+    [N,F,3] -> (pix_to_face [N,H,H,K] i64 packed n*F+f, zbuf [N,H,H,K], bary_coords [N,H,H,K,3], dists [N,H,H,K]),
+    -1 in every empty slot.  zbuf / bary_coords / dists are differentiable with respect to verts_ndc (any subset of
+    them may be used).  K = faces_per_pixel in FRAGMENT_K; raster_tuning(deterministic=True) makes the backward
+    bit-reproducible."""
+    H, K = int(image_size), int(faces_per_pixel)
+    if K not in FRAGMENT_K:
+        raise ValueError("faces_per_pixel=%d is not supported (one of %s)" % (K, FRAGMENT_K))
+    if not blur_radius >= 0.0:
+        raise ValueError("blur_radius must be >= 0, got %r" % (blur_radius,))
+    if verts_ndc.dim() != 3 or verts_ndc.shape[-1] != 3:
+        raise ValueError("verts_ndc must be [N,V,3], got %s" % (tuple(verts_ndc.shape),))
+    _lib.require_gpu(verts_ndc, faces)
+    return _Fragments.apply(verts_ndc, faces, H, K, float(blur_radius), bool(clip_barycentric_coords))
+
+
 # ------------------------------------------------------------------------------ texture
 # atlas gradient: gather per face over the pixels of its box (acfm_tex_backward_faces, R <= 8) instead
 # of one global float atomic per pixel and channel (acfm_tex_backward); both are kept and tested

@@ -3,13 +3,18 @@
 `structures.Meshes`, `loss.mesh_laplacian_smoothing`, `ops.SubdivideMeshes`, `io.load_obj`,
 `transforms.{standardize_quaternion, quaternion_multiply, matrix_to_quaternion, ...}`.
 
-It is a shape-compatible shim (same names, arguments, return types), not PyTorch3D: the
-renderer classes are NOT here -- rendering goes through nnutils.nmr on the HIP kernels.
+It is a shape-compatible shim (same names, arguments, return types), not PyTorch3D.  Of the
+renderer, `renderer` holds the rasterizer (`rasterize_meshes`, `MeshRasterizer`, `Fragments`,
+`RasterizationSettings`, `SfMOrthographicCameras`, `look_at_view_transform`) on the HIP kernels;
+the shaders are NOT here -- the reference's renders go through nnutils.nmr.
 `install()` registers the shim as the `pytorch3d` package so `from pytorch3d.structures import
 Meshes` in unmodified caller code resolves to it when the real package is absent."""
 import sys
 
-from . import io, loss, ops, structures, transforms  # noqa: F401
+from . import io, loss, ops, renderer, structures, transforms  # noqa: F401
+
+_RENDERER_MODULES = ("renderer", "renderer.cameras", "renderer.mesh", "renderer.mesh.rasterizer",
+                     "renderer.mesh.rasterize_meshes")
 
 
 def install(force=False):
@@ -19,4 +24,6 @@ def install(force=False):
     sys.modules["pytorch3d"] = me
     for name in ("io", "loss", "ops", "structures", "transforms"):
         sys.modules["pytorch3d." + name] = getattr(me, name)
+    for name in _RENDERER_MODULES:
+        sys.modules["pytorch3d." + name] = sys.modules[__name__ + "." + name]
     return me

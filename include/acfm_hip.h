@@ -78,6 +78,8 @@ int acfm_stream_capture_id(void* stream, unsigned long long* id_host);
 #define ACFM_PROF_DEFORM_BWD 16
 #define ACFM_PROF_SOLVE 17
 #define ACFM_PROF_SOLVE_BWD 18
+#define ACFM_PROF_FRAG_FWD 19
+#define ACFM_PROF_FRAG_BWD 20
 #define ACFM_PROF_NKERNELS 24
 #define ACFM_PROF_RING 8192
 int acfm_prof_enable(int on);
@@ -355,6 +357,37 @@ int acfm_sil_loss_backward_ex(const float* verts_world, const int64_t* faces, co
 int acfm_hard_raster(const float* verts_proj, const int64_t* faces, int N, int V, int F, int H,
                      int64_t* pix_to_face, uint8_t* vis /* optional [N,V], as above */, void* ws,
                      size_t ws_bytes, const AcfmRasterTuning* tuning, void* stream);
+
+/* ---- rasterizer fragments ------------------------------------------------------------
+ * PyTorch3D 0.3.0 rasterize_meshes (the naive path, which oracle_rasterize restates) over
+ * vertices already in NDC / view space: verts_ndc [N,V,3] = (NDC x, NDC y, view z), faces [N,F,3] i64.  Pixel
+ * (y, x) of the H x H image sits at NDC (pix_to_ndc(H-1-x), pix_to_ndc(H-1-y)); a face is kept at a pixel when its
+ * interpolated depth is >= 0 and the pixel is inside it or its squared distance to the face is < blur_radius;
+ * the K nearest are kept in ascending (depth, packed id) order.  Per (pixel, slot), -1 in all four where empty:
+ *   -> pix_to_face [N,H,H,K] i64   packed n*F + f
+ *   -> zbuf        [N,H,H,K] f32   interpolated view z (clipped barycentrics with clip_bary)
+ *   -> bary        [N,H,H,K,3] f32 barycentrics, clamped to [0,1] and renormalised by max(sum, 1e-5) with clip_bary
+ *                                  (16-byte aligned)
+ *   -> dists       [N,H,H,K] f32   squared distance to the nearest edge, negative inside
+ * K in {1,2,4,8,10,20,32}; tuning flags bit 1 (half storage) is refused. */
+size_t acfm_rasterize_fragments_workspace_bytes(int N, int V, int F, int H);
+int acfm_rasterize_fragments(const float* verts_ndc, const int64_t* faces, int N, int V, int F, int H, int K,
+                             float blur_radius, int clip_bary, int64_t* pix_to_face, float* zbuf, float* bary,
+                             float* dists, void* ws, size_t ws_bytes, const AcfmRasterTuning* tuning, void* stream);
+
+/* RasterizeMeshesBackward: upstream gradients of zbuf / bary / dists (each may be NULL: that path
+ * is skipped, nothing is read) -> grad_verts [N,V,3] (d / d verts_ndc, overwritten).  dists: PointLineDistanceBackward
+ * of the arg-min edge with the clamped segment parameter held constant, sign -1 inside; zbuf: d zbuf / d z_i = b_i
+ * plus z_i into the gradient of b_i; bary: through the clamp-and-renormalise (clip_bary) and w_i = edge_i / (area +
+ * kEps), area included.  pix_to_face is the forward's; ws_from_forward != 0: ws holds the face setup of that forward
+ * (same verts / faces / H / blur / tuning).  Tuning flags bit 0: deterministic -- every contribution is split into
+ * two integers (units 2^-4 and 2^-40) summed with integer atomics: bit-identical runs, range |gradient| < 2^59,
+ * resolution 2^-40 (barycentric gradients scale like 1 / area and reach 1e9 near degenerate faces). */
+int acfm_rasterize_fragments_backward(const float* verts_ndc, const int64_t* faces, const int64_t* pix_to_face,
+                                      const float* grad_zbuf, const float* grad_bary, const float* grad_dists, int N,
+                                      int V, int F, int H, int K, float blur_radius, int clip_bary, float* grad_verts,
+                                      void* ws, size_t ws_bytes, int ws_from_forward,
+                                      const AcfmRasterTuning* tuning, void* stream);
 
 /* ---- atlas-textured render -----------------------------------------------------------
  * replaces NeuralRenderer.forward, texture branch with atlas=True
