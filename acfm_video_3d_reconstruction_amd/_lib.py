@@ -69,6 +69,14 @@ SIGNATURES = {
     "acfm_rasterize_fragments": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "acfm_rasterize_fragments_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp,
                                                _sz, _i, _vp, _vp]),
+    "acfm_sigmoid_alpha_blend": (_i, [_vp, _vp, _vp, _sz, _i, _f, _vp, _vp, _vp]),
+    "acfm_sigmoid_alpha_blend_backward": (_i, [_vp, _vp, _vp, _sz, _i, _f, _vp, _vp, _vp, _vp]),
+    "acfm_softmax_rgb_blend": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    "acfm_softmax_rgb_blend_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i, _vp, _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "acfm_interpolate_face_attributes": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _vp, _vp, _vp]),
+    "acfm_interpolate_face_attributes_backward": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp, _vp, _vp, _sz, _vp,
+                                                       _vp]),
     "acfm_tex_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp,
                               _vp, _sz, _i, _f, _i, _vp, _vp]),
     "acfm_vertex_color_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz,
@@ -242,6 +250,11 @@ def sil_extras(proj_xy=None, grad_proj_xy=None, prefill=None):
     pf = prefill or (None, None, None, None)
     e = SilExtras(p(proj_xy), p(grad_proj_xy), p(pf[0]), p(pf[1]), p(pf[2]), p(pf[3]))
     return ctypes.byref(e), e
+
+
+class BlendParams(ctypes.Structure):
+    """AcfmBlendParams of include/acfm_hip.h (host structure, read at call time)."""
+    _fields_ = [("sigma", _f), ("gamma", _f), ("background", _f * 3), ("znear", _f), ("zfar", _f)]
 
 
 _CONSTS = {}

@@ -260,6 +260,18 @@ __device__ __forceinline__ float sigmoid_neg(float sd, float sigma) {
   return 1.0f / (1.0f + expf(sd / sigma));
 }
 
+// Deterministic accumulation of float64 contributions (k_frag_bwd, and the scattering shader backwards): v is split
+// exactly into v_hi = rint(v 2^4) 2^-4 and v_lo = v - v_hi, summed as two integers in units of 2^-4 and 2^-40 with
+// integer atomics (order-independent): range |sum| < 2^59, resolution 2^-40.  frag_unsplit turns a sum back to float.
+struct FragFix { long long hi, lo; };
+__device__ __forceinline__ FragFix frag_split(double v) {
+  const double h = rint(v * 16.0);
+  return FragFix{(long long)h, __double2ll_rn((v - h * 0.0625) * 1099511627776.0)};   // 2^40
+}
+__device__ __forceinline__ float frag_unsplit(long long hi, long long lo) {
+  return (float)((double)hi * 0.0625 + (double)lo * (1.0 / 1099511627776.0));
+}
+
 // wave64 sum via DPP-free shuffles
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

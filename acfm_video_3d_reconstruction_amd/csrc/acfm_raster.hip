@@ -2682,11 +2682,7 @@ constexpr int FRAG_PROBES = 32;
 // together with the 1e-6 resolution of small gradients.  Every contribution v is therefore split exactly into
 // v_hi = rint(v 2^4) 2^-4 and v_lo = v - v_hi, summed as two integers in units of 2^-4 and 2^-40: range |sum| < 2^59
 // (5.8e17), resolution 2^-40 (9.1e-13), integer atomics only (table of 256 faces in LDS, [N,V,3] x 2 in memory).
-struct FragFix { long long hi, lo; };
-__device__ __forceinline__ FragFix frag_split(double v) {
-  const double h = rint(v * 16.0);
-  return FragFix{(long long)h, __double2ll_rn((v - h * 0.0625) * 1099511627776.0)};   // 2^40
-}
+// (FragFix / frag_split: acfm_common.h, shared with the shader backwards of acfm_shade.hip.)
 template <bool DET>
 __device__ __forceinline__ void frag_add(void* acc, size_t o, double v) {   // o: element [N,V,3] index (memory or LDS slot)
   if constexpr (DET) {

@@ -1094,6 +1094,241 @@ def rasterize_fragments(verts_ndc, faces, image_size, faces_per_pixel, blur_radi
     return _Fragments.apply(verts_ndc, faces, H, K, float(blur_radius), bool(clip_barycentric_coords))
 
 
+# ------------------------------------------------------------------------------ shaders over fragments
+# PyTorch3D 0.3.0's blends and interpolate_face_attributes over Fragments: flattened to
+# P = N*H*W pixels of K slots, each a call of acfm_shade.hip.  Gradients to zbuf / bary_coords / dists go back into the
+# fragments, and _Fragments.backward carries them to the vertices.
+def _shade_storage(storage):
+    if storage != "f32":
+        raise ValueError("storage=%r: half storage is not supported on the shader path (float32 only)" % (storage,))
+
+
+def _frag_planes(fragments):
+    """Fragments (or a (pix_to_face, zbuf, bary_coords, dists) tuple) -> the four planes.  The kernels index every
+    plane by pix_to_face's [N,H,W,K] layout, so the shapes are checked here: dists / zbuf [N,H,W,K], bary_coords
+    [N,H,W,K,3], K in FRAGMENT_K.  (The device is checked by the caller, after its own shape checks.)"""
+    p2f, zbuf, bary, dists = (fragments.pix_to_face, fragments.zbuf, fragments.bary_coords, fragments.dists) \
+        if hasattr(fragments, "pix_to_face") else tuple(fragments)
+    if p2f.dim() != 4:
+        raise ValueError("pix_to_face must be [N,H,W,K], got %s" % (tuple(p2f.shape),))
+    K = int(p2f.shape[-1])
+    if K not in FRAGMENT_K:
+        raise ValueError("faces_per_pixel=%d is not supported (one of %s)" % (K, FRAGMENT_K))
+    shape = tuple(p2f.shape)
+    for name, t, want in (("zbuf", zbuf, shape), ("dists", dists, shape), ("bary_coords", bary, shape + (3,))):
+        if t is None or tuple(t.shape) != want:
+            raise ValueError("fragments.%s must be %s like pix_to_face, got %s"
+                             % (name, want, None if t is None else tuple(t.shape)))
+    return p2f, zbuf, bary, dists
+
+
+def _i64c(t):
+    return t.detach().to(torch.int64).contiguous()
+
+
+def _a16(t):
+    """float32 contiguous, 16-byte aligned (the RGBA planes are read as float4)."""
+    t = _f32c(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def blend_struct(blend_params, znear=1.0, zfar=100.0):
+    """BlendParams (sigma, gamma, background_color: a scalar or an RGB triple) -> the AcfmBlendParams structure."""
+    bg = blend_params.background_color
+    if torch.is_tensor(bg):
+        bg = bg.detach().cpu().reshape(-1).tolist()
+    bg = [float(bg)] * 3 if not isinstance(bg, (tuple, list)) else [float(c) for c in bg]
+    if len(bg) == 1:
+        bg = bg * 3
+    if len(bg) != 3:
+        raise ValueError("background_color must be a scalar or an RGB triple, got %r" % (blend_params.background_color,))
+    if not (blend_params.sigma > 0 and blend_params.gamma > 0):
+        raise ValueError("sigma and gamma must be > 0")
+    return _lib.BlendParams(float(blend_params.sigma), float(blend_params.gamma), (ctypes.c_float * 3)(*bg),
+                            float(znear), float(zfar))
+
+
+def _det_ws(tune, n, dev):
+    """Workspace of a scattering backward: 16 bytes per gradient element in deterministic mode, else none."""
+    if tune is not None and tune.flags & 1:
+        nb = 16 * n
+        return torch.empty(nb, dtype=torch.uint8, device=dev), nb
+    return None, 0
+
+
+class _SigmoidBlend(torch.autograd.Function):
+    """sigmoid_alpha_blend (acfm_sigmoid_alpha_blend{,_backward}) -> RGBA [N,H,W,4]; gradients to colors and dists."""
+
+    @staticmethod
+    def forward(ctx, colors, dists, p2f, sigma):
+        p2f, d = _i64c(p2f), _f32c(dists)
+        K = p2f.shape[-1]
+        P = p2f.numel() // K
+        c = _f32c(colors) if colors is not None else None
+        rgba = torch.empty(p2f.shape[:-1] + (4,), dtype=torch.float32, device=p2f.device)
+        tune = _lib.tuning()[1]
+        _lib.call("acfm_sigmoid_alpha_blend", p2f.device, _lib.ptr(p2f), _lib.ptr(d), _lib.ptr(c), P, K, float(sigma),
+                  _lib.ptr(rgba), _lib.tuning_ptr(tune))
+        ctx.save_for_backward(p2f, d)
+        ctx.cfg = (P, K, float(sigma), tune)
+        ctx.set_materialize_grads(False)
+        return rgba
+
+    @staticmethod
+    def backward(ctx, g):
+        need_c, need_d = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g is None or not (need_c or need_d):
+            return None, None, None, None
+        p2f, d = ctx.saved_tensors
+        P, K, sigma, tune = ctx.cfg
+        gd = torch.empty_like(d) if need_d else None
+        gc = torch.empty(p2f.shape + (3,), dtype=torch.float32, device=p2f.device) if need_c else None
+        _lib.call("acfm_sigmoid_alpha_blend_backward", p2f.device, _lib.ptr(p2f), _lib.ptr(d), _lib.ptr(_a16(g)), P, K,
+                  sigma, _lib.ptr(gd), _lib.ptr(gc), _lib.tuning_ptr(tune))
+        return gc, gd, None, None
+
+
+class _SoftmaxBlend(torch.autograd.Function):
+    """softmax_rgb_blend (acfm_softmax_rgb_blend{,_backward}) -> RGBA [N,H,W,4].  Colours: `colors` [N,H,W,K,3], or
+    `atlas` [N*F,R,R,3] sampled at bary_coords (times ambient [N,3]); gradients to colors / atlas, dists and zbuf."""
+
+    @staticmethod
+    def forward(ctx, colors, atlas, dists, zbuf, bary, p2f, ambient, params):
+        p2f, d, z = _i64c(p2f), _f32c(dists), _f32c(zbuf)
+        K = p2f.shape[-1]
+        P = p2f.numel() // K
+        N, H, W = p2f.shape[:3]
+        c = _f32c(colors) if colors is not None else None
+        a = _f32c(atlas) if atlas is not None else None
+        b = _f32c(bary) if atlas is not None else None
+        am = _f32c(ambient) if ambient is not None else None
+        R, Fp = (a.shape[1], a.shape[0]) if a is not None else (0, 0)
+        rgba = torch.empty((N, H, W, 4), dtype=torch.float32, device=p2f.device)
+        tune = _lib.tuning()[1]
+        P_ = _lib.ptr
+        _lib.call("acfm_softmax_rgb_blend", p2f.device, P_(p2f), P_(d), P_(z), P_(b), P_(c), P_(a), R, Fp, P_(am), P,
+                  K, H * W, ctypes.byref(params), P_(rgba), _lib.tuning_ptr(tune))
+        ctx.save_for_backward(p2f, d, z, b, c, a, am)
+        ctx.cfg = (P, K, H * W, R, Fp, params, tune)
+        ctx.set_materialize_grads(False)
+        return rgba
+
+    @staticmethod
+    def backward(ctx, g):
+        nig = ctx.needs_input_grad
+        if g is None or not (nig[0] or nig[1] or nig[2] or nig[3]):
+            return (None,) * 8
+        p2f, d, z, b, c, a, am = ctx.saved_tensors
+        P, K, HW, R, Fp, params, tune = ctx.cfg
+        gc = torch.empty_like(c) if nig[0] else None
+        ga = torch.empty_like(a) if nig[1] else None
+        gd = torch.empty_like(d) if nig[2] else None
+        gz = torch.empty_like(z) if nig[3] else None
+        ws, nb = _det_ws(tune, a.numel(), a.device) if ga is not None else (None, 0)
+        P_ = _lib.ptr
+        _lib.call("acfm_softmax_rgb_blend_backward", p2f.device, P_(p2f), P_(d), P_(z), P_(b), P_(c), P_(a), R, Fp,
+                  P_(am), P, K, HW, ctypes.byref(params), P_(_a16(g)), P_(gd), P_(gz), P_(gc), P_(ga), P_(ws), nb,
+                  _lib.tuning_ptr(tune))
+        return gc, ga, gd, gz, None, None, None, None
+
+
+class _Interpolate(torch.autograd.Function):
+    """interpolate_face_attributes (acfm_interpolate_face_attributes{,_backward}); gradients to bary and attributes."""
+
+    @staticmethod
+    def forward(ctx, bary, attrs, p2f):
+        p2f, b, fa = _i64c(p2f), _f32c(bary), _f32c(attrs)
+        K = p2f.shape[-1]
+        P = p2f.numel() // K
+        Fp, D = fa.shape[0], fa.shape[2]
+        out = torch.empty(p2f.shape + (D,), dtype=torch.float32, device=p2f.device)
+        tune = _lib.tuning()[1]
+        _lib.call("acfm_interpolate_face_attributes", p2f.device, _lib.ptr(p2f), _lib.ptr(b), _lib.ptr(fa), P, K, Fp, D,
+                  _lib.ptr(out), _lib.tuning_ptr(tune))
+        ctx.save_for_backward(p2f, b, fa)
+        ctx.cfg = (P, K, Fp, D, tune)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need_b, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g is None or not (need_b or need_a):
+            return None, None, None
+        p2f, b, fa = ctx.saved_tensors
+        P, K, Fp, D, tune = ctx.cfg
+        gb = torch.empty_like(b) if need_b else None
+        ga = torch.empty_like(fa) if need_a else None
+        ws, nb = _det_ws(tune, fa.numel(), fa.device) if need_a else (None, 0)
+        _lib.call("acfm_interpolate_face_attributes_backward", p2f.device, _lib.ptr(p2f), _lib.ptr(b), _lib.ptr(fa),
+                  _lib.ptr(_f32c(g)), P, K, Fp, D, _lib.ptr(gb), _lib.ptr(ga), _lib.ptr(ws), nb, _lib.tuning_ptr(tune))
+        return gb, ga, None
+
+
+def sigmoid_alpha_blend(colors, fragments, blend_params, storage="f32"):
+    """PyTorch3D 0.3.0 sigmoid_alpha_blend -> RGBA [N,H,W,4]: RGB = colors[..., 0, :] (1 where colors is None: the
+    silhouette shader builds no ones_like tensor), A = 1 - prod_k (1 - sigmoid(-dists / sigma) [pix_to_face >= 0]).
+    Differentiable with respect to colors [N,H,W,K,3] and fragments.dists."""
+    _shade_storage(storage)
+    p2f, zbuf, bary, dists = _frag_planes(fragments)
+    if colors is not None and tuple(colors.shape) != tuple(p2f.shape) + (3,):
+        raise ValueError("colors must be None or [N,H,W,K,3] = %s, got %s"
+                         % (tuple(p2f.shape) + (3,), tuple(colors.shape)))
+    _lib.require_gpu(p2f, zbuf, bary, dists, colors)
+    if not blend_params.sigma > 0:
+        raise ValueError("sigma must be > 0")
+    return _SigmoidBlend.apply(colors, dists, p2f, float(blend_params.sigma))
+
+
+def softmax_rgb_blend(colors, fragments, blend_params, znear=1.0, zfar=100.0, storage="f32"):
+    """PyTorch3D 0.3.0 softmax_rgb_blend of colors [N,H,W,K,3] -> RGBA [N,H,W,4].
+    Differentiable with respect to colors, fragments.dists and fragments.zbuf (the z_max path included)."""
+    _shade_storage(storage)
+    p2f, zbuf, bary, dists = _frag_planes(fragments)
+    if tuple(colors.shape) != tuple(p2f.shape) + (3,):
+        raise ValueError("colors must be [N,H,W,K,3] = %s, got %s" % (tuple(p2f.shape) + (3,), tuple(colors.shape)))
+    _lib.require_gpu(p2f, zbuf, bary, dists, colors)
+    return _SoftmaxBlend.apply(colors, None, dists, zbuf, None, p2f, None, blend_struct(blend_params, znear, zfar))
+
+
+def atlas_softmax_blend(atlas, fragments, blend_params, ambient=None, znear=1.0, zfar=100.0, storage="f32"):
+    """TexturesAtlas.sample_textures + an ambient-only Phong + softmax_rgb_blend in one pass (the reference's texture
+    configuration): atlas [N,F,R,R,3] (or packed [N*F,R,R,3]) is sampled at fragments.bary_coords inside the kernel,
+    times ambient [N,3] / [1,3] / [3] (a constant: no gradient) when given.  -> RGBA [N,H,W,4]; differentiable with
+    respect to atlas, fragments.dists and fragments.zbuf (not bary_coords: the texel index is an integer)."""
+    _shade_storage(storage)
+    p2f, zbuf, bary, dists = _frag_planes(fragments)
+    _lib.require_gpu(p2f, zbuf, bary, dists, atlas, ambient)
+    if atlas.dim() == 5:
+        atlas = atlas.reshape((-1,) + tuple(atlas.shape[2:]))
+    if atlas.dim() != 4 or atlas.shape[1] != atlas.shape[2] or atlas.shape[3] != 3:
+        raise ValueError("atlas must be [N,F,R,R,3] or [N*F,R,R,3] with 3 channels, got %s" % (tuple(atlas.shape),))
+    N = p2f.shape[0]
+    if ambient is not None:
+        if ambient.requires_grad:
+            raise ValueError("ambient is a constant of the fused atlas path (no gradient); use softmax_rgb_blend")
+        ambient = ambient.detach().to(torch.float32).reshape(-1, 3)
+        if ambient.shape[0] not in (1, N):
+            raise ValueError("ambient must be [3], [1,3] or [N,3], got %s" % (tuple(ambient.shape),))
+        ambient = ambient.expand(N, 3)
+    return _SoftmaxBlend.apply(None, atlas, dists, zbuf, bary, p2f, ambient, blend_struct(blend_params, znear, zfar))
+
+
+def interpolate_face_attributes(pix_to_face, barycentric_coords, face_attributes):
+    """PyTorch3D 0.3.0 interpolate_face_attributes: face_attributes [F_packed,3,D] -> [N,H,W,K,D] = sum_i bary_i
+    face_attributes[pix_to_face, i], 0 in empty slots.  Differentiable with respect to both float inputs."""
+    K = int(pix_to_face.shape[-1])
+    if K not in FRAGMENT_K:
+        raise ValueError("faces_per_pixel=%d is not supported (one of %s)" % (K, FRAGMENT_K))
+    if face_attributes.dim() != 3 or face_attributes.shape[1] != 3 or face_attributes.shape[2] < 1:
+        raise ValueError("face_attributes must be [F,3,D], got %s" % (tuple(face_attributes.shape),))
+    if tuple(barycentric_coords.shape) != tuple(pix_to_face.shape) + (3,):
+        raise ValueError("barycentric_coords must be %s, got %s" % (tuple(pix_to_face.shape) + (3,),
+                                                                    tuple(barycentric_coords.shape)))
+    _lib.require_gpu(pix_to_face, barycentric_coords, face_attributes)
+    return _Interpolate.apply(barycentric_coords, face_attributes, pix_to_face)
+
+
 # ------------------------------------------------------------------------------ texture
 # atlas gradient: gather per face over the pixels of its box (acfm_tex_backward_faces, R <= 8) instead
 # of one global float atomic per pixel and channel (acfm_tex_backward); both are kept and tested

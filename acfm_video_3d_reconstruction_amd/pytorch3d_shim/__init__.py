@@ -6,15 +6,19 @@
 It is a shape-compatible shim (same names, arguments, return types), not PyTorch3D.  Of the
 renderer, `renderer` holds the rasterizer (`rasterize_meshes`, `MeshRasterizer`, `Fragments`,
 `RasterizationSettings`, `SfMOrthographicCameras`, `look_at_view_transform`) on the HIP kernels;
-the shaders are NOT here -- the reference's renders go through nnutils.nmr.
+and the shading half over its Fragments (`BlendParams`, the blends, lights, materials, `TexturesAtlas` /
+`TexturesVertex` / `Textures`, the shaders and `MeshRenderer`), so the reference's `MeshRenderer(MeshRasterizer,
+shader)` compositions run as written; nnutils.nmr keeps the hand-fused renders of its two fixed settings.
 `install()` registers the shim as the `pytorch3d` package so `from pytorch3d.structures import
 Meshes` in unmodified caller code resolves to it when the real package is absent."""
 import sys
 
 from . import io, loss, ops, renderer, structures, transforms  # noqa: F401
 
-_RENDERER_MODULES = ("renderer", "renderer.cameras", "renderer.mesh", "renderer.mesh.rasterizer",
-                     "renderer.mesh.rasterize_meshes")
+_RENDERER_MODULES = ("renderer", "renderer.blending", "renderer.cameras", "renderer.lighting", "renderer.materials",
+                     "renderer.mesh", "renderer.mesh.rasterizer", "renderer.mesh.rasterize_meshes",
+                     "renderer.mesh.renderer", "renderer.mesh.shader", "renderer.mesh.shading",
+                     "renderer.mesh.textures")
 
 
 def install(force=False):

@@ -1,6 +1,8 @@
-"""pytorch3d.ops.SubdivideMeshes (multiframe/main.py:196-199); semantics: SURVEY App-A.8."""
+"""pytorch3d.ops.SubdivideMeshes (multiframe/main.py:196-199; semantics: SURVEY App-A.8) and
+interpolate_face_attributes (the HIP kernel of ops.interpolate_face_attributes)."""
 import torch
 
+from ..ops import interpolate_face_attributes  # noqa: F401  (pytorch3d.ops.interpolate_face_attributes)
 from .structures import Meshes
 
 

@@ -53,6 +53,11 @@ class SfMOrthographicCameras:
         T = _batched(kwargs.get("T", self.T), 2, self.device)
         return _WorldToView(R, T)
 
+    def get_camera_center(self, **kwargs):
+        """-> [N,3] world position of the camera: C R + T = 0 (the specular term of phong_shading)."""
+        w2v = self.get_world_to_view_transform(**kwargs)
+        return -torch.matmul(w2v.T[:, None, :], torch.inverse(w2v.R))[:, 0]
+
     def transform_points(self, points, eps=None, **kwargs):
         """points [N,P,3] world -> (fx x_v + px, fy y_v + py, z_v) with (x_v, y_v, z_v) = X R + T."""
         del eps

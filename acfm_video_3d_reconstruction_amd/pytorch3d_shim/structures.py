@@ -182,9 +182,43 @@ class Meshes:
         val = torch.cat([val, -torch.ones(V, dtype=torch.float32, device=self.device)])
         return torch.sparse_coo_tensor(idx, val, (V, V)).coalesce()
 
+    # ---- normals (0.3.0's rule: the unnormalised cross product of every face -- twice its area times its normal --
+    # added into each of its vertices, then F.normalize(eps=1e-6)); torch, differentiable
+    def _compute_normals(self):
+        if "verts_normals" not in self._cache:
+            verts, faces = self.verts_packed(), self.faces_packed()
+            fv = verts[faces]
+            n = torch.zeros_like(verts)
+            n = n.index_add(0, faces[:, 1], torch.cross(fv[:, 2] - fv[:, 1], fv[:, 0] - fv[:, 1], dim=1))
+            n = n.index_add(0, faces[:, 2], torch.cross(fv[:, 0] - fv[:, 2], fv[:, 1] - fv[:, 2], dim=1))
+            n = n.index_add(0, faces[:, 0], torch.cross(fv[:, 1] - fv[:, 0], fv[:, 2] - fv[:, 0], dim=1))
+            self._cache["verts_normals"] = torch.nn.functional.normalize(n, eps=1e-6, dim=1)
+            fn = torch.cross(fv[:, 2] - fv[:, 1], fv[:, 0] - fv[:, 1], dim=1)
+            self._cache["faces_normals"] = torch.nn.functional.normalize(fn, eps=1e-6, dim=1)
+        return self._cache["verts_normals"], self._cache["faces_normals"]
+
+    def verts_normals_packed(self):
+        return self._compute_normals()[0]
+
+    def verts_normals_padded(self):
+        if not self._equal_sized():
+            raise ValueError("verts_normals_padded: meshes of different sizes are not supported")
+        return self.verts_normals_packed().reshape(len(self), -1, 3)
+
+    def faces_normals_packed(self):
+        return self._compute_normals()[1]
+
+    def sample_textures(self, fragments):
+        if self.textures is None:
+            raise ValueError("Meshes does not have textures")
+        if hasattr(self.textures, "verts_features_packed"):
+            return self.textures.sample_textures(fragments, faces_packed=self.faces_packed())
+        return self.textures.sample_textures(fragments)
+
     def update_padded(self, new_verts_padded):
         return Meshes(verts=new_verts_padded, faces=self.faces_padded(), textures=self.textures)
 
     def to(self, device):
+        tex = self.textures.to(device) if self.textures is not None and hasattr(self.textures, "to") else self.textures
         return Meshes(verts=[v.to(device) for v in self._verts_list],
-                      faces=[f.to(device) for f in self._faces_list], textures=self.textures)
+                      faces=[f.to(device) for f in self._faces_list], textures=tex)

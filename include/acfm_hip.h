@@ -389,6 +389,54 @@ int acfm_rasterize_fragments_backward(const float* verts_ndc, const int64_t* fac
                                       void* ws, size_t ws_bytes, int ws_from_forward,
                                       const AcfmRasterTuning* tuning, void* stream);
 
+/* ---- shaders over fragments ---------------------------------------------------------------
+ * The shading half of PyTorch3D 0.3.0's mesh renderer over the outputs of
+ * acfm_rasterize_fragments, flattened: P = N*H*W pixels, K slots per pixel (K in {1,2,4,8,10,20,32}),
+ * pix_to_face [P,K] i64 (packed n*F + f, -1 empty), dists / zbuf [P,K], bary [P,K,3], RGBA [P,4] (16-byte aligned).
+ * Tuning flags bit 1 (half storage) is refused; bit 0 makes the two scattering backwards (grad_atlas,
+ * grad_face_attrs) bit-reproducible (integer-split sums as acfm_rasterize_fragments_backward, in `ws`, which then
+ * needs 16 bytes per gradient element; ws is unused otherwise and may be NULL).  Every gradient output is nullable
+ * (that path is skipped) and overwritten. */
+typedef struct AcfmBlendParams {   /* BlendParams + the znear / zfar of softmax_rgb_blend (host structure) */
+  float sigma;
+  float gamma;
+  float background[3];
+  float znear;
+  float zfar;
+} AcfmBlendParams;
+
+/* sigmoid_alpha_blend: RGB = colors[p,0,:] (1 where colors is NULL: SoftSilhouetteShader), A = 1 - prod_k (1 - p_k),
+ * p_k = sigmoid(-dists / sigma) [pix_to_face >= 0].  Backward: grad_dists [P,K] by the closed form
+ * -(1 - A) p_k / sigma (App-A.5), grad_colors [P,K,3] (slot 0 only, zeros elsewhere). */
+int acfm_sigmoid_alpha_blend(const int64_t* pix_to_face, const float* dists, const float* colors, size_t P, int K,
+                             float sigma, float* rgba, const AcfmRasterTuning* tuning, void* stream);
+int acfm_sigmoid_alpha_blend_backward(const int64_t* pix_to_face, const float* dists, const float* grad_rgba,
+                                      size_t P, int K, float sigma, float* grad_dists, float* grad_colors,
+                                      const AcfmRasterTuning* tuning, void* stream);
+/* softmax_rgb_blend (App-A.6, A.10).  Colours come from exactly one source: `colors` [P,K,3], or `atlas`
+ * [F_packed,R,R,3] sampled at `bary` as TexturesAtlas.sample_textures does (no [P,K,3] texel tensor), times
+ * `ambient` [N,3] of mesh p / pix_per_mesh when given.  Backward: grad_dists, grad_zbuf [P,K], grad_colors [P,K,3]
+ * (dense source) or grad_atlas [F_packed,R,R,3] (atlas source, scattered); nothing flows to bary or ambient. */
+int acfm_softmax_rgb_blend(const int64_t* pix_to_face, const float* dists, const float* zbuf, const float* bary,
+                           const float* colors, const float* atlas, int R, int F_packed, const float* ambient,
+                           size_t P, int K, int pix_per_mesh, const AcfmBlendParams* blend, float* rgba,
+                           const AcfmRasterTuning* tuning, void* stream);
+int acfm_softmax_rgb_blend_backward(const int64_t* pix_to_face, const float* dists, const float* zbuf,
+                                    const float* bary, const float* colors, const float* atlas, int R, int F_packed,
+                                    const float* ambient, size_t P, int K, int pix_per_mesh,
+                                    const AcfmBlendParams* blend, const float* grad_rgba, float* grad_dists,
+                                    float* grad_zbuf, float* grad_colors, float* grad_atlas, void* ws,
+                                    size_t ws_bytes, const AcfmRasterTuning* tuning, void* stream);
+/* interpolate_face_attributes: face_attrs [F_packed,3,D] -> out [P,K,D] = sum_i bary_i face_attrs[f,i,:], 0 in empty
+ * slots.  Backward: grad_bary [P,K,3], grad_face_attrs [F_packed,3,D] (scattered). */
+int acfm_interpolate_face_attributes(const int64_t* pix_to_face, const float* bary, const float* face_attrs,
+                                     size_t P, int K, int F_packed, int D, float* out,
+                                     const AcfmRasterTuning* tuning, void* stream);
+int acfm_interpolate_face_attributes_backward(const int64_t* pix_to_face, const float* bary, const float* face_attrs,
+                                              const float* grad_out, size_t P, int K, int F_packed, int D,
+                                              float* grad_bary, float* grad_face_attrs, void* ws, size_t ws_bytes,
+                                              const AcfmRasterTuning* tuning, void* stream);
+
 /* ---- atlas-textured render -----------------------------------------------------------
  * replaces NeuralRenderer.forward, texture branch with atlas=True
  * (multiframe/nnutils/nmr.py:173-200): hard raster K=1, clip_barycentric_coords=True,
