@@ -19,12 +19,17 @@ def _rel_l2(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
 
 
-@pytest.mark.parametrize("name,G,NF,H,split", [("bird", 1, 3, 96, -3), ("horse", 2, 4, 64, 1), ("cow", 3, 8, 72, 0)])
+@pytest.mark.parametrize("name,G,NF,H,split", [
+    ("bird", 1, 3, 96, -3), ("horse", 2, 4, 64, 1), ("cow", 3, 8, 72, 0),
+    ("bird", 1, 2, 57, -3), ("horse", 2, 2, 97, 0), ("cow", 1, 3, 100, 1), ("bird", 1, 1, 17, -3),
+    ("bird", 3, 100, 17, 0)])
 def test_fused_silhouette_losses(meshes, name, G, NF, H, split):
     """acfm_sil_loss_forward/backward == acfm_sil_forward + acfm_mask_losses (+ their backwards) == oracle:
     loss vector 1e-5, mask / ids identical to the plain render, gradients 1e-4 of their scale and 1e-5 relative L2;
-    references shared by G hypotheses (ref_batch), odd image sizes, forced split / unsplit blocks; two runs of
-    the fused forward are bit-identical (no atomics on that path)."""
+    references shared by G hypotheses (ref_batch); H = 64, 72, 96 (whole 8x8 blocks), 57 and 97 (odd H: partial edge
+    blocks and the scalar gt sum of the finish kernel, 97 with ref_batch < N), 100 (H = 4 mod 8) and 17 (mostly edge
+    blocks) with N = 1 and N = 300 (the finish split at 64 and at 8 chunks per mesh); forced split / unsplit blocks; two
+    runs of the fused forward are bit-identical (no atomics on that path)."""
     from acfm_video_3d_reconstruction_amd import _lib, ops
     from acfm_video_3d_reconstruction_amd.nnutils.nmr import NeuralRenderer
     d = _d()
@@ -80,11 +85,15 @@ def test_fused_silhouette_losses(meshes, name, G, NF, H, split):
     np.testing.assert_allclose(e.cpu().numpy(), eu.cpu().numpy(), rtol=1e-5, atol=1e-7)
 
 
-@pytest.mark.parametrize("name,G,NF,H,R,take_over", [("bird", 1, 3, 96, 4, False), ("cow", 2, 4, 72, 2, True)])
+@pytest.mark.parametrize("name,G,NF,H,R,take_over", [
+    ("bird", 1, 3, 96, 4, False), ("cow", 2, 4, 72, 2, True),
+    ("bird", 1, 2, 57, 3, False), ("horse", 2, 2, 97, 2, True), ("cow", 1, 3, 100, 2, False),
+    ("bird", 1, 1, 17, 2, False), ("bird", 3, 100, 17, 2, False)])
 def test_fused_texture_mse(meshes, name, G, NF, H, R, take_over):
     """acfm_tex_mse_forward / _backward_faces == acfm_tex_forward + acfm_tex_mse (+ backwards) == oracle: loss 1e-5,
     images / ids identical to the plain render, atlas gradient 1e-5; atlas and references shared by G hypotheses;
-    on a workspace taken over from the silhouette render; deterministic forward."""
+    on a workspace taken over from the silhouette render; deterministic forward; H = 72, 96, odd H = 57, 97 (the finish
+    kernel's scalar path), 100 and 17 with N = 1 and N = 300."""
     from acfm_video_3d_reconstruction_amd import ops
     from acfm_video_3d_reconstruction_amd.nnutils.nmr import NeuralRenderer
     d = _d()
@@ -127,6 +136,47 @@ def test_fused_texture_mse(meshes, name, G, NF, H, R, take_over):
     (rl * torch.from_numpy(w).double()).sum().backward()
     ga = O.tex_render_backward_atlas(rt, rtex.grad.float().numpy(), at_rep.shape).reshape(G, *atlas.shape).sum(0)
     np.testing.assert_allclose(ta.grad.cpu().numpy(), ga, rtol=1e-4, atol=1e-5 * np.abs(ga).max())
+
+
+def test_fused_silhouette_losses_f16_odd_size(meshes):
+    """storage="f16" at an odd H (partial edge blocks, scalar finish) against the float64 loss vector of the oracle's
+    mask, not only against the f32 build: the sums of |m - gt|, m gt and m + gt - m gt stay fp32 (0/1 references are
+    exact in half), the edt term sees the edt rounded to half (exact against that, 1e-3 against the unrounded one);
+    gradients within test_gpu_fp16's 2e-3 of their scale of the oracle's."""
+    from acfm_video_3d_reconstruction_amd import ops
+    d = _d()
+    rng = np.random.default_rng(97)
+    v, f = meshes["bird_v"], meshes["bird_f"]
+    G, NF, H = 2, 2, 97
+    N = G * NF
+    verts = batch_verts(v, N, rng, 0.01)
+    cams = make_cams(N, rng, extent=float(np.abs(v).max()))
+    gt = (rng.uniform(size=(NF, H, H)) > 0.5).astype(np.float32)
+    edt = rng.uniform(0, 3, (NF, H, H)).astype(np.float32)
+    w = rng.uniform(0.2, 1.0, (N, 4)).astype(np.float32)
+    tv = torch.tensor(verts, device=d, requires_grad=True)
+    tc = torch.tensor(cams, device=d, requires_grad=True)
+    los, mask, p2f = ops.sil_render_losses(tv, torch.from_numpy(f).to(d), tc, H, torch.tensor(gt, device=d),
+                                           torch.tensor(edt, device=d), storage="f16")
+    assert mask.dtype == torch.float16 and los.dtype == torch.float32
+    (los * torch.tensor(w, device=d)).sum().backward()
+    ref_mask, ref_p2f = O.sil_render(verts, f, cams, H)
+    np.testing.assert_array_equal(p2f[..., 0].long().cpu().numpy(), ref_p2f[..., 0])
+    got = los.detach().cpu().numpy()
+
+    def ref_losses(e):
+        rm = torch.from_numpy(ref_mask).double().requires_grad_(True)
+        rg, re = torch.from_numpy(np.tile(gt, (G, 1, 1))).double(), torch.from_numpy(np.tile(e, (G, 1, 1))).double()
+        m2, g2 = rm.reshape(N, -1), rg.reshape(N, -1)
+        return rm, torch.stack([O.l1_loss(rm, rg, reduce=False), (m2 * g2).sum(1), (m2 + g2 - m2 * g2).sum(1),
+                                O.edt_loss(rm, re[:, None], reduce=False)], 1)
+    rm, rl = ref_losses(edt.astype(np.float16).astype(np.float32))
+    np.testing.assert_allclose(got, rl.detach().numpy(), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(got[:, 3], ref_losses(edt)[1][:, 3].detach().numpy(), rtol=1e-3, atol=1e-7)
+    (rl * torch.from_numpy(w).double()).sum().backward()
+    gv, gc, _, _ = O.sil_render_backward(verts, f, cams, H, rm.grad.float().numpy())
+    for got_g, want, what in ((tv.grad, gv, "verts"), (tc.grad, gc, "cams")):
+        np.testing.assert_allclose(got_g.cpu().numpy(), want, rtol=0, atol=2e-3 * np.abs(want).max(), err_msg=what)
 
 
 def test_deterministic_backward_mode(meshes):
