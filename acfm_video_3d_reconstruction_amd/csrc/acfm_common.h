@@ -12,14 +12,6 @@
 
 #pragma clang fp contract(off)
 
-#ifndef ACFM_EDGE_CONST
-#define ACFM_EDGE_CONST 1   // see acfm_raster.hip
-#endif
-#ifndef ACFM_BWD_EDGE_GLOBAL
-#define ACFM_BWD_EDGE_GLOBAL 1   // see acfm_raster.hip (sil_bwd_block): measured 180.8 -> 171.4 us per 64-frame launch
-#endif
-#define ACFM_REC_EDGES (ACFM_EDGE_CONST || ACFM_BWD_EDGE_GLOBAL)
-
 #define ACFM_K_EPS 1e-8f   // PyTorch3D kEpsilon
 #define ACFM_EYE_Z 2.732f  // nmr.py:144: eye=(0,0,-2.732) -> T=(0,0,2.732)
 #define ACFM_WAVE 64
@@ -43,35 +35,30 @@ struct ProfScope {
   ~ProfScope() { prof_end(st); }
 };
 
-#ifndef ACFM_CTILE
-#define ACFM_CTILE 16
-#endif
-constexpr int CTILE = ACFM_CTILE;  // coarse tile side (pixels): k_setup leaves one face bitmask per coarse tile
+constexpr int CTILE = 16;  // coarse tile side (pixels): k_setup leaves one face bitmask per coarse tile
 
 // Per-face record of the raster workspace (k_setup writes it, the binning of the raster kernels reads it).
-// The first cache line is all the backward and nearest-face walks need; ACFM_EDGE_CONST adds what is constant per
-// FACE in the exact per-pixel distance test of the K-nearest forward -- the squared lengths of the three edges and
-// their refined reciprocals (operands of the IEEE-exact division of point_line_dist) -- computed once per face in
-// k_setup with the very operations the per-pixel code used to repeat for every pixel, so every per-pixel value is
-// bit-identical to the unfactored evaluation (and to the oracle).
+// 128 bytes.  The first 64-byte half is all the binning and the nearest-face walk need; the second holds what is
+// constant per FACE in the exact per-pixel distance test of the K-nearest forward and the silhouette backward -- the
+// squared lengths of the three edges and their refined reciprocals (operands of the IEEE-exact division of
+// point_line_dist) -- computed once per face in k_setup with the very operations the per-pixel code used to repeat for
+// every pixel, so every per-pixel value is bit-identical to the unfactored evaluation (and to the oracle).
 struct __attribute__((aligned(64))) FaceRec {
   float4 box;   // (xmin,xmax,ymin,ymax), blur margin included; degenerate face = (inf,-inf,inf,-inf)
   float4 a;     // (x0,y0,x1,x2)   -- (x1,x2), (y1,y2) as register pairs for the packed fp32 pipe
   float4 b;     // (y1,y2,z0,z1)
   float4 c;     // (z2, area, denom = area + kEps, rden = refined 1/denom)
-#if ACFM_REC_EDGES
   float4 e0;    // (|e01|^2, |e02|^2, 1/|e01|^2, 1/|e02|^2): edges v0->v1 and v0->v2, the pair the packed pipe evaluates
   float4 e1;    // (|e12|^2, 1/|e12|^2, flag = 1 if any |e|^2 <= kEps (that face takes the unfactored path), -)
   float4 pad_[2];
-#endif
 };
 
 // Workspace carve-up shared by every raster entry point (acfm_raster_workspace_bytes).
 struct RasterWs {
   float* ndc;      // [N,V,3] NDC x, NDC y, view z
-  FaceRec* rec;    // [N,F] one 64-byte record per face: the box test and the copy of a passing face touch ONE cache line
+  FaceRec* rec;    // [N,F] one 128-byte record per face: the box test and the copy of a passing face touch its first half
   int4* vidx;      // [N,F] (i0,i1,i2,-)
-  float4* mbox;    // [N,4] union of the face boxes of each of the 4 face slices of k_setup
+  float4* mbox;    // [N,slices] union of the face boxes of each face slice of k_setup (slices > 4: k_order joins them in slot 0)
   float* grad_ndc; // [N,V,2]
   long long* grad_fix; // [N,V,2] the same in 2^-36 fixed point (deterministic backward)
   int* tile_cnt;   // [N,blocks^2] faces whose box meets the 8x8 block (cost estimate for scheduling)

@@ -6,11 +6,13 @@
 // SURVEY.md App-A; the CPU oracle in oracle/acfm_oracle.c is the bit-level spec).
 //
 // Design:
-//   * k_setup: four workgroups per mesh project the V vertices into LDS (weak-perspective
-//     camera, y flip, view transform) and write one 64-byte record per face (blur-expanded box,
-//     vertices, depths), the face bitmask of every 16x16 coarse tile and a cost count per 8x8
-//     block; k_order sorts every XCD group's (mesh, block) entries heavy-first (counting sort,
-//     no atomics) and puts the blocks no face box comes near at the end.
+//   * k_setup: 4, 8 or 16 workgroups per mesh (face slices) project the V vertices into LDS
+//     (weak-perspective camera, y flip, view transform) and write one 128-byte record per face
+//     (blur-expanded box, vertices, depths, per-edge constants), the face bitmask of every 16x16
+//     coarse tile and a cost count per 8x8 block, counted in LDS and stored as one plane per slice
+//     (no zero fill, no atomics in memory); k_order adds the planes, sorts every XCD group's
+//     (mesh, block) entries heavy-first (counting sort, no atomics) and puts the blocks no face
+//     box comes near at the end.
 //   * k_raster_fwd / k_sil_bwd share one skeleton: a ONE-WAVE workgroup owns an 8x8 pixel
 //     block (four 4x4 blocks, one per 16-lane group).  Faces are binned against the block with
 //     wave ballots into an LDS candidate list (deterministic, face-ordered, no barriers); the
@@ -18,17 +20,17 @@
 //     workgroup j renders the entries j, j + stride, .. that have work and, in the forward,
 //     first stores the constant outputs of its share of the empty blocks (struct Sched).
 //   * forward, K > 1: every lane keeps its pixel's K nearest (depth|face) keys and blend
-//     factors SORTED in registers (bubble-through insertion on static register indices, 4-slot
+//     factors SORTED in registers (shift insertion on static register indices, 4-slot
 //     blocks no lane's element can enter are skipped): no per-pixel LDS or memory lists, no final
 //     sort, the blend product runs over exactly the kept faces; the block's candidates are walked
 //     roughly front to back (8 depth classes); ids leave through LDS as 16-byte stores in image
 //     order.  128 VGPRs, 4 waves per SIMD.
-//   * forward, K = 1 (blur 0): only the winner's edge distances are evaluated; 6-7 waves per SIMD.
+//   * forward, K = 1 (blur 0): only the winner's edge distances are evaluated; 6 waves per SIMD.
 //   * backward: the same walk; membership of a face in a pixel's top-K is `key <= kth[pixel]`
 //     (kth saved by the forward), gradients of a candidate are summed over the 16 lanes of its
 //     group (pair swap, then DPP row shifts on three values per lane) and TWO lanes add them to the
 //     candidate's LDS accumulator, which is flushed with one global float atomic per touched
-//     coordinate.  23 waves per CU.
+//     coordinate.  5 waves per SIMD.
 //   * forward, K > 1, ACFM_RECORD_COVER: the walk also keeps the nearest COVERING face per pixel (the
 //     hard K = 1 render's answer); k_tex_cover shades the texture render of the same geometry from it.
 //   * workgroups are dealt so that all blocks of a mesh run on one XCD (its face records stay
@@ -62,11 +64,10 @@ __device__ unsigned long long g_diag[16];
 // flagged-empty blocks -- 70 % of a 256^2 frame of the bird -- cost no workgroup dispatch of their own.
 constexpr int RBLK = 8;       // pixels per block side: one wave64 per block
 constexpr int RT = 64;        // threads per raster workgroup = RBLK*RBLK
-constexpr int RCAP = 128;     // LDS candidate-list capacity of a block (walked early when it could overflow)
 constexpr int TPB = 256;      // threads per workgroup of the per-mesh kernels (setup, projection)
 constexpr unsigned long long KEY_NONE = ~0ull;
 constexpr int CNT_TILE = 8;   // cost counters per 8x8 pixels (= per raster block)
-constexpr int SETUP_LDS_TILES = 4096;  // counters kept in LDS up to 1024x1024 images
+constexpr int SETUP_LDS_TILES = 4096;  // counters kept in LDS up to 512x512 images (64^2 blocks)
 constexpr int ENTRY_EMPTY = 1 << 30;   // order entry flag: no face box comes near this block
 constexpr int ENTRY_SPLIT = 1 << 29;   // order entry flag: a heavy block, rendered by four workgroups (one per 4x4 pixels)
 constexpr int ENTRY_FLAGS = ENTRY_EMPTY | ENTRY_SPLIT;
@@ -82,8 +83,10 @@ constexpr int FLCAP = 512;    // LDS face-id list of one wave (faces of its coar
 // Grid (N, ws.slices): every workgroup projects the mesh's V vertices into LDS (cheap, and it
 // keeps the slices independent) and handles one slice of the faces; slice boundaries are multiples
 // of 64 faces, so each slice owns whole words of the coarse masks and builds them in LDS without
-// talking to the others.  Tile counters are summed into zeroed memory with global atomics, the
-// mesh box is left as one box per slice (the raster kernels take the union of the four).
+// talking to the others.  Tile counters are kept in LDS and leave as one plane per slice with plain
+// stores (k_order adds the planes: no zero fill, no global atomics); only images beyond 512^2 fall
+// back to global atomics on a zeroed ws.tile_cnt.  The mesh box is left as one box per slice (the
+// raster kernels take the union of four; k_order joins 8 or 16 into the first slot).
 __host__ __device__ __forceinline__ int setup_slice_faces(int F, int slices) {
   return ((F + slices - 1) / slices + 63) / 64 * 64;
 }
@@ -185,14 +188,12 @@ __global__ __launch_bounds__(TPB) void k_setup(const float* __restrict__ verts,
     {
       const float denom = area + ACFM_K_EPS;
       r.c = make_float4(z2, area, denom, recip_refined(denom));
-#if ACFM_REC_EDGES
       // point_line_dist's own operations on (a, b) = (v0, v1), (v0, v2), (v1, v2): bax = bx - ax, l2 = bax bax + bay bay
       const float e01x = x1 - x0, e01y = y1 - y0, e02x = x2 - x0, e02y = y2 - y0, e12x = x2 - x1, e12y = y2 - y1;
       const float l01 = e01x * e01x + e01y * e01y, l02 = e02x * e02x + e02y * e02y, l12 = e12x * e12x + e12y * e12y;
       const bool deg = (l01 <= ACFM_K_EPS) || (l02 <= ACFM_K_EPS) || (l12 <= ACFM_K_EPS);
       r.e0 = make_float4(l01, l02, recip_refined(l01), recip_refined(l02));
       r.e1 = make_float4(l12, recip_refined(l12), deg ? 1.0f : 0.0f, 0.0f);
-#endif
     }
     ws.vidx[o] = make_int4(i0, i1, i2, 0);
     ws.fvis[o] = 0;
@@ -548,7 +549,7 @@ struct Cand {
   float4 box, a, b;
   float2 c;      // (z2, denom = area + kEps)
   float rden;    // refined 1 / denom (k_setup's, the very operations the per-pixel code used to repeat)
-  int fid, idx;  // idx: list position (the ACFM_EDGE_CONST walk reads L.e0 / L.e1[idx] when it reaches the distance stage)
+  int fid, idx;  // idx: list position (the K-nearest walk reads L.e0 / L.e1[idx] when it reaches the distance stage)
 };
 
 template <class LT, class = void> struct has_edge_const : std::false_type {};
@@ -669,7 +670,7 @@ __device__ __forceinline__ void walk_wave(LT& L, const Tile& t, int H, int list_
     // (A1') front to back, roughly: the wave's list is dealt into 8 depth classes (nearest vertex of
     // the face, classes between the block's nearest and farthest) by a counting sort with ballots.
     // Results never depend on the order of the candidates, the cost of the walk does: a face that
-    // arrives after the nearer ones enters a pixel's sorted list near its end, the bubble insertion
+    // arrives after the nearer ones enters a pixel's sorted list near its end, the insertion
     // skips the leading 4-slot blocks it cannot touch, and once a list is full the faces behind it
     // fail the depth test before their edge distances are computed.
     if (nw > 8) {
@@ -780,29 +781,14 @@ __device__ __forceinline__ void walk_wave(LT& L, const Tile& t, int H, int list_
   }
   // a group that has run out of faces (or has none) keeps loading its last (or the tile's
   // first) record: harmless, the lanes are masked by `have`.  (Prefetching the next record one
-  // iteration ahead was measured: +16 VGPRs, no change in time.)
+  // iteration ahead was measured: +16 VGPRs, no change in time.  Reading only the list position of
+  // the next candidate one iteration ahead -- one LDS round trip per iteration instead of two -- was
+  // measured too (64 frames, A/B on one box, twice): 192.7 / 193.4 us with it, 189.9 / 192.5 without.)
   const int last = max(my_n - 1, 0);
-#ifndef ACFM_WALK_PREFETCH
-#define ACFM_WALK_PREFETCH 0   // measured (64 frames, A/B on one box, twice): 192.7 / 193.4 us with it, 189.9 / 192.5 without
-#endif
-#if ACFM_WALK_PREFETCH
-  // the list position of the NEXT iteration's candidate is read one iteration ahead: the walk's dependent chain per
-  // iteration is then one LDS round trip (the record) instead of two (sub-list byte -> record)
-  int nxt = my_n > 0 ? (split ? grp : (int)sub[0]) : 0;
-#endif
   if constexpr (SHARE) prep(-1);
   for (int i = 0; i < n_max; ++i) {
-#if ACFM_WALK_PREFETCH
-    const int ci = nxt;
-    {
-      const int l2 = min(i + 1, last);
-      nxt = my_n > 0 ? (split ? 4 * l2 + grp : (int)sub[l2]) : 0;
-    }
-    const Cand cur = load_cand(L, ci);
-#else
     const int li = min(i, last);
     const Cand cur = load_cand(L, my_n > 0 ? (split ? 4 * li + grp : (int)sub[li]) : 0);
-#endif
     const bool have = i < my_n;
     const bool in_box = have &&
         !((t.xf > cur.box.y) | (t.xf < cur.box.x) | (t.yf > cur.box.w) | (t.yf < cur.box.z));
@@ -833,17 +819,13 @@ __device__ __forceinline__ int wave_inclusive_scan(int x, int lane) {
   return x;
 }
 
-// ACFM_MBOX_TEST: the mesh-box early-out in front of the mask loads.  It looks redundant beside k_order's empty flag,
-// but the flag comes from counts per 16x16 pixels: without the test the K = 20 kernels measured 6-7 us slower each
-// (blocks next to the mesh that bin a mask row to find nothing), the K = 1 kernel 2 us faster.
-#ifndef ACFM_MBOX_TEST
-#define ACFM_MBOX_TEST 1
-#endif
+// The mesh-box early-out in front of the mask loads looks redundant beside k_order's empty flag, but the flag comes
+// from counts per 16x16 pixels: without the test the K = 20 kernels measured 6-7 us slower each (blocks next to the
+// mesh that bin a mask row to find nothing), the K = 1 kernel 2 us faster.
 template <class LT, class Walk>
 __device__ __forceinline__ void bin_and_walk(const RasterWs& ws, const Tile& t, int F, int H, LT& L,
                                              fl_t* s_fl /* [FLCAP] */, float box_shrink, Walk&& walk) {
   if (t.empty) return;  // flagged by k_order: no face box near this block
-#if ACFM_MBOX_TEST
   {
   // the mesh's box: the four slices' boxes (the usual case), or slot 0 where k_order joined 8 or 16 of them
   float4 mb = ws.mbox[(size_t)t.n * ws.slices];
@@ -856,7 +838,6 @@ __device__ __forceinline__ void bin_and_walk(const RasterWs& ws, const Tile& t, 
   }
   if (t.t_xmin > mb.y || t.t_xmax < mb.x || t.t_ymin > mb.w || t.t_ymax < mb.z) return;
   }
-#endif
   const unsigned long long lt = (1ull << t.lane) - 1ull;
   const int ctiles = (H + CTILE - 1) / CTILE, words = (F + 63) / 64;
   const int cty = (t.yi & ~7) / CTILE, ctx = (t.xi & ~7) / CTILE;
@@ -919,9 +900,7 @@ __device__ __forceinline__ void bin_and_walk(const RasterWs& ws, const Tile& t, 
         L.b[pos] = ws.rec[o].b;
         const float4 c4 = ws.rec[o].c;
         L.c[pos] = make_float4(c4.x, c4.z, c4.w, __int_as_float(f));
-#if ACFM_EDGE_CONST
         if constexpr (has_edge_const<LT>::value) { L.e0[pos] = ws.rec[o].e0; L.e1[pos] = ws.rec[o].e1; }
-#endif
       }
       list_n += __popcll(bal);
     }
@@ -996,7 +975,7 @@ __device__ __forceinline__ bool test_face_dist(float xf, float yf, const float4&
   return inside || !(d >= blur);
 }
 
-// The same with the per-edge constants of the candidate (ACFM_EDGE_CONST): E0 = (|e01|^2, |e02|^2, r01, r02),
+// The same with the per-edge constants of the candidate: E0 = (|e01|^2, |e02|^2, r01, r02),
 // E1 = (|e12|^2, r12, degenerate flag, -).  Operation for operation point_line_dist / point_line_dist2 minus what does
 // not depend on the pixel; a face with a degenerate edge (flag) must take test_face_dist (its distance-to-endpoint branch).
 __device__ __forceinline__ bool test_face_dist_e(float xf, float yf, const float4& A, const float4& B, const float4& E0,
@@ -1031,33 +1010,19 @@ __device__ __forceinline__ bool test_face_dist_e(float xf, float yf, const float
   return inside || !(d >= blur);
 }
 
-template <bool CLIP>
-__device__ __forceinline__ bool test_face(float xf, float yf, const float4& A, const float4& B,
-                                          float z2, float denom, float rden, float blur, Hit& h) {
-  bool inside;
-  if (!test_face_depth<CLIP>(xf, yf, A, B, z2, denom, rden, h, inside)) return false;
-  return test_face_dist(xf, yf, A, B, blur, inside, h);
-}
-
 // blend probability sigmoid(-sd/sigma) = 1 / (1 + 2^(sd * log2(e)/sigma)) as mul + v_exp_f32 + add +
 // v_rcp_f32 (4 instructions; the IEEE division sd/sigma + library expf + reciprocal were 33, most of them
 // half-rate selects / compares -- tools/ubench/valu_rates.hip).  Error budget against the oracle's exact
 // expf: the product rounds once (|arg| <= 13.3 up to the blur radius: 5.5e-7 relative on 2^arg where
 // p ~ 1e-4, nothing where p ~ 0.5), v_exp_f32 and v_rcp_f32 are 1 ulp each: |dp| <= p (1 - p) 2e-7 + 6e-8 p
 // <= 1e-7 per face; measured on the parity sweep: masks within 4e-7 (bar 1e-6).  Inside faces (sd < 0, far
-// from the edge) underflow to p = 1 exactly like expf does.  Face ids never depend on p.
-#ifndef ACFM_FAST_SIGMOID
-#define ACFM_FAST_SIGMOID 1
-#endif
+// from the edge) underflow to p = 1 exactly like expf does.  Face ids never depend on p.  (The library form,
+// sigmoid_neg of acfm_common.h, stays where a pixel evaluates it once: k1_finish, acfm_shade.hip.)
 __device__ __forceinline__ float sigmoid_scale(float sigma) {   // wave-uniform: kept in an SGPR
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(1.44269504088896341f / sigma)));
 }
 __device__ __forceinline__ float sigmoid_neg_fast(float sd, float sigma, float scale) {
-#if ACFM_FAST_SIGMOID
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(sd * scale));
-#else
-  return __builtin_amdgcn_rcpf(1.0f + expf(sd / sigma));
-#endif
 }
 
 // (depth, face) key: pz >= 0 so its bit pattern orders like the float; +0.0f folds -0.0 into
@@ -1074,17 +1039,11 @@ typedef _Float16 half_t;
 __device__ __forceinline__ float ld_real(const void* p, size_t i, int h16) {
   return h16 ? (float)reinterpret_cast<const half_t*>(p)[i] : reinterpret_cast<const float*>(p)[i];
 }
-#ifndef ACFM_OUT_NT
-#define ACFM_OUT_NT 0
-#endif
+// (plain stores, also in st_face: non-temporal ones on these 4-byte-per-pixel planes measured 75 -> 123 us on the
+// texture forward, see fwd_fill_block)
 __device__ __forceinline__ void st_real(void* p, size_t i, float v, int h16) {
-#if ACFM_OUT_NT
-  if (h16) __builtin_nontemporal_store((half_t)v, reinterpret_cast<half_t*>(p) + i);
-  else __builtin_nontemporal_store(v, reinterpret_cast<float*>(p) + i);
-#else
   if (h16) reinterpret_cast<half_t*>(p)[i] = (half_t)v;
   else reinterpret_cast<float*>(p)[i] = v;
-#endif
 }
 __device__ __forceinline__ float4 ld4_real(const void* p, size_t i4, int h16) {   // elements 4 i4 .. 4 i4 + 3 (aligned)
   if (!h16) return reinterpret_cast<const float4*>(p)[i4];
@@ -1093,13 +1052,8 @@ __device__ __forceinline__ float4 ld4_real(const void* p, size_t i4, int h16) { 
   return make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
 }
 __device__ __forceinline__ void st_face(void* p, size_t i, long long id, int h16) {   // nearest-face plane
-#if ACFM_OUT_NT
-  if (h16) __builtin_nontemporal_store((int32_t)id, reinterpret_cast<int32_t*>(p) + i);
-  else __builtin_nontemporal_store((int64_t)id, reinterpret_cast<int64_t*>(p) + i);
-#else
   if (h16) reinterpret_cast<int32_t*>(p)[i] = (int32_t)id;
   else reinterpret_cast<int64_t*>(p)[i] = (int64_t)id;
-#endif
 }
 
 struct FwdOut {
@@ -1159,24 +1113,15 @@ __device__ __forceinline__ void mark_visible(const RasterWs& ws, const FwdOut& o
 // at or beyond it are still empty in every lane, so blocks that lie wholly beyond it are skipped
 // with scalar branches while every register index stays a compile-time constant.
 //
-// ACFM_INSERT_SHIFT = 1 (shipping): SHIFT form, top block first.  With P_k = (x < key[k]) the new list is
+// SHIFT form, top block first (called as shift_insert_block<K, (K - 1) / 4>).  With P_k = (x < key[k]) the new list is
 //   key'[k] = P_k ? (P_{k-1} ? key[k-1] : x) : key[k]        (P_{-1} = false; sorted list: P_{k-1} implies P_k)
 // evaluated for k descending, in place: slot k reads only the OLD slots k and k-1 and x itself never changes.
-// Per slot one 64-bit compare + six selects, like the compare-exchange of the bubble form (0), but
-//   * no register copies: the bubble form carries the displaced element from slot to slot, and the compiler kept the
-//     old and the new 64-bit key of a slot in different register pairs (their 32-bit halves overlap in time), which
-//     cost 4 v_mov_b64 + 4 v_mov_b32 per 4-slot block -- a fifth of the insertion's instructions;
-//   * the compares of a block are independent of its selects (no v_cmp -> s_nop -> v_cndmask chains);
-//   * the walk is top-down, so the first block no lane's element enters ENDS the insertion (everything below holds
-//     smaller keys): the bubble form tested every block below the insertion point one by one.
-// Lanes that do not insert are masked by exec (their compare bits are 0).  Results are identical: both forms
-// produce THE sorted list of the K smallest keys (keys are unique per pixel: the face id is part of the key).
-#ifndef ACFM_ASM_SLOT
-#define ACFM_ASM_SLOT 1
-#endif
-#ifndef ACFM_INSERT_SHIFT
-#define ACFM_INSERT_SHIFT 1
-#endif
+// Per slot one 64-bit compare + six selects.  The walk is top-down, so the first block no lane's element enters ENDS
+// the insertion (everything below holds smaller keys).  Lanes that do not insert are masked by exec (their compare
+// bits are 0).  The compare goes through the wave mask + inverse ballot: a plain `x < key[k]` lets the two selects of
+// a pair be canonicalised into a 64-bit umin / umax, which the backend expands into two compares plus register copies.
+// (It replaced a bubble form -- compare-exchange from slot 0 upwards, carrying the displaced element -- which cost
+// 4 v_mov_b64 + 4 v_mov_b32 of register copies per 4-slot block and tested every block below the insertion point.)
 __device__ __forceinline__ unsigned long long key_lt_mask(unsigned long long x, unsigned long long k) {
   return __builtin_amdgcn_uicmpl(x, k, 36 /* ICMP_ULT */);   // one v_cmp_lt_u64 into an SGPR pair (lanes off: 0)
 }
@@ -1184,18 +1129,12 @@ template <int K, int B>   // block B = slots [4B, min(4B + 4, K)), called for B 
 __device__ __forceinline__ void shift_insert_block(unsigned long long (&key)[K], float (&q)[K], const unsigned long long x,
                                                    const float xq, int lim) {
   constexpr int LO = 4 * B, HI = (LO + 4 < K ? LO + 4 : K);
-#ifndef ACFM_INSERT_FILLTEST
-#define ACFM_INSERT_FILLTEST 0   // measured: 197.1 us with it, 197.5 without (A/B on one box): within noise, and it costs three registers
-#endif
-  bool beyond = lim <= LO;   // (the list holds at most lim entries after this insertion: slots >= lim stay empty in every lane)
-#if ACFM_INSERT_FILLTEST
-  // `lim` counts the faces WALKED, a loose bound on the faces a pixel KEPT: if slot LO - 1 is still empty in every
-  // inserting lane, every insertion point lies below this block and it would only shift empties into empties
-  // (one 32-bit compare -- the depth word of an empty slot is all ones, no depth >= 0 is -- instead of the block)
-  if constexpr (LO > 0) {
-    if (!beyond) beyond = __builtin_amdgcn_uicmp((unsigned)(key[LO - 1] >> 32), 0xffffffffu, 33 /* ICMP_NE */) == 0ull;
-  }
-#endif
+  // (the list holds at most lim entries after this insertion: slots >= lim stay empty in every lane.  `lim` counts the
+  // faces WALKED, a loose bound on the faces a pixel KEPT; also testing whether slot LO - 1 is still empty in every
+  // inserting lane measured 197.1 us against 197.5 without, A/B on one box: within noise, and it costs three registers)
+  // (a flag and its negation, not `if (lim > LO)`: the two compile to different code for K >= 8 -- the direct form came
+  // out ~30 instructions shorter per kernel, unmeasured -- and this is the form the recorded timings belong to)
+  bool beyond = lim <= LO;
   if (!beyond) {
     DIAG_ADD(9, 1);
     unsigned long long pk = key_lt_mask(x, key[HI - 1]);
@@ -1216,69 +1155,23 @@ __device__ __forceinline__ void shift_insert_block(unsigned long long (&key)[K],
   if constexpr (B > 0) shift_insert_block<K, B - 1>(key, q, x, xq, lim);
 }
 
-template <int K, int LO>
-__device__ __forceinline__ void bubble_insert(unsigned long long (&key)[K], float (&q)[K],
-                                              unsigned long long& x, float& xq, int lim) {
-#if ACFM_INSERT_SHIFT
-  static_assert(LO == 0, "the shift form inserts into the whole list");
-  shift_insert_block<K, (K - 1) / 4>(key, q, x, xq, lim);
-#else
-  // The list is sorted, so key[HI-1] is the largest of the block: if no active lane's element is
-  // smaller, nothing moves in these four slots (the new face lies deeper than all of them in every
-  // lane -- faces arrive in id order, not in depth order) and the block costs one compare.
-  constexpr int HI = (LO + 4 < K ? LO + 4 : K);
-  DIAG_ADD(9, 1);
-  if (__ballot(x < key[HI - 1]) != 0ull) {
-    DIAG_ADD(8, 1);
-#pragma unroll
-    for (int k = LO; k < HI; ++k) {
-#if ACFM_ASM_SLOT
-      // ONE 64-bit compare + six selects.  (With a plain `x < key[k]` the two selects of a pair are
-      // canonicalised into a 64-bit umin / umax, which the backend expands into TWO compares plus register
-      // copies: 9.5 half-rate instructions per slot instead of 7.  The wave-mask compare + inverse ballot
-      // is opaque to that transformation and costs nothing: the mask stays in VCC.)
-      const bool sw = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_uicmpl(x, key[k], 36 /* ICMP_ULT */));
-      const unsigned long long tk = key[k];
-      const float tq = q[k];
-      key[k] = sw ? x : tk; x = sw ? tk : x;
-      q[k] = sw ? xq : tq;  xq = sw ? tq : xq;
-#else
-      const bool sw = x < key[k];
-      const unsigned long long tk = key[k];
-      const float tq = q[k];
-      key[k] = sw ? x : tk; x = sw ? tk : x;
-      q[k] = sw ? xq : tq;  xq = sw ? tq : xq;
-#endif
-    }
-  }
-  if constexpr (LO + 4 < K) {
-    if (lim > LO + 4) bubble_insert<K, LO + 4>(key, q, x, xq, lim);
-  }
-#endif
-}
-
 // LDS of a forward workgroup (one wave).  The nearest-face kernels keep a 64-slot candidate list
 // (5.5 KB: the register budget, not LDS, then bounds the waves per SIMD -- measured on the
 // backward: 13.8 KB -> 6.9 KB per wave = 292 -> 256 us); the K-nearest kernels are register-bound
 // at 4 waves per SIMD and get 10 240 B each (16 one-wave workgroups per CU): with every slot of pix_to_face stored
 // (k_out = K) that is exactly the staging area of the block's ids, a union with the lists.
-// (The per-pixel-list forward walk of round 2, ACFM_FWD_V2, lives in tools/variants/fwd_v2_per_pixel_lists.inc.)
+// (The per-pixel-list forward walk of round 2 lives in tools/variants/fwd_v2_per_pixel_lists.inc.)
 //
-// ACFM_EDGE_CONST (K-nearest kernels): a candidate carries, besides its record, what the exact per-pixel distance
+// Per-edge constants (K-nearest kernels): a candidate carries, besides its record, what the exact per-pixel distance
 // test needs per EDGE and not per pixel -- |e|^2 and the refined reciprocal 1/|e|^2 of the three edges (operands of
 // the IEEE-exact division of point_line_dist) and a flag for an edge with |e|^2 <= kEps -- computed once per face by
 // k_setup with the very operations the walk used to repeat for every (pixel, face) pair: two more 16-byte LDS
 // entries per candidate (32 B), ~33 instruction slots fewer per walk iteration, bit-identical values.
-#ifndef ACFM_EDGE_CONST
-#define ACFM_EDGE_CONST 1
-#endif
-#ifndef ACFM_FWD_CAP
-#define ACFM_FWD_CAP (ACFM_EDGE_CONST ? 88 : RCAP)   // 96 B x 88 + sub-lists + id list + cull lists = 10 208 B <= 10 240
-#endif
+constexpr int FWD_CAP = 88;   // K-nearest candidate list: 96 B x 88 + sub-lists + id list + cull lists = 10 208 B <= 10 240
 template <int CAP_>
 struct CandListET : CandListT<CAP_> {
-  float4 e0[CAP_];   // (|e01|^2, 1/|e01|^2, |e02|^2, 1/|e02|^2)   -- the pair the packed pipe evaluates together
-  float4 e1[CAP_];   // (|e12|^2, 1/|e12|^2, degenerate flag, -)
+  float4 e0[CAP_];   // FaceRec::e0: (|e01|^2, |e02|^2, 1/|e01|^2, 1/|e02|^2)   -- the pair the packed pipe evaluates together
+  float4 e1[CAP_];   // FaceRec::e1: (|e12|^2, 1/|e12|^2, degenerate flag, -)
 };
 template <int CAP, int MIN_BYTES, bool EDGE>
 struct FwdLdsT {
@@ -1292,27 +1185,18 @@ struct FwdLdsT {
     char stage[MIN_BYTES > 16 ? MIN_BYTES : 16];   // the block's K ids in image order (the lists are dead by then)
   };
 };
-template <int K> using FwdLdsK = FwdLdsT<(K > 1 ? ACFM_FWD_CAP : 64), (K > 1 ? 64 * K * 8 : 0), (K > 1 && ACFM_EDGE_CONST)>;
-#ifndef ACFM_NO_LDS_ASSERT
+template <int K> using FwdLdsK = FwdLdsT<(K > 1 ? FWD_CAP : 64), (K > 1 ? 64 * K * 8 : 0), (K > 1)>;
 static_assert(sizeof(FwdLdsK<20>) <= 10240, "the K = 20 forward runs 16 one-wave workgroups per CU: 10 240 B of LDS each");
-#endif
 
 
 // Constant outputs of a flagged-empty 8x8 block (no face box comes near it): exactly what
 // fwd_block leaves for a block without candidates.  Lane i owns pixel (i / 8, i % 8) of the block;
 // the K ids of the soft kernel go out as 16-byte pieces in image order (8 rows of 64 K bytes).
 // The K-slot pix_to_face stores (160 B per pixel at K = 20: whole lines, never read by this library) go out
-// non-temporal: -7 us on the K = 20 forward.  The 4-byte-per-pixel planes must NOT (ACFM_OUT_NT=1 measured 75 ->
-// 123 us on the texture forward): a block row of such a plane is a 32-byte fragment and the four fragments of a
-// line meet in L2.
-#ifndef ACFM_P2F_NT
-#define ACFM_P2F_NT 1
-#endif
-#if ACFM_P2F_NT
+// non-temporal: -7 us on the K = 20 forward.  The 4-byte-per-pixel planes must NOT (non-temporal st_real / st_face
+// measured 75 -> 123 us on the texture forward): a block row of such a plane is a 32-byte fragment and the four
+// fragments of a line meet in L2.
 #define P2F_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define P2F_STORE(ptr, val) (*(ptr) = (val))
-#endif
 template <int K, bool TEX>
 __device__ __forceinline__ void fwd_fill_block(const FwdOut& out, int n, int by, int bx, int H, int lane) {
   const int yi = by + (lane >> 3), xi = bx + (lane & 7);
@@ -1550,8 +1434,8 @@ __device__ __forceinline__ void fwd_block(const RasterWs& ws, const Tile& t, int
     k1_finish<CLIP, TEX>(ws, t, F, H, sigma, out, bestkey, bestsd, bestb0, bestb1, bestb2, dist_late);
   } else {
     // Per-pixel top-K list: K (depth|face) keys + their blend factors (1 - p), kept SORTED in
-    // registers.  A new face is bubbled through the array with compare-exchanges on static
-    // register indices (the displaced farthest entry falls off the end), so there is no LDS or
+    // registers.  A new face is inserted with compares and selects on static
+    // register indices (shift_insert_block; the farthest entry falls off the end), so there is no LDS or
     // memory list, no final sort and the kept set is exactly the K nearest at every moment.
     const float sig_scale = out.sig_scale;
     unsigned long long key[K];
@@ -1564,13 +1448,7 @@ __device__ __forceinline__ void fwd_block(const RasterWs& ws, const Tile& t, int
     DIAG_ADD(0, 1);
     bin_and_walk(ws, t, F, H, L, s_fl, out.box_shrink, [&](int list_n) {
       DIAG_ADD(1, 1); DIAG_ADD(2, list_n);
-#ifdef ACFM_DIAG_NO_WALK
-      if (list_n >= 0) { seen += list_n; return; }
-#endif
       walk_wave<true>(L, t, H, list_n, blur, s_wl, [&](const Cand& cd, bool in_box, int ord) {
-#ifdef ACFM_DIAG_NO_BODY
-        if (ord >= 0) return;
-#endif
         // stage 1 (depth): a face that is not nearer than the K-th kept face of a full list
         // cannot enter it; when that holds for every lane of the wave the face is dropped
         // before its edge distances are computed (empty slots hold ~0, so x < key[K-1] is
@@ -1602,10 +1480,6 @@ __device__ __forceinline__ void fwd_block(const RasterWs& ws, const Tile& t, int
         if (__ballot(live) == 0ull) return;
         DIAG_ADD(5, 1); DIAG_ADD(6, __popcll(__ballot(live)));
         if (!live) return;
-#ifdef ACFM_DIAG_NO_STAGE2
-        h.sd = h.pz;
-#else
-#if ACFM_EDGE_CONST
         // (read here, not with the record: 8 registers that need not live through the depth stage)
         const float4 e1 = L.e1[cd.idx];
         if (__ballot(e1.z != 0.0f) != 0ull) {   // (rare: some lane's face has an edge shorter than sqrt(kEps))
@@ -1613,10 +1487,6 @@ __device__ __forceinline__ void fwd_block(const RasterWs& ws, const Tile& t, int
         } else {
           if (!test_face_dist_e(t.xf, t.yf, cd.a, cd.b, L.e0[cd.idx], e1, blur, inside, h)) return;
         }
-#else
-        if (!test_face_dist(t.xf, t.yf, cd.a, cd.b, blur, inside, h)) return;
-#endif
-#endif
         DIAG_ADD(7, __popcll(__ballot(true))); DIAG_ADD(11, 1);
 #ifdef ACFM_DIAG_COUNT
         {   // (group, face) pairs with at least one accepting pixel
@@ -1625,11 +1495,7 @@ __device__ __forceinline__ void fwd_block(const RasterWs& ws, const Tile& t, int
         }
 #endif
         float xq = 1.0f - sigmoid_neg_fast(h.sd, sigma, sig_scale);
-#ifdef ACFM_DIAG_NO_INSERT
-        if (x < key[0]) { key[0] = x; q[0] = xq; }
-#else
-        bubble_insert<K, 0>(key, q, x, xq, __builtin_amdgcn_readfirstlane(seen + ord + 1));
-#endif
+        shift_insert_block<K, (K - 1) / 4>(key, q, x, xq, __builtin_amdgcn_readfirstlane(seen + ord + 1));
       });
       seen += list_n;
     });
@@ -1637,7 +1503,7 @@ __device__ __forceinline__ void fwd_block(const RasterWs& ws, const Tile& t, int
     if (split) {
       // The four 16-lane groups hold the K nearest of their quarter of the candidates for the same
       // 16 pixels.  Merge: group 0 takes group 1's entries and group 2 takes group 3's, then group 0
-      // takes group 2's; an entry enters by the same bubble insertion (the K nearest of a union are
+      // takes group 2's; an entry enters by the same insertion (the K nearest of a union are
       // the K nearest of the two K-nearest lists).  Senders keep their lists untouched while they
       // are being read; lists are sorted, so a round ends at the first empty slot of every sender.
 #pragma unroll
@@ -1650,7 +1516,7 @@ __device__ __forceinline__ void fwd_block(const RasterWs& ws, const Tile& t, int
           const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(key[k] >> 32), mask, 64);
           float oq = __shfl_xor(q[k], mask, 64);
           unsigned long long ok = recv ? (((unsigned long long)hi << 32) | lo) : KEY_NONE;
-          if (__ballot(ok != KEY_NONE) != 0ull) bubble_insert<K, 0>(key, q, ok, oq, K);
+          if (__ballot(ok != KEY_NONE) != 0ull) shift_insert_block<K, (K - 1) / 4>(key, q, ok, oq, K);
         }
       }
     }
@@ -1747,11 +1613,9 @@ __device__ __forceinline__ void fwd_block(const RasterWs& ws, const Tile& t, int
 
 // waves per SIMD the K = 1 kernels are compiled for: 4, 5 and 6 measured the same 70 us on the texture forward (it is
 // VALU-issue bound, 78 % busy, not latency bound), 7 and 8 spill (75 and 90 us)
-#ifndef ACFM_K1_WAVES
-#define ACFM_K1_WAVES 6
-#endif
+constexpr int K1_WAVES = 6;
 template <int K, bool CLIP, bool TEX>
-__global__ __launch_bounds__(RT, K > 20 ? 2 : K == 1 ? ACFM_K1_WAVES : 4) void k_raster_fwd(RasterWs ws, int N, int F, int H, float blur,
+__global__ __launch_bounds__(RT, K > 20 ? 2 : K == 1 ? K1_WAVES : 4) void k_raster_fwd(RasterWs ws, int N, int F, int H, float blur,
                                                     float sigma, FwdOut out) {
   __shared__ __attribute__((aligned(16))) FwdLdsK<K> S;
   const Sched sc = make_sched(ws, N, H, K > 1);   // the K-nearest kernels split their heaviest blocks
@@ -1778,22 +1642,17 @@ __global__ __launch_bounds__(RT, K > 20 ? 2 : K == 1 ? ACFM_K1_WAVES : 4) void k
     // blocks are neighbours in the image and their 32-byte row fragments meet in L2 as whole lines
     const int n_empty = sc.per - sc.n_work, chunk = (n_empty + sc.stride - 1) / sc.stride;
     const int e0 = sc.n_work + sc.j0 * chunk, e1 = min(sc.per, e0 + chunk);
-#ifdef ACFM_DIAG_NO_FILL
-    constexpr bool no_fill = K == 1;
-#else
-    constexpr bool no_fill = false;
-#endif
     if ((H & (RBLK - 1)) == 0) {
       const FillLane<K> fl = make_fill_lane<K>(H, lane);
 #pragma unroll 1
-      for (int e = e0; e < e1 && !no_fill; ++e) {
+      for (int e = e0; e < e1; ++e) {
         int n, by, bx;
         entry_block(ws.order[(size_t)sc.g * sc.per + e], sc, H, n, by, bx);
         fwd_fill_block_whole<K, TEX>(out, n, by, bx, H, lane, fl);
       }
     } else {
 #pragma unroll 1
-      for (int e = e0; e < e1 && !no_fill; ++e) {
+      for (int e = e0; e < e1; ++e) {
         int n, by, bx;
         entry_block(ws.order[(size_t)sc.g * sc.per + e], sc, H, n, by, bx);
         fwd_fill_block<K, TEX>(out, n, by, bx, H, lane);
@@ -1803,9 +1662,6 @@ __global__ __launch_bounds__(RT, K > 20 ? 2 : K == 1 ? ACFM_K1_WAVES : 4) void k
 #pragma unroll 1
   for (int e = sc.j0; e < sc.e_end; e += sc.stride) {
     const Tile t = make_tile(ws, sc, e, N, H, K > 1);
-#ifdef ACFM_DIAG_NO_WORK
-    if (K == 1) continue;
-#endif
     if (!t.none) {
 #ifdef ACFM_DIAG
       if (out.dbg) {
@@ -1943,19 +1799,6 @@ __global__ __launch_bounds__(64 * COVER_WPB) void k_tex_cover(RasterWs ws, int N
 }
 
 // ------------------------------------------------------------------------------- backward
-// Sum over the 16 lanes of a DPP row (= one 4x4 pixel block): four row shifts, the total lands
-// in lane 15 of the row.
-__device__ __forceinline__ float row_sum_dpp(float v) {
-#define ACFM_DPP_ADD(ctrl) \
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, true))
-  ACFM_DPP_ADD(0x111);  // row_shr:1
-  ACFM_DPP_ADD(0x112);  // row_shr:2
-  ACFM_DPP_ADD(0x114);  // row_shr:4
-  ACFM_DPP_ADD(0x118);  // row_shr:8
-#undef ACFM_DPP_ADD
-  return v;
-}
-
 // PointLineDistanceBackward with the clamped t held constant.  t is the forward's own clamped
 // parameter (point_line_dist, same expression; 1 for a degenerate segment: then q = b exactly, the gradient of a
 // is g 0 e = 0 and that of b is g 2 (b - p) = -2 (p - b) g, the degenerate branch of the reference bit for bit).
@@ -1968,10 +1811,7 @@ __device__ __forceinline__ void point_line_dist_bwd(float px, float py, float ax
   gbx = g * t * ex; gby = g * t * ey;
 }
 
-#ifndef ACFM_BWD_CAP
-#define ACFM_BWD_CAP 64
-#endif
-constexpr int BWD_CAP = ACFM_BWD_CAP;   // candidate-list capacity of the backward (LDS per wave: 108 B per slot)
+constexpr int BWD_CAP = 64;   // candidate-list capacity of the backward (LDS per wave: 108 B per slot)
 using BwdList = CandListT<BWD_CAP>;
 // Upstream gradient of the mask: either given per pixel (grad_mask) or, for the fused render+loss operator,
 // formed on the fly from the references and the per-mesh gradients of the four loss terms -- k_mask_losses_bwd's
@@ -2000,9 +1840,6 @@ __device__ __forceinline__ void acc_add_raw(float* p, float v) { atomicAdd(p, v)
 __device__ __forceinline__ void acc_add_raw(long long* p, long long v) {
   atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
 }
-#ifndef ACFM_BWD_SHARE
-#define ACFM_BWD_SHARE 1
-#endif
 template <class AccT>
 __device__ __forceinline__ void sil_bwd_block(const RasterWs& ws, const Tile& t, const void* __restrict__ mask,
                                               const unsigned long long* __restrict__ kth,
@@ -2049,26 +1886,17 @@ __device__ __forceinline__ void sil_bwd_block(const RasterWs& ws, const Tile& t,
   float coef_p = 0.f;
   unsigned long long kth_p = KEY_NONE;
   bin_and_walk(ws, t, F, H, L, s_fl, 0.f, [&](int list_n) {
-#ifdef ACFM_DIAG_BWD_NO_WALK
-    if (list_n >= 0) return;
-#endif
-    walk_wave<false, ACFM_BWD_SHARE != 0>(L, t, H, list_n, blur, nullptr,
-#if ACFM_BWD_SHARE
-                                          [&](const Cand& cd, bool in_box, int ord, bool helping, float exf, float eyf) {
+    walk_wave<false, true>(L, t, H, list_n, blur, nullptr,
+                           [&](const Cand& cd, bool in_box, int ord, bool helping, float exf, float eyf) {
       const float coef_e = helping ? coef_p : coef;
       const unsigned long long kth_e = helping ? kth_p : kthkey;
       bool member = (coef_e != 0.0f) && in_box;
-#else
-                                          [&](const Cand& cd, bool in_box, int ord) {
-      const float exf = t.xf, eyf = t.yf, coef_e = coef;
-      const unsigned long long kth_e = kthkey;
-      bool member = work && in_box;
-#endif
       if (__ballot(member) == 0ull) return;
-#if ACFM_BWD_EDGE_GLOBAL
+      // the per-edge constants (|e|^2, refined 1/|e|^2) of the face from its record in memory (L2-resident: 128 B x
+      // 1280 faces per mesh) instead of recomputing them per pixel -- measured 180.8 -> 171.4 us per 64-frame launch;
+      // requested before the depth stage so that its ~100 instructions cover the latency
       const FaceRec& grec = ws.rec[(size_t)t.n * F + cd.fid];
       const float4 e0g = grec.e0, e1g = grec.e1;
-#endif
       const float4 A = cd.a, B = cd.b;
       Hit h;
       h.pz = 0.f; h.sd = 0.f; h.d01 = 0.f; h.d02 = 0.f; h.d12 = 0.f;
@@ -2079,18 +1907,11 @@ __device__ __forceinline__ void sil_bwd_block(const RasterWs& ws, const Tile& t,
       member = member && (make_key(h.pz, cd.fid) <= kth_e);
       if (__ballot(member) == 0ull) return;
       float tpar[3] = {0.f, 0.f, 0.f};
-#if ACFM_BWD_EDGE_GLOBAL
-      // ACFM_BWD_EDGE_GLOBAL: the per-edge constants (|e|^2, refined 1/|e|^2) of the face from its record in memory
-      // (L2-resident: 128 B x 1280 faces per mesh) instead of recomputing them per pixel; requested before the depth
-      // stage so that its ~100 instructions cover the latency.  A face with a degenerate edge takes the unfactored path.
-      if (__ballot(e1g.z != 0.0f) != 0ull) {
+      if (__ballot(e1g.z != 0.0f) != 0ull) {   // a face with a degenerate edge takes the unfactored path
         if (member) member = test_face_dist(exf, eyf, A, B, blur, inside, h, tpar);
       } else {
         if (member) member = test_face_dist_e(exf, eyf, A, B, e0g, e1g, blur, inside, h, tpar);
       }
-#else
-      if (member) member = test_face_dist(exf, eyf, A, B, blur, inside, h, tpar);
-#endif
       if (__ballot(member) == 0ull) return;
       float g0x = 0.f, g0y = 0.f, g1x = 0.f, g1y = 0.f, g2x = 0.f, g2y = 0.f;
       if (member) {
@@ -2136,7 +1957,6 @@ __device__ __forceinline__ void sil_bwd_block(const RasterWs& ws, const Tile& t,
         }
       }
     }
-#if ACFM_BWD_SHARE
     , [&](int partner_lane) {
       const int src = partner_lane >= 0 ? partner_lane : t.lane;
       coef_p = __shfl(coef, src, 64);
@@ -2144,12 +1964,8 @@ __device__ __forceinline__ void sil_bwd_block(const RasterWs& ws, const Tile& t,
       const unsigned hi = (unsigned)__shfl((int)(unsigned)(kthkey >> 32), src, 64);
       kth_p = ((unsigned long long)hi << 32) | lo;
     }
-#endif
     );
     wave_lds_sync();
-#ifdef ACFM_DIAG_BWD_NO_FLUSH
-    if (list_n >= 0) return;
-#endif
     for (int c = t.lane; c < list_n; c += RT) {
       AccT* acc = s_acc[c];
       const AccT z = (AccT)0;
@@ -2170,11 +1986,9 @@ __device__ __forceinline__ void sil_bwd_block(const RasterWs& ws, const Tile& t,
 
 // waves per SIMD the backward is compiled for: with the shared walk 5 (no spills; 156.9 us in the benchmark step) beats
 // 6 (80 VGPRs + 28 B of scratch; 160.5 us); without it 6 had measured best
-#ifndef ACFM_BWD_WAVES
-#define ACFM_BWD_WAVES 5
-#endif
+constexpr int BWD_WAVES = 5;
 template <class AccT>
-__global__ __launch_bounds__(RT, ACFM_BWD_WAVES) void k_sil_bwd(RasterWs ws, const void* __restrict__ mask,
+__global__ __launch_bounds__(RT, BWD_WAVES) void k_sil_bwd(RasterWs ws, const void* __restrict__ mask,
                                                  const unsigned long long* __restrict__ kth,
                                                  BwdGrad grad_mask, int N, int V,
                                                  int F, int H, float blur, float sigma) {
@@ -2450,17 +2264,9 @@ __device__ __forceinline__ void divmod_small(int i, int w, float rw, int& q, int
   if (r >= w) { ++q; r -= w; }
 }
 constexpr int TEXG_MAX_R = 8;
-#ifndef ACFM_TEXG_FPW
-#define ACFM_TEXG_FPW 4
-#endif
-constexpr int TEXG_FPW = ACFM_TEXG_FPW;      // faces per wave: their boxes, texel indices and gradients are loaded side by side
-#ifndef ACFM_TEXG_U
-#define ACFM_TEXG_U 2    // (with 8 waves per SIMD below: 39.8 us per launch; U = 4 at 6 waves 41.4; U = 8 at 5 waves -- 92 VGPRs -- 45.2)
-#endif
-#ifndef ACFM_TEXG_WAVES
-#define ACFM_TEXG_WAVES 8
-#endif
-constexpr int TEXG_U = ACFM_TEXG_U;        // big boxes: 64 U pixels per round, all their loads in flight together
+constexpr int TEXG_FPW = 4;      // faces per wave: their boxes, texel indices and gradients are loaded side by side
+constexpr int TEXG_U = 2;        // big boxes: 64 U pixels per round, all their loads in flight together
+constexpr int TEXG_WAVES = 8;    // waves per SIMD (U = 2 at 8 waves: 39.8 us per launch; U = 4 at 6 waves 41.4; U = 8 at 5 waves -- 92 VGPRs -- 45.2)
 // Upstream gradient of the rendered image: given ([N,3,H,H]) or, for the fused texture render + masked MSE, formed
 // on the fly from the rendered image, the reference image and mask and the per-mesh gradient of the loss --
 // k_tex_mse_bwd's expression: w (tex m - img m) m with w = go[n] 2 / (3 HW).
@@ -2498,7 +2304,7 @@ __device__ __forceinline__ TexGradN tex_grad_of(const TexGrad& tg, int n, size_t
   t.w = tg.go[n] * 2.0f / (3.0f * (float)HW);
   return t;
 }
-__global__ __launch_bounds__(256, ACFM_TEXG_WAVES) void k_tex_bwd_faces(RasterWs ws, TexGrad tgrad,
+__global__ __launch_bounds__(256, TEXG_WAVES) void k_tex_bwd_faces(RasterWs ws, TexGrad tgrad,
                                                        const int32_t* __restrict__ tidx, int N, int F, int H,
                                                        int R, int NA, float box_shrink,
                                                        float* __restrict__ grad_atlas) {

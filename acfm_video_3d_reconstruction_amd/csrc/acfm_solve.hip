@@ -25,9 +25,8 @@
 //   substitutions are tile GEMMs, one WG of 16 waves per 32 vertices, no serial chain),
 //   dA = Q^T - (A Q) P^T - (A P) Q^T,   dlbs = softmax backward per handle     (k_solve_bwd_lbs)
 //
-// -DACFM_CHOL_STEPS=1 (make VARIANT=steps EXTRA=-DACFM_CHOL_STEPS=1) builds the round-1 schedule instead
-// -- one launch per tile column (k_chol_first, k_chol_step x nblk, k_apply_R) -- for A/B runs; both give
-// bit-identical results (same operations in the same order).
+// (The round-1 schedule -- one launch per tile column, then k_apply_R for P -- did the same operations in the same
+// order, bit-identical results; DESIGN.md section 4 has its numbers.)
 //
 // Storage: (2 nblk + 1) x nblk tiles, row-major, ld = n_pad = 32 nblk; tile rows [0, nblk) the
 // matrix, tile row nblk the right-hand sides (row h = handle h), tile rows (nblk, 2 nblk] the
@@ -104,16 +103,6 @@ __device__ __forceinline__ double block_reduce(double v, double* scratch /*[256]
   const double r = scratch[0];
   __syncthreads();
   return r;
-}
-
-// C (32x32, quadrant of this wave) += sum_p Aop(r, p) * Bop(p, c);  fa(r, p), fb(p, c) with
-// r, c in [0,16) relative to the wave's quadrant
-template <class FA, class FB>
-__device__ __forceinline__ f64x4 tile_mma(int lane, f64x4 acc, FA&& fa, FB&& fb) {
-  const int x = lane & 15, y = lane >> 4;
-#pragma unroll
-  for (int k0 = 0; k0 < NB; k0 += 4) acc = mfma64(fa(x, k0 + y), fb(k0 + y, x), acc);
-  return acc;
 }
 
 // The workgroup (4 waves) factorises the SPD tile sC[NB][LDT] (lower part read) and inverts the factor.
@@ -216,7 +205,7 @@ __device__ __forceinline__ void potrf32_wg(const double* sC, double* sU, int* sC
 }
 
 // ---- A = softmax(lbs[:, h]) over the vertices, fp64; grid = 32 (rows >= Kh are zero) ----------
-// grid = 32, or 32 + solve_prepare_blocks: the workgroups beyond the 32 handles fill the sentinels of the tile launch
+// grid = 32 + solve_prepare_blocks: the workgroups beyond the 32 handles fill the sentinels of the tile launch
 // (neither half depends on the other, both precede the rows of W: one launch instead of two)
 __device__ __forceinline__ void solve_prepare_block(const SolveWs& s, int b_in);
 __global__ __launch_bounds__(256) void k_solve_softmax(const float* __restrict__ lbs, SolveWs s, int Kh) {
@@ -229,10 +218,6 @@ __global__ __launch_bounds__(256) void k_solve_softmax(const float* __restrict__
   double* rowW = s.W + (size_t)(s.n_pad + h) * s.ld;
   double* rowA = s.A64 + (size_t)h * s.n_pad;
   if (h == 0 && t == 0) { s.info[0] = 0; s.info[1] = 0; }  // status, tile ticket of k_chol_tiles
-#if ACFM_CHOL_STEPS
-  // identity under the right-hand sides (the region was zeroed by the host): R = L^-T rides along
-  for (int v = h * 256 + t; v < s.n_pad; v += KHP * 256) s.W[(size_t)(s.n_pad + NB + v) * s.ld + v] = 1.0;
-#endif
   if (h >= Kh) {
     for (int v = t; v < s.n_pad; v += 256) rowW[v] = rowA[v] = 0.0;
     return;
@@ -347,100 +332,6 @@ __global__ __launch_bounds__(256) void k_solve_gram_rows(const float* __restrict
 #pragma unroll
     for (int q = 0; q < GRAM_CPT; ++q)
       if (col[q] < s.n_pad) wrow[col[q]] = acc[q];
-  }
-}
-
-// ---- factorise tile (0,0); one WG ----------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_chol_first(SolveWs s) {
-  __shared__ __attribute__((aligned(16))) double sBuf[2 * NB * LDT];
-  __shared__ int sCount;
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int idx = t + 256 * e, rr = idx >> 5, cc = idx & 31;
-    sBuf[rr * LDT + cc] = s.W[(size_t)rr * s.ld + cc];
-  }
-  __syncthreads();
-  potrf32_wg(sBuf, sBuf, &sCount, t, 0, s.info);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int idx = t + 256 * e, rr = idx >> 5, cc = idx & 31;
-    s.Lf[(size_t)rr * s.ld + cc] = potrf_L(sBuf, rr, cc);
-    s.Linv[rr * NB + cc] = sBuf[rr * 64 + 32 + cc];
-  }
-}
-
-// ---- one tile column of the factorisation; grid (m+1, nblk+1), m = nblk-1-k --------------------
-// blockIdx.y -> tile row i: y < m the matrix rows k+1+y, y == m the right-hand sides (i = nblk),
-// y > m the identity rows 0..k (i = nblk+1+(y-m-1); rows below k are still zero in column k).
-// blockIdx.x < m -> update of tile (i, j = k+1+x), blockIdx.x == m -> store L_ik.
-__global__ __launch_bounds__(256) void k_chol_step(SolveWs s, int k) {
-  const int m = s.nblk - 1 - k;
-  const int y = blockIdx.y;
-  const int i = y < m ? k + 1 + y : s.nblk + (y - m);
-  const bool panel = (int)blockIdx.x == m;
-  const int j = panel ? i : k + 1 + (int)blockIdx.x;
-  if (!panel && j > i) return;
-  __shared__ __attribute__((aligned(16))) double sInv[NB][LDT], sWW[2][NB][LDT], sLi[NB][LDT], sLj[NB][LDT];
-  __shared__ int sCount;
-  double(*sWi)[LDT] = sWW[0];
-  double(*sWj)[LDT] = sWW[1];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int qi = w >> 1, qj = w & 1;
-  const double* inv = s.Linv + (size_t)k * NB * NB;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int idx = t + 256 * e, rr = idx >> 5, cc = idx & 31;
-    sInv[rr][cc] = inv[rr * NB + cc];
-    sWi[rr][cc] = s.W[(size_t)(NB * i + rr) * s.ld + NB * k + cc];
-    if (!panel && j != i) sWj[rr][cc] = s.W[(size_t)(NB * j + rr) * s.ld + NB * k + cc];
-  }
-  __syncthreads();
-  const f64x4 zero = {0.0, 0.0, 0.0, 0.0};
-  const int col = 16 * qj + (lane & 15);
-  // L_ik = W_ik L_kk^-T
-  f64x4 li = tile_mma(lane, zero, [&](int r, int p) { return sWi[16 * qi + r][p]; },
-                      [&](int p, int c) { return sInv[16 * qj + c][p]; });
-  if (panel) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      s.Lf[(size_t)(NB * i + 16 * qi + acc_row(lane, e)) * s.ld + NB * k + col] = li[e];
-    return;
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) sLi[16 * qi + acc_row(lane, e)][col] = li[e];
-  if (j != i) {
-    f64x4 lj = tile_mma(lane, zero, [&](int r, int p) { return sWj[16 * qi + r][p]; },
-                        [&](int p, int c) { return sInv[16 * qj + c][p]; });
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sLj[16 * qi + acc_row(lane, e)][col] = lj[e];
-  }
-  __syncthreads();
-  double(*sR)[LDT] = (j != i) ? sLj : sLi;
-  f64x4 acc;
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    acc[e] = s.W[(size_t)(NB * i + 16 * qi + acc_row(lane, e)) * s.ld + NB * j + col];
-  acc = tile_mma(lane, acc, [&](int r, int p) { return -sLi[16 * qi + r][p]; },
-                 [&](int p, int c) { return sR[16 * qj + c][p]; });
-  const bool next_diag = (i == k + 1) && (j == k + 1);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int row = 16 * qi + acc_row(lane, e);
-    s.W[(size_t)(NB * i + row) * s.ld + NB * j + col] = acc[e];
-    if (next_diag) sWi[row][col] = acc[e];
-  }
-  if (next_diag) {
-    __syncthreads();
-    double* sU = &sWW[0][0][0];
-    potrf32_wg(sU, sU, &sCount, t, NB * i, s.info);
-    double* invn = s.Linv + (size_t)i * NB * NB;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int idx = t + 256 * e, rr = idx >> 5, cc = idx & 31;
-      s.Lf[(size_t)(NB * i + rr) * s.ld + NB * i + cc] = potrf_L(sU, rr, cc);
-      invn[rr * NB + cc] = sU[rr * 64 + 32 + cc];
-    }
   }
 }
 
@@ -708,8 +599,7 @@ __global__ __launch_bounds__(256) void k_chol_tiles(SolveWs s, int Kh, float* __
 
 // ---- out = R rhs (TRANS: R^T rhs), R = L^-T upper block-triangular; grid = nblk ------------------
 // WG c produces the 32 vertices of tile row c for all handles.  Right-hand sides and results are
-// [n_pad][32] (vertex-major); RHS 0: rhs^T = Y^T in the factor's right-hand-side tile row,
-// 1: an [n_pad][32] fp64 buffer, 2: an fp32 [V][Kh] tensor (the incoming gradient).
+// [n_pad][32] (vertex-major); RHS 1: an [n_pad][32] fp64 buffer, 2: an fp32 [V][Kh] tensor (the incoming gradient).
 constexpr int APPLY_PAR = 8;  // waves sharing the tile sum of one (vertex tile, handle half)
 template <bool TRANS, int RHS>
 __global__ __launch_bounds__(64 * 2 * APPLY_PAR) void k_apply_R(SolveWs s, const double* __restrict__ rhs64,
@@ -736,8 +626,7 @@ __global__ __launch_bounds__(64 * 2 * APPLY_PAR) void k_apply_R(SolveWs s, const
       for (int qi = 0; qi < 2; ++qi) {
         if (qi >= nqi) continue;
         const int h = 16 * qi + x, v = NB * p + q;
-        if (RHS == 0) a[qi][ks] = s.Lf[(size_t)(s.n_pad + h) * ld + v];
-        else if (RHS == 1) a[qi][ks] = rhs64[(size_t)v * KHP + h];
+        if (RHS == 1) a[qi][ks] = rhs64[(size_t)v * KHP + h];
         else a[qi][ks] = (v < n && h < Kh) ? (double)rhs32[(size_t)v * Kh + h] : 0.0;
       }
     }
@@ -825,16 +714,10 @@ __global__ __launch_bounds__(BWD_T) void k_solve_bwd_lbs(SolveWs s, int Kh, floa
 
 using namespace acfm;
 
-#ifndef ACFM_CHOL_STEPS
-#define ACFM_CHOL_STEPS 0  // 1: the factorisation as one launch per tile column (the round-1 path, kept for A/B runs)
-#endif
-
 // One workgroup per CU: a second one on the CU of a diagonal job, even one that only waits, slows that job's
 // serial chain (measured on the 642-vertex solve: 186 us with two per CU, 175 with one; 176 / 200 / 296 us with
 // 192 / 128 / 64 workgroups in all).
-#ifndef CHOL_PER_CU
-#define CHOL_PER_CU 1
-#endif
+constexpr int CHOL_PER_CU = 1;
 // workgroups of k_chol_tiles the device holds at once; only a grid size (the ticket makes any number correct)
 static int chol_resident_workgroups() {
   static std::atomic<int> cached[64];
@@ -864,28 +747,12 @@ int acfm_deform_solve(const float* L, const float* lbs, int V, int Kh, float* P,
   if (ws_bytes < s.bytes) return ACFM_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(ACFM_PROF_SOLVE, st);
-#if ACFM_CHOL_STEPS
-  if (zero_async(s.W + (size_t)(s.n_pad + NB) * s.ld, sizeof(double) * (size_t)s.n_pad * s.ld, st) != ACFM_OK)
-    return ACFM_E_LAUNCH;
-  hipLaunchKernelGGL(k_solve_softmax, dim3(KHP), dim3(256), 0, st, lbs, s, Kh);
-#else
   hipLaunchKernelGGL(k_solve_softmax, dim3(KHP + (2 * s.nblk + 2) * s.nblk), dim3(256), 0, st, lbs, s, Kh);
-#endif
   hipLaunchKernelGGL(k_solve_gram_rows, dim3(s.n_pad), dim3(256), 0, st, L, s, Kh);
-#if ACFM_CHOL_STEPS
-  hipLaunchKernelGGL(k_chol_first, dim3(1), dim3(256), 0, st, s);
-  for (int k = 0; k < s.nblk; ++k) {
-    const int m = s.nblk - 1 - k;
-    hipLaunchKernelGGL(k_chol_step, dim3(m + 1, s.nblk + 1), dim3(256), 0, st, s, k);
-  }
-  hipLaunchKernelGGL((k_apply_R<false, 0>), dim3(s.nblk), dim3(64 * 2 * APPLY_PAR), 0, st, s, (const double*)nullptr,
-                     (const float*)nullptr, Kh, s.X, P);
-#else
   {  // factorisation, R = L^-T, Y^T and P = R Y in one launch
     const int jobs = s.nblk * (s.nblk + 3), cap = chol_resident_workgroups();
     hipLaunchKernelGGL(k_chol_tiles, dim3(jobs < cap ? jobs : cap), dim3(256), 0, st, s, Kh, P);
   }
-#endif
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
 }

@@ -1,6 +1,9 @@
 #!/bin/bash
-# A/B of kernel variants on one box: tools/ab.sh "<kbench args>" variant1 variant2 ...   ("-" = the shipping library)
-# (variants are built with `make -C acfm_video_3d_reconstruction_amd/csrc VARIANT=name EXTRA="-D..."`); two interleaved rounds
+# A/B of library builds on one box: tools/ab.sh "<kbench args>" name1 name2 ...   ("-" = the shipping library);
+# two interleaved rounds.  `name` is the VARIANT of `make -C acfm_video_3d_reconstruction_amd/csrc VARIANT=name [EXTRA="-D..."]`
+# (-> libacfm_hip_name.so beside the shipping library: build one before an edit and one after it).  The named -D switches
+# of the earlier rounds were removed with the code they selected (verdicts: DESIGN.md section 5, code: tools/variants/).
+# tools/isa_diff.py shows which kernels two builds actually differ in.
 args="$1"; shift
 pat=${AB_PAT:-"k_raster_fwd<K|k_sil_bwd|k_raster_fwd<1|k_tex_bwd|sum of"}
 for rep in 1 2; do
