@@ -95,6 +95,10 @@ SIGNATURES = {
     "acfm_texture_cycle": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "acfm_texture_cycle_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "acfm_mask_losses": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "acfm_loss_partial_floats": (_sz, [_i, _i, _i]),
+    "acfm_mask_losses_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "acfm_tex_mse_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "acfm_bds_loss_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "acfm_mask_losses_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "acfm_tex_mse": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "acfm_tex_mse_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),

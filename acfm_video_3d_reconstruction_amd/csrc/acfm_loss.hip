@@ -8,24 +8,100 @@ namespace acfm {
 
 constexpr int LTPB = 256;
 constexpr int PIX_PER_BLOCK = 2048;  // 8 px per thread: 2 x float4
+// The two forward reductions take 8192 pixels per workgroup where that still leaves two workgroups for each of the
+// chip's 256 CUs (N * ceil(HW / 8192) >= 512), else 2048.  The workgroups of a mesh meet in one ticket word: at 256^2
+// the narrow form sends 32 of them there at about the same time, which cost k_mask_losses 9 us; with 8 the
+// one-launch form is faster than fill + atomics (profiles/r04_loss_in_graph.txt).  Below the threshold the wide
+// form would leave CUs without a workgroup, which costs more bandwidth than the tickets do.
+constexpr int PIX_PER_BLOCK_WIDE = 8192;
+static inline int fwd_pix_per_block(int N, int HW) {
+  constexpr size_t CUS = 256;
+  return (size_t)N * ((HW + PIX_PER_BLOCK_WIDE - 1) / PIX_PER_BLOCK_WIDE) >= 2 * CUS ? PIX_PER_BLOCK_WIDE : PIX_PER_BLOCK;
+}
 
-// out[n] += (sum|m-gt|/HW, sum m*gt, sum(m+gt-m*gt), sum edt*m/HW); one pass over the mask.
+// ---- per-mesh sums in one launch: no zero fill of the output, no float atomics (the *_ws entry points) -------------
+// Every workgroup of mesh `row` hands its C partial sums over in `partials`, draws a ticket, and the workgroup that
+// draws the mesh's last ticket adds the partials in workgroup order 0, 1, 2, ... and stores the result: the same
+// inputs give the same bits, and the output needs no prior contents.  The ticket is a WRAPPING increment
+// (limit nblk - 1): the word is 0 again when the launch ends, so the caller zeroes it once, at allocation.
+//
+// The hand-over does not use a device-scope fence.  Such a fence in front of the ticket is a write-back of the
+// XCD's whole L2 (buffer_wbl2 sc1), once per workgroup: measured at 9x the kernel time (DESIGN.md section 5,
+// tools/variants/loss_ticket_finish.patch).  Instead every word that crosses workgroups is itself a device-scope
+// atomic, performed at the memory side like the float atomicAdd it replaces: the partials go out as RETURNING
+// exchanges, the wave waits for the old values to come back -- the exchanges have been performed by then -- and
+// only then draws its ticket; the last workgroup reads the partials with device-scope atomic loads, after its own
+// ticket came back.  The wait for the exchanges is the use of their old values (the empty asm: s_waitcnt vmcnt(0));
+// the workgroup-scope fences keep the compiler from moving the atomics across it and do no cache maintenance.
+//
+// THIS RESTS ON THE HARDWARE, NOT ON THE MEMORY MODEL: relaxed atomics with workgroup-scope fences give no formal
+// happens-before between workgroups.  What it needs is (1) a returning device-scope read-modify-write comes back only
+// after it was performed where every XCD sees it, and (2) a device-scope atomic load (sc1) does not answer from a stale
+// line of the reader's own L2.  Both hold on gfx942 / gfx950; a compiler that drops the wait, or an architecture
+// with another coherence point, breaks it SILENTLY (a stale partial in a sum).  After a change of either, read the ISA
+// (global_atomic_swap sc0 / s_waitcnt vmcnt(0) / global_atomic_inc sc0 / global_load_dword sc1) and run
+// tests/test_gpu_loss_reductions.py: the graph replayed on changed inputs and the two-stream test read partials
+// that other XCDs wrote in the launch before with different values, so a stale read fails their bit comparison.
+struct RowScratch {
+  unsigned* tickets;   // [N], zero between launches; nullptr = the atomics form behind a zero fill (plain entry points)
+  float* partials;     // [N][nblk][C], any contents
+};
+// Called by one whole wave (lanes 0..63 of it); lane c < C carries the workgroup's partial sum c in `mine`.
+template <int C>
+__device__ __forceinline__ void row_finish(const RowScratch& sc, int row, int nblk, int blk, float mine,
+                                           float* __restrict__ out_row) {
+  const int lane = threadIdx.x & 63;
+  unsigned* slot = reinterpret_cast<unsigned*>(sc.partials) + ((size_t)row * nblk + blk) * C;
+  unsigned old = 0u;
+  if (lane < C)
+    old = __hip_atomic_exchange(slot + lane, __float_as_uint(mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("" ::"v"(old));   // the old values are back: the exchanges were performed
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  unsigned ticket = 0u;
+  if (lane == 0) ticket = atomicInc(&sc.tickets[row], (unsigned)(nblk - 1));
+  ticket = __shfl(ticket, 0, 64);
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  if (ticket != (unsigned)(nblk - 1)) return;
+  const unsigned* rowp = reinterpret_cast<const unsigned*>(sc.partials) + (size_t)row * nblk * C;
+  float acc[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = 0.f;
+  for (int b0 = 0; b0 < nblk; b0 += 64) {    // lane l holds workgroup b0 + l; added one after the other, in order
+    float x[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+      x[c] = (b0 + lane < nblk) ? __uint_as_float(__hip_atomic_load(rowp + (size_t)(b0 + lane) * C + c, __ATOMIC_RELAXED,
+                                                                    __HIP_MEMORY_SCOPE_AGENT))
+                                : 0.f;
+    const int cnt = min(64, nblk - b0);
+    for (int l = 0; l < cnt; ++l) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) acc[c] += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[c]), l));
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < C; ++c)
+    if (lane == c) out_row[c] = acc[c];
+}
+
+// out[n] = (sum|m-gt|/HW, sum m*gt, sum(m+gt-m*gt), sum edt*m/HW); one pass over the mask.
 // (prediction n is compared with reference n % RB: the G camera hypotheses of a frame share the
 // frame's ground truth, so the trainer's gt.repeat(G, ...) copies are never made)
+template <int PIX_FWD>
 __global__ __launch_bounds__(LTPB) void k_mask_losses(const float* __restrict__ mask,
                                                       const float* __restrict__ gt,
                                                       const float* __restrict__ edt, int HW, int RB,
-                                                      float* __restrict__ out) {
+                                                      float* __restrict__ out, RowScratch sc) {
   __shared__ float s_red[4][4];
   const int n = blockIdx.y, tid = threadIdx.x;
   const size_t base = (size_t)n * HW, rbase = (size_t)(n % RB) * HW;
-  const int start = blockIdx.x * PIX_PER_BLOCK;
-  const int end = min(start + PIX_PER_BLOCK, HW);
+  const int start = blockIdx.x * PIX_FWD;
+  const int end = min(start + PIX_FWD, HW);
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   const bool vec = ((HW & 3) == 0);
   if (vec) {
     // the block's two 16-byte pieces per thread and array are loaded before any of them is used
-    constexpr int U = PIX_PER_BLOCK / (LTPB * 4);
+    constexpr int U = PIX_FWD / (LTPB * 4);
     float4 m[U], g[U], e[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -53,11 +129,14 @@ __global__ __launch_bounds__(LTPB) void k_mask_losses(const float* __restrict__ 
   const int w = tid >> 6;
   if ((tid & 63) == 0) { s_red[w][0] = a0; s_red[w][1] = a1; s_red[w][2] = a2; s_red[w][3] = a3; }
   __syncthreads();
+  if (tid >= 64) return;
+  float v = 0.f;
   if (tid < 4) {
-    float v = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
+    v = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
     if (tid == 0 || tid == 3) v = v / (float)HW;
-    atomicAdd(&out[4 * (size_t)n + tid], v);
   }
+  if (sc.tickets) row_finish<4>(sc, n, (int)gridDim.x, (int)blockIdx.x, v, out + 4 * (size_t)n);
+  else if (tid < 4) atomicAdd(&out[4 * (size_t)n + tid], v);
 }
 
 // grad_mask = go0*sign(m-gt)/HW + go1*gt + go2*(1-gt) + go3*edt/HW
@@ -95,16 +174,17 @@ __global__ __launch_bounds__(LTPB) void k_mask_losses_bwd(const float* __restric
 }
 
 // masked texture MSE (multiframe/main.py:655-662): per mesh mean over (3,H,W) of
-// (tex*m - img*m)^2; out[n] accumulated with one atomic per block.
+// (tex*m - img*m)^2; the workgroups' sums are added by row_finish (or, without scratch, one atomic per workgroup).
+template <int PIX_FWD>
 __global__ __launch_bounds__(LTPB) void k_tex_mse(const float* __restrict__ tex,
                                                   const float* __restrict__ img,
                                                   const float* __restrict__ m, int HW, int RB,
-                                                  float* __restrict__ out) {
+                                                  float* __restrict__ out, RowScratch sc) {
   __shared__ float s_red[4];
   const int n = blockIdx.y, tid = threadIdx.x;
   const size_t b3 = (size_t)n * 3 * HW, r3 = (size_t)(n % RB) * 3 * HW, b1 = (size_t)(n % RB) * HW;
-  const int start = blockIdx.x * PIX_PER_BLOCK;
-  const int end = min(start + PIX_PER_BLOCK, HW);
+  const int start = blockIdx.x * PIX_FWD;
+  const int end = min(start + PIX_FWD, HW);
   float acc = 0.f;
   if ((HW & 3) == 0) {   // 16-byte loads
     for (int i = start + tid * 4; i < end; i += LTPB * 4) {
@@ -130,7 +210,10 @@ __global__ __launch_bounds__(LTPB) void k_tex_mse(const float* __restrict__ tex,
   acc = wave_sum(acc);
   if ((tid & 63) == 0) s_red[tid >> 6] = acc;
   __syncthreads();
-  if (tid == 0) atomicAdd(&out[n], (s_red[0] + s_red[1] + s_red[2] + s_red[3]) / (3.0f * (float)HW));
+  if (tid >= 64) return;
+  const float v = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) / (3.0f * (float)HW);
+  if (sc.tickets) row_finish<1>(sc, n, (int)gridDim.x, (int)blockIdx.x, v, out + n);
+  else if (tid == 0) atomicAdd(&out[n], v);
 }
 
 __global__ __launch_bounds__(LTPB) void k_tex_mse_bwd(const float* __restrict__ tex,
@@ -186,71 +269,64 @@ __global__ void k_visible(const int64_t* __restrict__ p2f, const int64_t* __rest
 }
 
 // One workgroup = 64 boundary points x all vertices: its four waves search a quarter of the vertices
-// each (the search is a chain of V dependent compare-selects per point: one wave per SIMD left the
+// each (the search is a chain of dependent compare-selects per point: one wave per SIMD left the
 // chip idle for 20 us) and wave 0 merges the four partial minima in vertex order, so the first
 // nearest vertex wins exactly as in a single ascending scan.
+// Only VISIBLE vertices are searched (half of a closed mesh is never seen): every wave stages its own quarter
+// straight from memory into LDS, 64 vertices a round, keeping the visible ones packed in ascending order
+// (ballot + prefix count) next to the index each came from.  A wave reads no other wave's quarter, so no
+// workgroup barrier stands between the staging and the search.
 __global__ __launch_bounds__(LTPB) void k_bds_loss(const float* __restrict__ verts_xy,
                                                    const float* __restrict__ bds,
                                                    const uint8_t* __restrict__ vis, int V, int P, int RB,
-                                                   float* __restrict__ loss, int32_t* __restrict__ argmin) {
-  extern __shared__ float s_xy[];  // [V][2], x = +inf for invisible verts
+                                                   float* __restrict__ loss, int32_t* __restrict__ argmin,
+                                                   RowScratch sc) {
+  extern __shared__ float s_xy[];  // [V][2]: per quarter, its visible vertices packed to the front; then int s_idx[V]
   __shared__ float s_best[4][64];
   __shared__ int s_bi[4][64];
   const int n = blockIdx.y, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  // (unconditional loads, four vertices per thread in flight: with the loads behind the visibility
-  // test this fill was a chain of ~9 memory latencies and the whole kernel took 21 us)
-  for (int v0 = tid; v0 < V; v0 += 4 * LTPB) {
-    uint8_t vz[4];
-    float2 xy[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int v = min(v0 + u * LTPB, V - 1);
-      vz[u] = vis[(size_t)n * V + v];
-      xy[u] = *reinterpret_cast<const float2*>(verts_xy + ((size_t)n * V + v) * 2);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int v = v0 + u * LTPB;
-      if (v < V) {
-        s_xy[2 * v] = vz[u] ? xy[u].x : __builtin_inff();
-        s_xy[2 * v + 1] = vz[u] ? xy[u].y : 0.f;
-      }
-    }
-  }
-  __syncthreads();
+  // the lane's boundary point first: its load is in flight while the vertices are staged
   const int p = blockIdx.x * 64 + lane;
   float bx = 0.f, by = 0.f, bm = 0.f;
   if (p < P) {
     const float* b = bds + ((size_t)(n % RB) * P + p) * 3;
     bx = b[0]; by = b[1]; bm = b[2];
   }
-  float best = 1000.0f;  // loss_utils.py:228: invisible vertices sit at distance 1000
-  int bi = -1;
   const int chunk = (V + 3) / 4, v0 = wv * chunk, v1 = min(V, v0 + chunk);
-  // The wave's quarter of the vertices is packed IN PLACE to its visible ones (half of a closed mesh is never seen):
-  // 64 vertices a round, every lane reads its vertex before any lane writes, a kept vertex moves to a position at or
-  // before its own, order kept -- so the first nearest vertex still wins; s_idx remembers where it came from.
   int* s_idx = reinterpret_cast<int*>(s_xy + 2 * (size_t)V);
   int nvis = 0;
   {
     const unsigned long long lt = (1ull << lane) - 1ull;
-    for (int base = v0; base < v1; base += 64) {
-      const int v = base + lane;
-      float2 q = make_float2(__builtin_inff(), 0.f);
-      if (v < v1) q = *reinterpret_cast<const float2*>(s_xy + 2 * v);
-      const bool keep = (v < v1) && !(q.x == __builtin_inff());
-      const unsigned long long m = __ballot(keep);
-      if (keep) {
-        const int pos = v0 + nvis + __popcll(m & lt);
-        *reinterpret_cast<float2*>(s_xy + 2 * pos) = q;
-        s_idx[pos] = v;
+    // (unconditional loads, four rounds in flight: with the loads behind the visibility test the staging was a
+    // chain of memory latencies)
+    for (int base = v0; base < v1; base += 4 * 64) {
+      uint8_t vz[4];
+      float2 xy[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int v = min(base + u * 64 + lane, v1 - 1);
+        vz[u] = vis[(size_t)n * V + v];
+        xy[u] = *reinterpret_cast<const float2*>(verts_xy + ((size_t)n * V + v) * 2);
       }
-      nvis += __popcll(m);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int v = base + u * 64 + lane;
+        const bool keep = (v < v1) && vz[u] != 0;
+        const unsigned long long m = __ballot(keep);
+        if (keep) {
+          const int pos = v0 + nvis + __popcll(m & lt);
+          *reinterpret_cast<float2*>(s_xy + 2 * pos) = xy[u];
+          s_idx[pos] = v;
+        }
+        nvis += __popcll(m);
+      }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
+  float best = 1000.0f;  // loss_utils.py:228: invisible vertices sit at distance 1000
+  int bi = -1;
 #pragma unroll 8
   for (int v = v0; v < v0 + nvis; ++v) {
     const float2 q = *reinterpret_cast<const float2*>(s_xy + 2 * v);
@@ -273,7 +349,8 @@ __global__ __launch_bounds__(LTPB) void k_bds_loss(const float* __restrict__ ver
     argmin[(size_t)n * P + p] = bi;
   }
   contrib = wave_sum(contrib);
-  if (lane == 0) atomicAdd(&loss[n], contrib);
+  if (sc.tickets) row_finish<1>(sc, n, (int)gridDim.x, (int)blockIdx.x, contrib, loss + n);
+  else if (lane == 0) atomicAdd(&loss[n], contrib);
 }
 
 // One workgroup per mesh: the points' contributions are summed per vertex in LDS (P <= ~1000 points
@@ -578,22 +655,55 @@ __global__ __launch_bounds__(256) void k_tex_cycle_bwd(const float* __restrict__
   grad[src] = g * go[0] * scale;
 }
 
+// Scratch of the *_ws entry points: `tickets`, one word per mesh, zero between launches; `partials`, [N][nblk][C]
+// floats of any contents (sized for the most workgroups a launch of that shape can have).
+static inline int loss_blocks(int which, int n) {
+  return which == ACFM_LOSS_BDS ? (n + 63) / 64 : (n + PIX_PER_BLOCK - 1) / PIX_PER_BLOCK;
+}
+static inline size_t loss_partial_floats(int which, int N, int n) {
+  return (which == ACFM_LOSS_MASK ? 4 : 1) * (size_t)N * loss_blocks(which, n);
+}
+// -> ACFM_OK; both pointers null select the atomics form behind a zero fill (sc.tickets == nullptr)
+static inline int row_scratch(int which, int N, int n, uint32_t* tickets, float* partials, size_t partial_floats,
+                              RowScratch& sc) {
+  sc.tickets = nullptr; sc.partials = nullptr;
+  if (!tickets && !partials) return ACFM_OK;
+  if (!tickets || !partials) return ACFM_E_BADARG;
+  if (partial_floats < loss_partial_floats(which, N, n)) return ACFM_E_WORKSPACE;
+  sc.tickets = tickets; sc.partials = partials;
+  return ACFM_OK;
+}
+
 }  // namespace acfm
 
 using namespace acfm;
 
 extern "C" {
 
-int acfm_mask_losses(const float* mask, const float* gt, const float* edt, int N, int HW, int ref_batch,
-                     float* out, void* stream) {
+size_t acfm_loss_partial_floats(int which, int N, int n) {
+  if (which < ACFM_LOSS_MASK || which > ACFM_LOSS_BDS || N <= 0 || n <= 0) return 0;
+  return loss_partial_floats(which, N, n);
+}
+
+int acfm_mask_losses_ws(const float* mask, const float* gt, const float* edt, int N, int HW, int ref_batch,
+                        float* out, uint32_t* tickets, float* partials, size_t partial_floats, void* stream) {
   if (!mask || !out || N <= 0 || N > 65535 || HW <= 0 || ref_batch <= 0 || N % ref_batch != 0) return ACFM_E_BADARG;
+  RowScratch sc;
+  if (const int rc = row_scratch(ACFM_LOSS_MASK, N, HW, tickets, partials, partial_floats, sc)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (zero_async(out, sizeof(float) * 4 * (size_t)N, st) != ACFM_OK) return ACFM_E_LAUNCH;
-  const int chunks = (HW + PIX_PER_BLOCK - 1) / PIX_PER_BLOCK;
+  if (!sc.tickets && zero_async(out, sizeof(float) * 4 * (size_t)N, st) != ACFM_OK) return ACFM_E_LAUNCH;
+  const int ppb = fwd_pix_per_block(N, HW), chunks = (HW + ppb - 1) / ppb;
   ProfScope ps(ACFM_PROF_MASK_LOSS, st);
-  hipLaunchKernelGGL(k_mask_losses, dim3(chunks, N), dim3(LTPB), 0, st, mask, gt, edt, HW, ref_batch, out);
+  if (ppb == PIX_PER_BLOCK_WIDE)
+    hipLaunchKernelGGL(k_mask_losses<PIX_PER_BLOCK_WIDE>, dim3(chunks, N), dim3(LTPB), 0, st, mask, gt, edt, HW, ref_batch, out, sc);
+  else
+    hipLaunchKernelGGL(k_mask_losses<PIX_PER_BLOCK>, dim3(chunks, N), dim3(LTPB), 0, st, mask, gt, edt, HW, ref_batch, out, sc);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
+}
+int acfm_mask_losses(const float* mask, const float* gt, const float* edt, int N, int HW, int ref_batch,
+                     float* out, void* stream) {
+  return acfm_mask_losses_ws(mask, gt, edt, N, HW, ref_batch, out, nullptr, nullptr, 0, stream);
 }
 
 int acfm_mask_losses_backward(const float* mask, const float* gt, const float* edt,
@@ -609,17 +719,26 @@ int acfm_mask_losses_backward(const float* mask, const float* gt, const float* e
   return ACFM_OK;
 }
 
-int acfm_tex_mse(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,
-                 float* out, void* stream) {
+int acfm_tex_mse_ws(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,
+                    float* out, uint32_t* tickets, float* partials, size_t partial_floats, void* stream) {
   if (!tex || !img || !mask || !out || N <= 0 || N > 65535 || HW <= 0 || ref_batch <= 0 || N % ref_batch != 0)
     return ACFM_E_BADARG;
+  RowScratch sc;
+  if (const int rc = row_scratch(ACFM_LOSS_TEX_MSE, N, HW, tickets, partials, partial_floats, sc)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (zero_async(out, sizeof(float) * (size_t)N, st) != ACFM_OK) return ACFM_E_LAUNCH;
+  if (!sc.tickets && zero_async(out, sizeof(float) * (size_t)N, st) != ACFM_OK) return ACFM_E_LAUNCH;
+  const int ppb = fwd_pix_per_block(N, HW), chunks = (HW + ppb - 1) / ppb;
   ProfScope ps(ACFM_PROF_TEX_MSE, st);
-  hipLaunchKernelGGL(k_tex_mse, dim3((HW + PIX_PER_BLOCK - 1) / PIX_PER_BLOCK, N), dim3(LTPB), 0, st, tex,
-                     img, mask, HW, ref_batch, out);
+  if (ppb == PIX_PER_BLOCK_WIDE)
+    hipLaunchKernelGGL(k_tex_mse<PIX_PER_BLOCK_WIDE>, dim3(chunks, N), dim3(LTPB), 0, st, tex, img, mask, HW, ref_batch, out, sc);
+  else
+    hipLaunchKernelGGL(k_tex_mse<PIX_PER_BLOCK>, dim3(chunks, N), dim3(LTPB), 0, st, tex, img, mask, HW, ref_batch, out, sc);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
+}
+int acfm_tex_mse(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,
+                 float* out, void* stream) {
+  return acfm_tex_mse_ws(tex, img, mask, N, HW, ref_batch, out, nullptr, nullptr, 0, stream);
 }
 
 int acfm_tex_mse_backward(const float* tex, const float* img, const float* mask, const float* grad_out,
@@ -768,20 +887,27 @@ int acfm_visible_vertices(const int64_t* pix_to_face, const int64_t* faces, int 
   return ACFM_OK;
 }
 
-int acfm_bds_loss(const float* verts_xy, const float* bds, const uint8_t* vis, int N, int V, int P,
-                  int ref_batch, float* loss, int32_t* argmin, void* stream) {
+int acfm_bds_loss_ws(const float* verts_xy, const float* bds, const uint8_t* vis, int N, int V, int P,
+                     int ref_batch, float* loss, int32_t* argmin, uint32_t* tickets, float* partials,
+                     size_t partial_floats, void* stream) {
   if (!verts_xy || !bds || !vis || !loss || !argmin || N <= 0 || N > 65535 || V <= 0 || P <= 0 || ref_batch <= 0 ||
       N % ref_batch != 0)
     return ACFM_E_BADARG;
   const size_t lds = sizeof(float) * 3 * (size_t)V;   // (x, y) per vertex + the index a packed vertex came from
   if (lds > 150 * 1024) return ACFM_E_BADARG;
+  RowScratch sc;
+  if (const int rc = row_scratch(ACFM_LOSS_BDS, N, P, tickets, partials, partial_floats, sc)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (zero_async(loss, sizeof(float) * (size_t)N, st) != ACFM_OK) return ACFM_E_LAUNCH;
+  if (!sc.tickets && zero_async(loss, sizeof(float) * (size_t)N, st) != ACFM_OK) return ACFM_E_LAUNCH;
   ProfScope ps(ACFM_PROF_BDS, st);
   hipLaunchKernelGGL(k_bds_loss, dim3((P + 63) / 64, N), dim3(LTPB), lds, st, verts_xy, bds, vis,
-                     V, P, ref_batch, loss, argmin);
+                     V, P, ref_batch, loss, argmin, sc);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
+}
+int acfm_bds_loss(const float* verts_xy, const float* bds, const uint8_t* vis, int N, int V, int P,
+                  int ref_batch, float* loss, int32_t* argmin, void* stream) {
+  return acfm_bds_loss_ws(verts_xy, bds, vis, N, V, P, ref_batch, loss, argmin, nullptr, nullptr, 0, stream);
 }
 
 int acfm_bds_loss_backward(const float* verts_xy, const float* bds, const int32_t* argmin,

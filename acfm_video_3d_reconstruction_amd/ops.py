@@ -128,6 +128,70 @@ def _setup_key(v, c, f, H, offset_z):
             _capture_id(v.device), _EPOCH[0])
 
 
+# Scratch of the one-launch loss sums (acfm_mask_losses_ws, acfm_tex_mse_ws, acfm_bds_loss_ws: include/acfm_hip.h):
+# per (device, stream, capture, loss) one ticket word per mesh -- zero before the first launch, left at zero by
+# every launch -- and a buffer for the workgroups' partial sums (any contents).  Keyed like that, two calls that can
+# be in flight at the same time never share them, and a captured graph keeps the addresses it was recorded with.
+#   * The ticket words are slices (N rounded up to 64 words) of zeroed 256 KiB chunks, so handing one out launches
+#     nothing -- inside a capture a fill would be recorded and replayed with every step.  A spent chunk is followed
+#     by a new one; only if that has to happen inside a capture (first use on the device, or chunk spent there) are
+#     the words a zeroed tensor of their own, whose fill the graph then replays: call a loss once eagerly first.
+#   * Reclaiming: an eager entry lives as long as its stream is used (a bigger call replaces it).  A capture's entry
+#     (64 words and a few KiB per loss at 64 meshes) is kept, because the graph may be replayed at any time;
+#     reset_loss_scratch() drops everything once no such graph is left.
+#   * A launch that is killed midway (device fault, abort) leaves its ticket words non-zero, and later sums on them
+#     would be wrong without a sign: after any device error call reset_loss_scratch(); loss_tickets_clean() checks.
+_TICKET_CHUNKS = {}      # device index -> [int32 tensor, words handed out] (the current chunk)
+_LOSS_SCRATCH = {}       # (device index, stream, capture id, which) -> [tickets slice, partials]
+_TICKET_CHUNK_WORDS = 1 << 16
+_LOSS_MASK, _LOSS_TEX_MSE, _LOSS_BDS = 0, 1, 2
+
+
+def _ticket_words(device, n, capturing):
+    chunk = _TICKET_CHUNKS.get(device.index)
+    if (chunk is None or chunk[1] + n > chunk[0].numel()) and not capturing and n <= _TICKET_CHUNK_WORDS:
+        chunk = _TICKET_CHUNKS[device.index] = [torch.zeros(_TICKET_CHUNK_WORDS, dtype=torch.int32, device=device), 0]
+        torch.cuda.current_stream(device).synchronize()   # once per chunk: its slices are used on any stream
+    if chunk is not None and chunk[1] + n <= chunk[0].numel():
+        t = chunk[0][chunk[1]:chunk[1] + n]
+        chunk[1] += n
+        return t
+    return torch.zeros(n, dtype=torch.int32, device=device)
+
+
+def _loss_scratch(device, which, N, n):
+    """-> (tickets, partials, floats in partials) for an acfm_*_ws call of loss `which` on the current stream."""
+    need = int(_lib.lib().acfm_loss_partial_floats(which, N, n))
+    cid = _capture_id(device)
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream, cid, which)
+    with _LOCK:
+        ent = _LOSS_SCRATCH.get(key)
+        if ent is None:
+            ent = _LOSS_SCRATCH[key] = [None, None]
+        if ent[0] is None or ent[0].numel() < N:
+            ent[0] = _ticket_words(device, -(-N // 64) * 64, cid != 0)
+        if ent[1] is None or ent[1].numel() < need:
+            ent[1] = torch.empty(need, dtype=torch.float32, device=device)
+    return ent[0], ent[1], ent[1].numel()
+
+
+def reset_loss_scratch():
+    """Forget the scratch of the one-launch loss sums (fresh, zeroed ticket words on the next call).  For after a
+    device error, and to release what captured graphs held once none of them will be replayed again."""
+    with _LOCK:
+        _LOSS_SCRATCH.clear()
+        _TICKET_CHUNKS.clear()
+
+
+def loss_tickets_clean():
+    """Debug check (synchronises): True if every ticket word handed out so far reads zero, as it must whenever no
+    loss launch is in flight."""
+    with _LOCK:
+        held = [e[0] for e in _LOSS_SCRATCH.values() if e[0] is not None]
+    torch.cuda.synchronize()
+    return all(int(t.abs().max()) == 0 for t in held)
+
+
 PREFILL_TEX = [True]    # the silhouette render pre-fills the following texture render's empty blocks (see _SilRender.forward)
 
 
@@ -1499,7 +1563,10 @@ class _MaskLosses(torch.autograd.Function):
         if g is not None and e is not None and g.shape[0] != e.shape[0]:
             raise ValueError("mask_losses: gt and edt must have the same batch")
         out = torch.empty((N, 4), dtype=torch.float32, device=m.device)
-        _lib.call("acfm_mask_losses", m.device, _lib.ptr(m), _lib.ptr(g), _lib.ptr(e), N, HW, RB, _lib.ptr(out))
+        with torch.cuda.device(m.device):
+            tk, part, nf = _loss_scratch(m.device, _LOSS_MASK, N, HW)
+        _lib.call("acfm_mask_losses_ws", m.device, _lib.ptr(m), _lib.ptr(g), _lib.ptr(e), N, HW, RB, _lib.ptr(out),
+                  _lib.ptr(tk), _lib.ptr(part), nf)
         ctx.save_for_backward(m, g, e)
         ctx.rb = RB
         return out
@@ -1539,7 +1606,10 @@ class _TexMSE(torch.autograd.Function):
         if t.shape[1:] != i.shape[1:] or t.shape[1] != 3 or t[0, 0].numel() != HW or m.shape[0] != RB:
             raise ValueError("tex [N,3,H,W], img [N or N/G,3,H,W] and mask [same batch as img,H,W]")
         out = torch.empty((N,), dtype=torch.float32, device=t.device)
-        _lib.call("acfm_tex_mse", t.device, _lib.ptr(t), _lib.ptr(i), _lib.ptr(m), N, HW, RB, _lib.ptr(out))
+        with torch.cuda.device(t.device):
+            tk, part, nf = _loss_scratch(t.device, _LOSS_TEX_MSE, N, HW)
+        _lib.call("acfm_tex_mse_ws", t.device, _lib.ptr(t), _lib.ptr(i), _lib.ptr(m), N, HW, RB, _lib.ptr(out),
+                  _lib.ptr(tk), _lib.ptr(part), nf)
         ctx.save_for_backward(t, i, m)
         ctx.rb = RB
         return out
@@ -1717,8 +1787,10 @@ class _BdsLoss(torch.autograd.Function):
         RB = _ref_batch(N, b, "bds_loss")
         loss = torch.empty((N,), dtype=torch.float32, device=v.device)
         arg = torch.empty((N, P), dtype=torch.int32, device=v.device)
-        _lib.call("acfm_bds_loss", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vis.contiguous()), N, V, P, RB,
-                  _lib.ptr(loss), _lib.ptr(arg))
+        with torch.cuda.device(v.device):
+            tk, part, nf = _loss_scratch(v.device, _LOSS_BDS, N, P)
+        _lib.call("acfm_bds_loss_ws", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vis.contiguous()), N, V, P, RB,
+                  _lib.ptr(loss), _lib.ptr(arg), _lib.ptr(tk), _lib.ptr(part), nf)
         ctx.save_for_backward(v, b, arg)
         ctx.rb = RB
         return loss

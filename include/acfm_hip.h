@@ -546,6 +546,22 @@ int acfm_texture_cycle_backward(const float* textures, const float* scratch, con
  * main.py:472-479, 644-662): ref_batch = N / G spares those copies; ref_batch = N is the plain case. */
 int acfm_mask_losses(const float* mask, const float* gt, const float* edt, int N, int HW, int ref_batch,
                      float* out, void* stream);
+/* Scratch-backed forms of the three per-mesh loss sums (acfm_mask_losses_ws, acfm_tex_mse_ws, acfm_bds_loss_ws):
+ * the same inputs and outputs in ONE launch.  The plain entry points zero the output with a launch of their own
+ * and add the workgroups' sums to it with float atomics, in the order they arrive.  Here every workgroup hands
+ * its sums over in `partials`, counts itself in `tickets`, and the workgroup that finishes a mesh last adds the
+ * sums in workgroup order: no fill, and the same inputs give the same bits on every run.
+ *   tickets: N words, ALL ZERO before their first use; every launch leaves them at zero again, so any of the
+ *     three entry points, with any shape of at most that many meshes, can follow on them.  (A launch that is
+ *     killed midway leaves them undefined: zero them again.)
+ *   partials: partial_floats >= acfm_loss_partial_floats(which, N, n) floats, n = HW for the two image losses and
+ *     P for the boundary loss; any contents.  Too small: ACFM_E_WORKSPACE.
+ *   Calls that can be in flight at the same time (different streams) need tickets and partials each.
+ *   tickets == partials == NULL: the plain behaviour; only one of them NULL: ACFM_E_BADARG. */
+enum { ACFM_LOSS_MASK = 0, ACFM_LOSS_TEX_MSE = 1, ACFM_LOSS_BDS = 2 };
+size_t acfm_loss_partial_floats(int which, int N, int n);
+int acfm_mask_losses_ws(const float* mask, const float* gt, const float* edt, int N, int HW, int ref_batch,
+                        float* out, uint32_t* tickets, float* partials, size_t partial_floats, void* stream);
 /* grad_mask [N,HW] = w_l1[n]*sign(m-gt)/HW + w_edt[n]*edt/HW + IoU term
  * (w_inter[n]*gt + w_union[n]*(1-gt)); weights are per-mesh upstream gradients [N,4]. */
 int acfm_mask_losses_backward(const float* mask, const float* gt, const float* edt,
@@ -558,6 +574,9 @@ int acfm_mask_losses_backward(const float* mask, const float* gt, const float* e
  *   tex [N,3,HW], img [ref_batch,3,HW], mask [ref_batch,HW] f32 -> out [N]; backward -> grad_tex [N,3,HW]. */
 int acfm_tex_mse(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,
                  float* out, void* stream);
+int acfm_tex_mse_ws(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,
+                    float* out, uint32_t* tickets, float* partials, size_t partial_floats,
+                    void* stream);                                                  /* see acfm_mask_losses_ws */
 int acfm_tex_mse_backward(const float* tex, const float* img, const float* mask,
                           const float* grad_out, int N, int HW, int ref_batch, float* grad_tex, void* stream);
 
@@ -572,6 +591,9 @@ int acfm_visible_vertices(const int64_t* pix_to_face, const int64_t* faces, int 
  * summed per mesh.  verts_xy [N,V,2], bds [ref_batch,P,3] -> loss [N], argmin [N,P] i32 (saved). */
 int acfm_bds_loss(const float* verts_xy, const float* bds, const uint8_t* vis, int N, int V, int P,
                   int ref_batch, float* loss, int32_t* argmin, void* stream);
+int acfm_bds_loss_ws(const float* verts_xy, const float* bds, const uint8_t* vis, int N, int V, int P,
+                     int ref_batch, float* loss, int32_t* argmin, uint32_t* tickets, float* partials,
+                     size_t partial_floats, void* stream);                          /* see acfm_mask_losses_ws */
 int acfm_bds_loss_backward(const float* verts_xy, const float* bds, const int32_t* argmin,
                            const float* grad_loss, int N, int V, int P, int ref_batch, float* grad_verts_xy,
                            void* stream);
