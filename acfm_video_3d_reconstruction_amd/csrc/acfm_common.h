@@ -23,10 +23,10 @@
 
 namespace acfm {
 
-// stream-ordered zero fill by a kernel (the library issues no hipMemsetAsync: see acfm_raster.hip)
+// stream-ordered zero fill by a kernel (the library issues no hipMemsetAsync: see acfm_runtime.hip)
 int zero_async(void* p, size_t nbytes, hipStream_t st);
 
-// per-kernel hipEvent bracketing (acfm_prof_* in include/acfm_hip.h); state lives in acfm_raster.hip
+// per-kernel hipEvent bracketing (acfm_prof_* in include/acfm_hip.h); state lives in acfm_runtime.hip
 void prof_begin(int id, hipStream_t st);
 void prof_end(hipStream_t st);
 struct ProfScope {

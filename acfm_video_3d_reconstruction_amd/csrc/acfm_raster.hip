@@ -1,18 +1,14 @@
-// Rasterisation kernels for gfx950: face setup, tiled top-K forward (soft silhouette K<=32,
-// hard K=1 with optional atlas shading) and the silhouette backward.
+// The walk kernels of the rasteriser for gfx950: tiled top-K forward (soft silhouette K<=32, hard K=1 with
+// optional atlas shading) and the silhouette backward, with their launchers (acfm_raster.h).  The forward and the
+// backward stay in ONE unit, forward first: compiled apart they come out different.  The other
+// units of the rasteriser: acfm_raster_setup.hip (k_setup, k_order), acfm_raster_api.hip (entry points),
+// acfm_raster_frag.hip, acfm_raster_texgrad.hip, acfm_project.hip.
 //
 // Replaces PyTorch3D 0.3.0's rasterize_meshes coarse/fine/backward CUDA kernels and the
 // blending shaders as used by multiframe/nnutils/nmr.py:143-200, 224-238 (semantics:
 // SURVEY.md App-A; the CPU oracle in oracle/acfm_oracle.c is the bit-level spec).
 //
 // Design:
-//   * k_setup: 4, 8 or 16 workgroups per mesh (face slices) project the V vertices into LDS
-//     (weak-perspective camera, y flip, view transform) and write one 128-byte record per face
-//     (blur-expanded box, vertices, depths, per-edge constants), the face bitmask of every 16x16
-//     coarse tile and a cost count per 8x8 block, counted in LDS and stored as one plane per slice
-//     (no zero fill, no atomics in memory); k_order adds the planes, sorts every XCD group's
-//     (mesh, block) entries heavy-first (counting sort, no atomics) and puts the blocks no face
-//     box comes near at the end.
 //   * k_raster_fwd / k_sil_bwd share one skeleton: a ONE-WAVE workgroup owns an 8x8 pixel
 //     block (four 4x4 blocks, one per 16-lane group).  Faces are binned against the block with
 //     wave ballots into an LDS candidate list (deterministic, face-ordered, no barriers); the
@@ -35,12 +31,8 @@
 //     hard K = 1 render's answer); k_tex_cover shades the texture render of the same geometry from it.
 //   * workgroups are dealt so that all blocks of a mesh run on one XCD (its face records stay
 //     in that XCD's L2).
-//   * k_tex_bwd_faces: the atlas gradient as a per-face gather over the face's box (no global
-//     atomics); k_tex_bwd: the scatter form (one atomic per covered pixel and channel).
-#include "acfm_common.h"
+#include "acfm_raster.h"
 
-#include <atomic>
-#include <mutex>
 #include <type_traits>
 
 namespace acfm {
@@ -60,381 +52,11 @@ __device__ unsigned long long g_diag[16];
 #define DIAG_ADD(i, v) do {} while (0)
 #endif
 
-// A raster launch has entries / div workgroups per XCD group (see Sched; div = Tune::div of the call): the
-// flagged-empty blocks -- 70 % of a 256^2 frame of the bird -- cost no workgroup dispatch of their own.
-constexpr int RBLK = 8;       // pixels per block side: one wave64 per block
-constexpr int RT = 64;        // threads per raster workgroup = RBLK*RBLK
-constexpr int TPB = 256;      // threads per workgroup of the per-mesh kernels (setup, projection)
-constexpr unsigned long long KEY_NONE = ~0ull;
-constexpr int CNT_TILE = 8;   // cost counters per 8x8 pixels (= per raster block)
-constexpr int SETUP_LDS_TILES = 4096;  // counters kept in LDS up to 512x512 images (64^2 blocks)
-constexpr int ENTRY_EMPTY = 1 << 30;   // order entry flag: no face box comes near this block
-constexpr int ENTRY_SPLIT = 1 << 29;   // order entry flag: a heavy block, rendered by four workgroups (one per 4x4 pixels)
-constexpr int ENTRY_FLAGS = ENTRY_EMPTY | ENTRY_SPLIT;
-constexpr int SPLIT_MAX_CLASS = 4;     // ... if their cost class is at most this (>= 80 face boxes)
-constexpr int SETUP_LDS_MASK_BYTES = 64 * 1024;  // coarse masks built in LDS up to this size
-typedef unsigned short fl_t;  // face ids of one mesh (F <= ACFM_MAX_FACES = 65535)
-constexpr int FLCAP = 512;    // LDS face-id list of one wave (faces of its coarse tile, 4096 faces at a time)
-
-// ------------------------------------------------------------------------------- setup
-// mode 0: verts are world coordinates -> project with cams, flip y   (nmr.py:145-149)
-// mode 1: verts are already projected, no y flip                     (nmr.py:224-238)
-// mode 2: verts are already NDC x, NDC y, view z: taken as they are (acfm_rasterize_fragments)
-// Grid (N, ws.slices): every workgroup projects the mesh's V vertices into LDS (cheap, and it
-// keeps the slices independent) and handles one slice of the faces; slice boundaries are multiples
-// of 64 faces, so each slice owns whole words of the coarse masks and builds them in LDS without
-// talking to the others.  Tile counters are kept in LDS and leave as one plane per slice with plain
-// stores (k_order adds the planes: no zero fill, no global atomics); only images beyond 512^2 fall
-// back to global atomics on a zeroed ws.tile_cnt.  The mesh box is left as one box per slice (the
-// raster kernels take the union of four; k_order joins 8 or 16 into the first slot).
-__host__ __device__ __forceinline__ int setup_slice_faces(int F, int slices) {
-  return ((F + slices - 1) / slices + 63) / 64 * 64;
-}
-
-template <int SLICES>   // face slices per mesh (grid y): 4, 8 or 16 -- a template so that the slice arithmetic stays compile-time
-__global__ __launch_bounds__(TPB) void k_setup(const float* __restrict__ verts,
-                                               const int64_t* __restrict__ faces,
-                                               const float* __restrict__ cams, int V, int F, int H,
-                                               float offset_z, int mode, float margin, RasterWs ws,
-                                               uint8_t* __restrict__ vis, float* __restrict__ proj_xy) {
-  extern __shared__ float s_v[];  // [V][3], then [tiles^2] int counters and this slice's mask words (if they fit)
-  __shared__ float s_red[4][4];
-  const int n = blockIdx.x, slice = blockIdx.y, tid = threadIdx.x;
-  const float* cam = cams ? cams + 7 * (size_t)n : nullptr;
-  const int tiles_ = (H + CNT_TILE - 1) / CNT_TILE, tt_ = tiles_ * tiles_;
-  const bool lds_cnt = tt_ <= SETUP_LDS_TILES;
-  int* s_cnt = reinterpret_cast<int*>(s_v + 3 * V);
-  if (lds_cnt)
-    for (int i = tid; i < tt_; i += TPB) s_cnt[i] = 0;
-  const int q = setup_slice_faces(F, SLICES);
-  const int f_lo = slice * q, f_hi = min(F, f_lo + q);
-  // coarse face masks: bit f of row (cty, ctx) <=> the box of face f may touch that CTILE x CTILE tile
-  const int ctiles_ = (H + CTILE - 1) / CTILE, mwords = 2 * ((F + 63) / 64);  // u32 words per row
-  const int rows = ctiles_ * ctiles_;
-  const int w_lo = f_lo >> 5, w_n = max(0, min(mwords, (f_lo + q) >> 5) - w_lo);  // this slice's words of a row
-  const bool lds_mask = (size_t)rows * w_n * sizeof(unsigned) <= (size_t)SETUP_LDS_MASK_BYTES;
-  unsigned* g_mask = ws.cmask + (size_t)n * rows * mwords;              // zeroed by the host if !lds_mask
-  unsigned* s_mask = reinterpret_cast<unsigned*>(s_cnt + (lds_cnt ? tt_ : 0));
-  if (lds_mask)
-    for (int i = tid; i < rows * w_n; i += TPB) s_mask[i] = 0u;
-  for (int v = tid; v < V; v += TPB) {
-    const float* x = verts + ((size_t)n * V + v) * 3;
-    float px, py, pz;
-    if (mode == 0) {
-      project_point(cam, x[0], x[1], x[2], offset_z, px, py, pz);
-      // NeuralRenderer.project_points of the same vertices and cameras (nmr.py:127-129: proj_fn(...)[:, :, :2]) is
-      // this very (px, py): handed out on request (AcfmSilExtras.proj_xy) instead of being projected again
-      if (proj_xy && slice == 0) { proj_xy[((size_t)n * V + v) * 2] = px; proj_xy[((size_t)n * V + v) * 2 + 1] = py; }
-      py = py * -1.0f;
-    } else {
-      px = x[0]; py = x[1]; pz = x[2];
-    }
-    if (mode != 2) {
-      px = -px;               // view R = diag(-1, 1, 1)
-      pz = pz + ACFM_EYE_Z;   // view T = (0, 0, 2.732)
-    }
-    s_v[3 * v + 0] = px; s_v[3 * v + 1] = py; s_v[3 * v + 2] = pz;
-    if (slice == 0) {
-      float* o = ws.ndc + ((size_t)n * V + v) * 3;
-      o[0] = px; o[1] = py; o[2] = pz;
-      // zeroed here instead of by launches of their own: the visible-vertex bytes the raster kernel
-      // marks, and the NDC-gradient scratch the backward accumulates into (k_project_bwd<1> leaves
-      // it zeroed again after reading it)
-      if (vis) vis[(size_t)n * V + v] = 0;
-      ws.grad_ndc[((size_t)n * V + v) * 2] = 0.f;
-      ws.grad_ndc[((size_t)n * V + v) * 2 + 1] = 0.f;
-      ws.grad_fix[((size_t)n * V + v) * 2] = 0;
-      ws.grad_fix[((size_t)n * V + v) * 2 + 1] = 0;
-    }
-  }
-  __syncthreads();
-  const float INF = __builtin_inff();
-  float bx0 = INF, bx1 = -INF, by0 = INF, by1 = -INF;
-  bool big = false;
-  auto count_box = [&](int xa, int ya, int xb, int yb) {   // pixel range (clamped to the image) -> +1 on its 8x8 blocks
-    xa /= CNT_TILE; ya /= CNT_TILE; xb /= CNT_TILE; yb /= CNT_TILE;
-    if ((xb - xa + 1) * (yb - ya + 1) > 256) {
-      big = true;  // too many tiles to count one by one: every tile of the mesh gets +1 below
-    } else
-      for (int ty = ya; ty <= yb; ++ty)
-        for (int tx = xa; tx <= xb; ++tx) {
-          if (lds_cnt) atomicAdd(&s_cnt[ty * tiles_ + tx], 1);
-          else atomicAdd(&ws.tile_cnt[((size_t)n * tiles_ + ty) * tiles_ + tx], 1);
-        }
-  };
-  for (int f = f_lo + tid; f < f_hi; f += TPB) {
-    const int64_t* fi = faces + ((size_t)n * F + f) * 3;
-    int i0 = (int)fi[0], i1 = (int)fi[1], i2 = (int)fi[2];
-    i0 = min(max(i0, 0), V - 1); i1 = min(max(i1, 0), V - 1); i2 = min(max(i2, 0), V - 1);
-    const float x0 = s_v[3 * i0], y0 = s_v[3 * i0 + 1], z0 = s_v[3 * i0 + 2];
-    const float x1 = s_v[3 * i1], y1 = s_v[3 * i1 + 1], z1 = s_v[3 * i1 + 2];
-    const float x2 = s_v[3 * i2], y2 = s_v[3 * i2 + 1], z2 = s_v[3 * i2 + 2];
-    const float area = edge_fn(x2, y2, x0, y0, x1, y1);
-    const bool degenerate = (area <= ACFM_K_EPS && area >= -1.0f * ACFM_K_EPS);
-    float4 b;
-    b.x = min3f(x0, x1, x2) - margin; b.y = max3f(x0, x1, x2) + margin;
-    b.z = min3f(y0, y1, y2) - margin; b.w = max3f(y0, y1, y2) + margin;
-    if (degenerate) {
-      b = make_float4(INF, -INF, INF, -INF);  // fails every "inside box" test
-    } else {
-      bx0 = fminf(bx0, b.x); bx1 = fmaxf(bx1, b.y); by0 = fminf(by0, b.z); by1 = fmaxf(by1, b.w);
-    }
-    const size_t o = (size_t)n * F + f;
-    // (x1, x2) and (y1, y2) sit in aligned register pairs after the 16-byte LDS reads: operands of the packed fp32 pipe
-    FaceRec& r = ws.rec[o];
-    r.box = b;
-    r.a = make_float4(x0, y0, x1, x2);
-    r.b = make_float4(y1, y2, z0, z1);
-    {
-      const float denom = area + ACFM_K_EPS;
-      r.c = make_float4(z2, area, denom, recip_refined(denom));
-      // point_line_dist's own operations on (a, b) = (v0, v1), (v0, v2), (v1, v2): bax = bx - ax, l2 = bax bax + bay bay
-      const float e01x = x1 - x0, e01y = y1 - y0, e02x = x2 - x0, e02y = y2 - y0, e12x = x2 - x1, e12y = y2 - y1;
-      const float l01 = e01x * e01x + e01y * e01y, l02 = e02x * e02x + e02y * e02y, l12 = e12x * e12x + e12y * e12y;
-      const bool deg = (l01 <= ACFM_K_EPS) || (l02 <= ACFM_K_EPS) || (l12 <= ACFM_K_EPS);
-      r.e0 = make_float4(l01, l02, recip_refined(l01), recip_refined(l02));
-      r.e1 = make_float4(l12, recip_refined(l12), deg ? 1.0f : 0.0f, 0.0f);
-    }
-    ws.vidx[o] = make_int4(i0, i1, i2, 0);
-    ws.fvis[o] = 0;
-    if (!degenerate) {
-      // pixel index of an NDC coordinate: i = H-1 - ((c+1)H - 1)/2; one pixel of slack
-      const float hf = (float)H;
-      int xa = (int)floorf(hf - 1.0f - ((b.y + 1.0f) * hf - 1.0f) * 0.5f) - 1;
-      int xb = (int)ceilf(hf - 1.0f - ((b.x + 1.0f) * hf - 1.0f) * 0.5f) + 1;
-      int ya = (int)floorf(hf - 1.0f - ((b.w + 1.0f) * hf - 1.0f) * 0.5f) - 1;
-      int yb = (int)ceilf(hf - 1.0f - ((b.z + 1.0f) * hf - 1.0f) * 0.5f) + 1;
-      if (xb >= 0 && yb >= 0 && xa < H && ya < H) {
-        xa = max(xa, 0); ya = max(ya, 0); xb = min(xb, H - 1); yb = min(yb, H - 1);
-        const unsigned bit = 1u << (f & 31);
-        for (int cy = ya / CTILE; cy <= yb / CTILE; ++cy)
-          for (int cx = xa / CTILE; cx <= xb / CTILE; ++cx) {
-            const int row = cy * ctiles_ + cx;
-            if (lds_mask) atomicOr(&s_mask[row * w_n + ((f >> 5) - w_lo)], bit);
-            else atomicOr(&g_mask[(size_t)row * mwords + (f >> 5)], bit);
-          }
-        // cost estimate for heavy-first scheduling: +1 on every 8x8 block the box may touch.  With the counters in LDS
-        // (images up to 512^2) every slice counts its own faces and stores its plane of ws.tile_part (k_order adds the
-        // four planes): no zero fill, no global atomics; larger images: every slice adds its faces to the zeroed ws.tile_cnt
-        count_box(xa, ya, xb, yb);
-      }
-    }
-  }
-  bx0 = wave_min(bx0); bx1 = wave_max(bx1); by0 = wave_min(by0); by1 = wave_max(by1);
-  const int w = tid >> 6;
-  if ((tid & 63) == 0) { s_red[w][0] = bx0; s_red[w][1] = bx1; s_red[w][2] = by0; s_red[w][3] = by1; }
-  const int any_big = __syncthreads_or(big) ? 1 : 0;  // (also the barrier before the copies below)
-  if (lds_cnt) {
-    int* part = ws.tile_part + ((size_t)slice * gridDim.x + n) * tt_;
-    for (int i = tid; i < tt_; i += TPB) part[i] = s_cnt[i] + any_big;   // this slice's faces: plain stores
-  } else {
-    for (int i = tid; i < tt_; i += TPB)                // ws.tile_cnt was zeroed by the host
-      if (any_big) atomicAdd(&ws.tile_cnt[(size_t)n * tt_ + i], any_big);
-  }
-  if (lds_mask)
-    for (int i = tid; i < rows * w_n; i += TPB)
-      g_mask[(size_t)(i / w_n) * mwords + w_lo + (i % w_n)] = s_mask[i];
-  if (tid == 0) {
-    for (int i = 1; i < 4; ++i) {
-      bx0 = fminf(bx0, s_red[i][0]); bx1 = fmaxf(bx1, s_red[i][1]);
-      by0 = fminf(by0, s_red[i][2]); by1 = fmaxf(by1, s_red[i][3]);
-    }
-    ws.mbox[(size_t)n * SLICES + slice] = make_float4(bx0, bx1, by0, by1);
-  }
-}
-
-// Zero-fill by a kernel instead of hipMemsetAsync: a memset node in front of k_setup came out
-// wrong when the call was captured into a hipGraph and replayed (tests/test_gpu_render.py::
-// test_hip_graph_capture_and_replay); kernel nodes replay reliably, so the library uses no memsets.
-__global__ void k_zero_bytes(unsigned char* __restrict__ p, size_t nbytes) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t nw = nbytes >> 2;
-  if (i < nw) reinterpret_cast<unsigned*>(p)[i] = 0u;
-  if (i < (nbytes & 3)) p[(nw << 2) + i] = 0;
-}
-// large 16-byte-aligned buffers (atlas gradients, the solver's identity rows): 16-byte stores, 4 per thread
-__global__ __launch_bounds__(256) void k_zero_vec(uint4* __restrict__ p, size_t n16) {
-  const size_t base = (size_t)blockIdx.x * 1024 + threadIdx.x;
-  const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const size_t i = base + 256 * (size_t)k;
-    if (i < n16) p[i] = z;
-  }
-}
-int zero_async(void* p, size_t nbytes, hipStream_t st) {
-  if (nbytes == 0) return ACFM_OK;
-  if (((uintptr_t)p & 3) != 0) return ACFM_E_BADARG;
-  if (nbytes >= (1u << 16) && ((uintptr_t)p & 15) == 0) {
-    const size_t n16 = nbytes >> 4;
-    hipLaunchKernelGGL(k_zero_vec, dim3((unsigned)((n16 + 1023) / 1024)), dim3(256), 0, st, (uint4*)p, n16);
-    p = (unsigned char*)p + (n16 << 4);
-    nbytes &= 15;
-    if (nbytes == 0) return hipGetLastError() == hipSuccess ? ACFM_OK : ACFM_E_LAUNCH;
-  }
-  const size_t n = (nbytes >> 2) > 4 ? (nbytes >> 2) : 4;
-  hipLaunchKernelGGL(k_zero_bytes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (unsigned char*)p, nbytes);
-  return hipGetLastError() == hipSuccess ? ACFM_OK : ACFM_E_LAUNCH;
-}
-
-// ------------------------------------------------------------------------------- scheduling
-// Heavy-first order.  Per-block work is heavy-tailed (dense clusters of tiny faces: a block can
-// take 20x the average), so every XCD group visits its (mesh, block) entries in descending cost
-// class; the long blocks start first and the short ones fill in behind them.
-// Entry e of group g  <->  mesh (e / tt) * G + g, block e % tt   (G = 8 groups if N % 8 == 0, else 1).
-// The cost of a block is the face count of its 16x16 tile (k_setup); count 0 = no face box comes
-// near: the entry is flagged and the raster kernels write that block's zeros without looking at
-// the mesh at all.
-constexpr int NCLASS = 10;
-// (the classes above 160 exist to ORDER the heaviest blocks: at 64 frames the blocks of >= 240 face boxes -- 89 of
-// 15 474, 3 % of the work -- start first and still run for the whole launch; see the split rule in k_order.  Every
-// class costs k_order a ballot per entry and pass: 12 classes measured 18.1 us per launch against 13.3 with 8)
-__device__ __forceinline__ int cost_class(int c) {
-  return c >= 240 ? 0 : c >= 200 ? 1 : c >= 160 ? 2 : c >= 112 ? 3 : c >= 80 ? 4 : c >= 56 ? 5 : c >= 36 ? 6 : c >= 20 ? 7 : c >= 1 ? 8 : 9;
-}
+// cost count of a block (k_setup, k_order): goes into the stamps of the diagnostic build
 __device__ __forceinline__ int block_cost(const RasterWs& ws, int n, int bl, int H) {
   const int blocks = (H + RBLK - 1) / RBLK, tiles = (H + CNT_TILE - 1) / CNT_TILE;
   const int by = bl / blocks, bx = bl % blocks;
   return ws.tile_cnt[((size_t)n * tiles + by * RBLK / CNT_TILE) * tiles + bx * RBLK / CNT_TILE];
-}
-template <bool MORE>   // MORE: k_setup ran 8 or 16 face slices per mesh (few meshes); false: the usual four
-__global__ __launch_bounds__(1024) void k_order(RasterWs ws, int N, int tt, int H, int g_split_dev) {
-  // counting sort by cost class without atomics: every wave counts its entries per class (ballots,
-  // wave-uniform counters), the counts are prefix-summed over (class, wave), and every wave then
-  // scatters its entries from its own running offsets.  Deterministic order.
-  constexpr int NW = 16;   // waves of the workgroup
-  __shared__ int s_cnt[NCLASS][NW], s_off[NCLASS][NW], s_hist[NCLASS], s_split;
-  const int G = gridDim.x, g = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int per = (N / G) * tt;
-  const int iters = (per + (int)blockDim.x - 1) / (int)blockDim.x;
-  // entry e = m tt + bl  <->  mesh m G + g, block bl; its cost is tile_cnt[mesh][bl] (CNT_TILE == RBLK).
-  // (m, bl) advance with e: no integer divisions in the loops (they were 2000 VALU instructions per wave).
-  static_assert(CNT_TILE == RBLK, "cost counters are per raster block");
-  const int m_first = (int)threadIdx.x / tt, bl_first = (int)threadIdx.x % tt;
-  if constexpr (MORE) {
-    // the mesh boxes: k_setup left one box per face slice; the raster kernels test a block against the mesh's box: with
-    // more than four slices it is joined here, once, into the first slot
-    for (int m = threadIdx.x; m < N / G; m += blockDim.x) {
-      float4* mb = ws.mbox + (size_t)(m * G + g) * ws.slices;
-      float4 u = mb[0];
-      for (int i = 1; i < ws.slices; ++i) {
-        const float4 m2 = mb[i];
-        u.x = fminf(u.x, m2.x); u.y = fmaxf(u.y, m2.y); u.z = fminf(u.z, m2.z); u.w = fmaxf(u.w, m2.w);
-      }
-      mb[0] = u;
-    }
-  }
-  constexpr int OCH = 8;   // entries per thread whose cost loads are in flight together
-  const bool parts = tt <= SETUP_LDS_TILES;   // k_setup kept its counters in LDS: one plane per face slice
-  int cnt[NCLASS];
-#pragma unroll
-  for (int c = 0; c < NCLASS; ++c) cnt[c] = 0;
-  int m1 = m_first, bl1 = bl_first;
-  int cst0[OCH];          // the costs of the first OCH entries of this thread: all of them up to 8192 entries per group
-                          // (64 frames @256^2), so that the scatter pass below does not load them again
-  for (int it0 = 0; it0 < iters; it0 += OCH) {
-    int cst[OCH];
-#pragma unroll
-    for (int u = 0; u < OCH; ++u) {
-      const int e = (it0 + u) * blockDim.x + threadIdx.x;
-      cst[u] = -1;
-      if (it0 + u < iters && e < per) {
-        const size_t o = (size_t)(m1 * G + g) * tt + bl1;
-        if (parts) {   // the four face slices' planes (k_setup); the sum is kept for the later readers (k_tex_cover)
-          const size_t plane = (size_t)N * tt;
-          cst[u] = (ws.tile_part[o] + ws.tile_part[plane + o]) + (ws.tile_part[2 * plane + o] + ws.tile_part[3 * plane + o]);
-          if constexpr (MORE)
-            for (int sl = 4; sl < ws.slices; sl += 4)     // 8 or 16 planes
-              cst[u] += (ws.tile_part[sl * plane + o] + ws.tile_part[(sl + 1) * plane + o]) +
-                        (ws.tile_part[(sl + 2) * plane + o] + ws.tile_part[(sl + 3) * plane + o]);
-          ws.tile_cnt[o] = cst[u];
-        } else {
-          cst[u] = ws.tile_cnt[o];
-        }
-      }
-      bl1 += blockDim.x;
-      while (bl1 >= tt) { bl1 -= tt; ++m1; }
-      if (it0 == 0) cst0[u] = cst[u];
-    }
-#pragma unroll
-    for (int u = 0; u < OCH; ++u) {
-      const int cl = cst[u] < 0 ? -1 : cost_class(cst[u]);
-#pragma unroll
-      for (int c = 0; c < NCLASS; ++c) cnt[c] += __popcll(__ballot(cl == c));
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int c = 0; c < NCLASS; ++c) s_cnt[c][wv] = cnt[c];
-  }
-  __syncthreads();
-  if (threadIdx.x < NCLASS) {   // per class: total, then (below) the offsets of the waves inside the class
-    int t = 0;
-    for (int w = 0; w < NW; ++w) t += s_cnt[threadIdx.x][w];
-    s_hist[threadIdx.x] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < NCLASS) {
-    int acc = 0;
-    for (int c = 0; c < (int)threadIdx.x; ++c) acc += s_hist[c];
-    for (int w = 0; w < NW; ++w) { s_off[threadIdx.x][w] = acc; acc += s_cnt[threadIdx.x][w]; }
-  }
-  if (threadIdx.x == 0) {
-    int nw = 0;
-    for (int c = 0; c < NCLASS - 1; ++c) nw += s_hist[c];
-    ws.n_work[g] = nw;   // the flagged-empty class sits at the end of the order
-    // Split the heaviest blocks over four workgroups each?  It adds ~25 % work to those blocks and shortens them about
-    // 3x.  A launch lasts at least as long as its longest block (per-block stamps at 64 frames @256^2: the blocks of
-    // ~300 face boxes start at t = 0 and end with the kernel, 225 us, while the work spread over the wave slots comes to
-    // 195 us), so a block is split when its cost exceeds `ratio` x the group's mean work per wave slot (512 slots per
-    // XCD at 16 one-wave workgroups per CU): a whole small launch, the top few dozen blocks of a large one.
-    // split_mode < 0: ratio = -split_mode / 4 (default -5: 1.25).
-    const int mid[NCLASS] = {290, 220, 180, 136, 96, 68, 46, 28, 10, 0};
-    long total = 0;
-    for (int c = 0; c < NCLASS; ++c) total += (long)s_hist[c] * mid[c];
-    int max_class = -1;                      // split the classes 0 .. max_class
-    if (ws.split_slots > 0) {
-      if (g_split_dev > 0) max_class = SPLIT_MAX_CLASS;
-      else if (g_split_dev < 0)
-        for (int c = 0; c <= SPLIT_MAX_CLASS; ++c)
-          if (4L * mid[c] * 512 > (long)(-g_split_dev) * total) max_class = c;
-    }
-    s_split = max_class;
-  }
-  __syncthreads();
-  const int split_slots = ws.split_slots, split_class = s_split;
-  // pass 2: scatter (order inside a class is arbitrary: results never depend on it)
-  int off[NCLASS];
-#pragma unroll
-  for (int c = 0; c < NCLASS; ++c) off[c] = s_off[c][wv];
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  int* ord = ws.order + (size_t)g * per;
-  m1 = m_first; bl1 = bl_first;
-  for (int it0 = 0; it0 < iters; it0 += OCH) {
-    int cst[OCH];
-#pragma unroll
-    for (int u = 0; u < OCH; ++u) {
-      const int e = (it0 + u) * blockDim.x + threadIdx.x;
-      if (it0 == 0) cst[u] = cst0[u];
-      else cst[u] = (it0 + u < iters && e < per) ? ws.tile_cnt[(size_t)(m1 * G + g) * tt + bl1] : -1;
-      bl1 += blockDim.x;
-      while (bl1 >= tt) { bl1 -= tt; ++m1; }
-    }
-#pragma unroll
-    for (int u = 0; u < OCH; ++u) {
-      const int e = (it0 + u) * blockDim.x + threadIdx.x;
-      const int cls = cst[u] < 0 ? -1 : cost_class(cst[u]);
-#pragma unroll
-      for (int c = 0; c < NCLASS; ++c) {
-        const unsigned long long m = __ballot(cls == c);
-        if (cls == c) {
-          const int pos = off[c] + __popcll(m & lt);
-          ord[pos] = e | (c == NCLASS - 1 ? ENTRY_EMPTY : 0) | ((c <= split_class && pos < split_slots) ? ENTRY_SPLIT : 0);
-        }
-        off[c] += __popcll(m);
-      }
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------- tile skeleton
@@ -804,12 +426,6 @@ __device__ __forceinline__ void walk_wave(LT& L, const Tile& t, int H, int list_
 // coarse tile (k_setup): lane i expands mask word i into the wave's face-id list (ascending), then
 // 64 ids per round lane i tests face i's box; survivors are compacted with one ballot, face
 // order kept.  No barriers: the workgroup is one wave.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ int wave_inclusive_scan(int x, int lane) {
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
@@ -914,67 +530,6 @@ __device__ __forceinline__ void bin_and_walk(const RasterWs& ws, const Tile& t, 
   }
 }
 
-struct Hit { float pz, sd, c0, c1, c2, d01, d02, d12; };
-
-// One pixel against one face, split in two stages so callers can drop a face after the cheap
-// half.  Every rejection of the oracle (oracle_rasterize) is a pure filter, so evaluating
-// them in a different order keeps the accepted set -- and every accepted value -- identical.
-//   stage 1: barycentrics (IEEE divisions), depth pz, inside flag;  rejects pz < 0
-//   stage 2: the three edge distances;  rejects !inside && d >= blur
-// INSIDE_ONLY: the caller keeps only pixels inside the face (blur == 0): the others leave before
-// the clipped barycentrics and the depth are computed.
-// clip_barycentric_coords (the texture branch): clamp to [0,1], renormalise by max(sum, 1e-5); and the depth
-// interpolated with whichever barycentrics apply.  One definition each: the K-nearest forward evaluates the
-// clipped depth of a covering face too (ACFM_RECORD_COVER) and must land on the bits of the K = 1 render.
-__device__ __forceinline__ void clip_bary(float& c0, float& c1, float& c2) {
-  c0 = fmaxf(fminf(c0, 1.0f), 0.0f);
-  c1 = fmaxf(fminf(c1, 1.0f), 0.0f);
-  c2 = fmaxf(fminf(c2, 1.0f), 0.0f);
-  const float s = fmaxf(c0 + c1 + c2, 1e-5f);
-  const float rs = recip_refined(s);
-  c0 = div_by(c0, s, rs); c1 = div_by(c1, s, rs); c2 = div_by(c2, s, rs);
-}
-__device__ __forceinline__ float bary_depth(float c0, float c1, float c2, float z0, float z1, float z2) {
-  return c0 * z0 + c1 * z1 + c2 * z2;
-}
-
-template <bool CLIP, bool INSIDE_ONLY = false>
-__device__ __forceinline__ bool test_face_depth(float xf, float yf, const float4& A, const float4& B,
-                                                float z2, float denom, float r, Hit& h, bool& inside) {
-  const float x0 = A.x, y0 = A.y, x1 = A.z, x2 = A.w, y1 = B.x, y2 = B.y;
-  const float z0 = B.z, z1 = B.w;
-  // three IEEE divisions by the same denominator denom = area + kEps share one refined reciprocal r (acfm_common.h),
-  // both computed once per face by k_setup (FaceRec.c) with these very operations
-  auto div = [&](float x) { return div_by(x, denom, r); };
-  const float w0 = div(edge_fn(xf, yf, x1, y1, x2, y2));
-  const float w1 = div(edge_fn(xf, yf, x2, y2, x0, y0));
-  const float w2 = div(edge_fn(xf, yf, x0, y0, x1, y1));
-  float c0 = w0, c1 = w1, c2 = w2;
-  inside = (w0 > 0.0f) && (w1 > 0.0f) && (w2 > 0.0f);
-  if (INSIDE_ONLY && !inside) return false;
-  if (CLIP) clip_bary(c0, c1, c2);
-  const float pz = bary_depth(c0, c1, c2, z0, z1, z2);
-  h.pz = pz; h.c0 = c0; h.c1 = c1; h.c2 = c2;
-  return !(pz < 0.0f);
-}
-
-// tpar (optional): the clamped segment parameters of the three edges (01, 02, 12), for the backward
-__device__ __forceinline__ bool test_face_dist(float xf, float yf, const float4& A, const float4& B,
-                                               float blur, bool inside, Hit& h, float* tpar = nullptr) {
-  const float x0 = A.x, y0 = A.y, x1 = A.z, x2 = A.w, y1 = B.x, y2 = B.y;
-  // edges 01 and 02 (both start at vertex 0) share the packed pipe, edge 12 goes through the scalar one
-  const v2f ax = {x0, x0}, ay = {y0, y0}, bx = {A.z, A.w}, by = {B.x, B.y};
-  v2f t2;
-  const v2f d2 = point_line_dist2(xf, yf, ax, ay, bx, by, tpar ? &t2 : nullptr);
-  h.d01 = d2.x;
-  h.d02 = d2.y;
-  h.d12 = point_line_dist(xf, yf, x1, y1, x2, y2, tpar ? tpar + 2 : nullptr);
-  if (tpar) { tpar[0] = t2.x; tpar[1] = t2.y; }
-  const float d = fminf(fminf(h.d01, h.d02), h.d12);
-  h.sd = inside ? -d : d;
-  return inside || !(d >= blur);
-}
-
 // The same with the per-edge constants of the candidate: E0 = (|e01|^2, |e02|^2, r01, r02),
 // E1 = (|e12|^2, r12, degenerate flag, -).  Operation for operation point_line_dist / point_line_dist2 minus what does
 // not depend on the pixel; a face with a degenerate edge (flag) must take test_face_dist (its distance-to-endpoint branch).
@@ -1032,76 +587,6 @@ __device__ __forceinline__ unsigned long long make_key(float pz, int fid) {
 }
 
 // ------------------------------------------------------------------------------- forward
-// Storage type of images and masks: float, or IEEE half with ACFM_STORE_F16 (AcfmRasterTuning.flags bit 1, BASELINE
-// config 5 "fp16 render with fp32 loss accumulate").  Only what is STORED changes: every accept / reject decision,
-// depth, blend factor and loss sum is computed in fp32 exactly as in the fp32 build, so face ids are identical.
-typedef _Float16 half_t;
-__device__ __forceinline__ float ld_real(const void* p, size_t i, int h16) {
-  return h16 ? (float)reinterpret_cast<const half_t*>(p)[i] : reinterpret_cast<const float*>(p)[i];
-}
-// (plain stores, also in st_face: non-temporal ones on these 4-byte-per-pixel planes measured 75 -> 123 us on the
-// texture forward, see fwd_fill_block)
-__device__ __forceinline__ void st_real(void* p, size_t i, float v, int h16) {
-  if (h16) reinterpret_cast<half_t*>(p)[i] = (half_t)v;
-  else reinterpret_cast<float*>(p)[i] = v;
-}
-__device__ __forceinline__ float4 ld4_real(const void* p, size_t i4, int h16) {   // elements 4 i4 .. 4 i4 + 3 (aligned)
-  if (!h16) return reinterpret_cast<const float4*>(p)[i4];
-  typedef half_t h4 __attribute__((ext_vector_type(4)));
-  const h4 v = reinterpret_cast<const h4*>(p)[i4];
-  return make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
-}
-__device__ __forceinline__ void st_face(void* p, size_t i, long long id, int h16) {   // nearest-face plane
-  if (h16) reinterpret_cast<int32_t*>(p)[i] = (int32_t)id;
-  else reinterpret_cast<int64_t*>(p)[i] = (int64_t)id;
-}
-
-struct FwdOut {
-  unsigned long long* dbg;   // diagnostic build only: per-block (t_start, t_end, hw_id) stamps
-  int h16;                   // ACFM_STORE_F16: mask / imgs / sil / atlas / references are IEEE half, p2f is an int32 [N,H,H] plane
-  void* mask;                // soft: [N,H,H] (real_t = float, or half with h16)
-  void* p2f;                 // [N,H,H,kout] int64; h16: [N,H,H] int32 (kout = 1)
-  int kout;                  // soft: K (all kept faces) or 1 (nearest face only)
-  unsigned long long* kth;   // soft, optional: [N,H,H] largest kept key if K faces kept, else ~0
-  uint8_t* vis;              // optional: [N,V] vertices of every nearest face
-  int V;
-  // texture branch (TEX)
-  const float* vrgb;         // optional [N,V,3]: per-vertex colours instead of an atlas (viz)
-  const void* atlas;         // [N,F,R,R,3] real_t
-  void* imgs;                // [N,3,H,H] real_t
-  void* sil;                 // [N,H,H] real_t
-  int32_t* tidx;             // [N,H,H]
-  int R;
-  float gamma;
-  float box_shrink;          // > 0: the workspace was set up with a larger blur margin; boxes are tightened by this much
-  int atlas_n;               // number of distinct atlases: mesh n samples atlas n % atlas_n
-  float sig_scale;           // log2(e) / sigma (sigmoid_scale), computed on the host: a kernel argument can be re-read
-                             // from the kernarg segment with a scalar load where a computed value would be spilled
-  // fused render + silhouette losses (acfm_sil_loss_forward): the block's partial sums of the loss terms leave
-  // with the mask; lpart == null: plain render
-  const void* lgt;           // [lrb,H,H] real_t ground-truth masks (may be null)
-  const void* ledt;          // [lrb,H,H] real_t distance transforms (may be null)
-  int lrb;                   // references: mesh n is compared with reference n % lrb
-  float4* lpart;             // [N,blocks^2,4] (ws.lpart)
-  // fused texture render + masked MSE (acfm_tex_mse_forward): lpart[..].x takes the block's sum of
-  // (tex m - img m)^2 - (img m)^2 over its covered pixels (elsewhere tex = 0 and the difference vanishes)
-  const void* timg;          // [lrb,3,H,H] real_t reference images
-  const void* tmask;         // [lrb,H,H] real_t reference masks
-  // ACFM_RECORD_COVER: the K-nearest forward writes ws.cover (cover_out), the texture forward that takes the
-  // workspace over reads it (cover_in) instead of walking the faces
-  int* cover_out;
-  const int* cover_in;
-  // acfm_sil_forward_prefill: the K-nearest forward also stores the CONSTANT outputs of the texture render that will
-  // take this workspace over (acfm_tex_forward ws_ready = 3) on the blocks no face comes near -- the same blocks that
-  // render would fill (one emptiness rule: the cost counts of this workspace); here the stores drain behind the walk
-  // of the blocks with work, there they were 24 of the kernel's 36 us.  float storage only.
-  float* pf_imgs;            // [N,3,H,H] -> 0
-  float* pf_sil;             // [N,H,H] -> 0
-  int64_t* pf_p2f;           // [N,H,H,1] -> -1
-  int32_t* pf_tidx;          // [N,H,H] -> -1
-  int prefilled;             // texture forward from the cover plane: the empty blocks hold their constants already
-};
-
 __device__ __forceinline__ void mark_visible(const RasterWs& ws, const FwdOut& out, int n, int F, int f) {
   const int4 vi = ws.vidx[(size_t)n * F + f];
   uint8_t* v = out.vis + (size_t)n * out.V;
@@ -1799,39 +1284,8 @@ __global__ __launch_bounds__(64 * COVER_WPB) void k_tex_cover(RasterWs ws, int N
 }
 
 // ------------------------------------------------------------------------------- backward
-// PointLineDistanceBackward with the clamped t held constant.  t is the forward's own clamped
-// parameter (point_line_dist, same expression; 1 for a degenerate segment: then q = b exactly, the gradient of a
-// is g 0 e = 0 and that of b is g 2 (b - p) = -2 (p - b) g, the degenerate branch of the reference bit for bit).
-__device__ __forceinline__ void point_line_dist_bwd(float px, float py, float ax, float ay, float bx,
-                                                    float by, float t, float g, float& gax, float& gay,
-                                                    float& gbx, float& gby) {
-  const float qx = (1.0f - t) * ax + t * bx, qy = (1.0f - t) * ay + t * by;
-  const float ex = 2.0f * (qx - px), ey = 2.0f * (qy - py);
-  gax = g * (1.0f - t) * ex; gay = g * (1.0f - t) * ey;
-  gbx = g * t * ex; gby = g * t * ey;
-}
-
 constexpr int BWD_CAP = 64;   // candidate-list capacity of the backward (LDS per wave: 108 B per slot)
 using BwdList = CandListT<BWD_CAP>;
-// Upstream gradient of the mask: either given per pixel (grad_mask) or, for the fused render+loss operator,
-// formed on the fly from the references and the per-mesh gradients of the four loss terms -- k_mask_losses_bwd's
-// expression, operation for operation: go0 sign(m - g) / HW + go1 g + go2 (1 - g) + go3 e / HW.
-struct BwdGrad {
-  const float* grad_mask;    // [N,H,H] (always float), or null: fused
-  const void* lgt;           // [lrb,H,H] real_t (may be null)
-  const void* ledt;          // [lrb,H,H] real_t (may be null)
-  const float* go;           // [N,4]
-  int lrb;
-  int h16;                   // mask / lgt / ledt are half
-};
-// Deterministic accumulation (AcfmRasterTuning.flags bit 0): every row sum (a fixed DPP tree of values that are
-// themselves computed deterministically) is converted to 64-bit fixed point (2^-36 units) before it is added to
-// the candidate's LDS accumulator and, from there, to the vertex's accumulator in memory -- integer addition is
-// associative, so the result does not depend on the order in which blocks, rows and atomics happen to be
-// served: two runs are bit-identical.  Rounding each contribution to 2^-36 (1.5e-11) keeps it within 1e-6 of the
-// floating-point mode at the gradient scales of this problem (contributions up to ~1, sums up to ~1e3 of 2^27).
-constexpr float FIX_SCALE = 68719476736.0f;          // 2^36
-constexpr float FIX_INV = 1.0f / 68719476736.0f;
 __device__ __forceinline__ void acc_add(float* p, float v) { atomicAdd(p, v); }
 __device__ __forceinline__ void acc_add(long long* p, float v) {
   atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__float2ll_rn(v * FIX_SCALE));
@@ -2008,734 +1462,14 @@ __global__ __launch_bounds__(RT, BWD_WAVES) void k_sil_bwd(RasterWs ws, const vo
   }
 }
 
-// Fused render + loss, finish: per mesh, the block partials of the raster kernel and sum(gt) over the whole image
-// (the blocks without work have m = 0: |m - g| = g, m + g - m g = g) -> out[n] = (mean|m - g|, sum m g,
-// sum(m + g - m g), mean e m), the [N,4] vector of k_mask_losses.  Two short launches, FIN_CHUNKS workgroups per mesh
-// in the first (one workgroup per mesh was latency-bound: 45 us for 64 meshes); every sum is formed in a fixed
-// order (thread-strided partial sums, a fixed tree, then the chunks in order): deterministic, no atomics.
-constexpr int FIN_MAX_CHUNKS = 64;   // (sizes ws.lpart2)
-static int fin_chunks(int N) {       // enough workgroups to fill the chip at any batch size: ~2048 in all
-  int c = 8;
-  while (c < FIN_MAX_CHUNKS && c * N < 2048) c *= 2;
-  return c;
-}
-__global__ __launch_bounds__(TPB) void k_sil_loss_finish1(const float4* __restrict__ lpart, const void* __restrict__ gt,
-                                                           int tt, int HW, int RB, int h16, float* __restrict__ part2) {
-  __shared__ float s_red[TPB][5];
-  const int n = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x, FIN_CHUNKS = gridDim.x;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, gs = 0.f;
-  const float4* p = lpart + (size_t)n * tt * 4;
-  const int np = tt * 4, p_lo = (int)((long long)np * ch / FIN_CHUNKS), p_hi = (int)((long long)np * (ch + 1) / FIN_CHUNKS);
-  for (int i = p_lo + tid; i < p_hi; i += TPB) {
-    const float4 v = p[i];
-    a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
-  }
-  if (gt) {
-    const size_t go = (size_t)(n % RB) * HW;
-    if ((HW & 3) == 0) {
-      const int q = HW / 4, q_lo = (int)((long long)q * ch / FIN_CHUNKS), q_hi = (int)((long long)q * (ch + 1) / FIN_CHUNKS);
-      constexpr int U = 8;                       // loads of a round in flight together
-      for (int i0 = q_lo + tid; i0 < q_hi; i0 += TPB * U) {
-        float4 v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int i = i0 + u * TPB;
-          v[u] = i < q_hi ? ld4_real(gt, go / 4 + i, h16) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) gs += (v[u].x + v[u].y) + (v[u].z + v[u].w);
-      }
-    } else {
-      const int g_lo = (int)((long long)HW * ch / FIN_CHUNKS), g_hi = (int)((long long)HW * (ch + 1) / FIN_CHUNKS);
-      for (int i = g_lo + tid; i < g_hi; i += TPB) gs += ld_real(gt, go + i, h16);
-    }
-  }
-  s_red[tid][0] = a0; s_red[tid][1] = a1; s_red[tid][2] = a2; s_red[tid][3] = a3; s_red[tid][4] = gs;
-  __syncthreads();
-  for (int s = TPB / 2; s > 0; s >>= 1) {
-    if (tid < s)
-#pragma unroll
-      for (int k = 0; k < 5; ++k) s_red[tid][k] += s_red[tid + s][k];
-    __syncthreads();
-  }
-  if (tid < 5) part2[((size_t)n * FIN_CHUNKS + ch) * 5 + tid] = s_red[0][tid];
-}
-__global__ void k_sil_loss_finish2(const float* __restrict__ part2, int N, int HW, int FIN_CHUNKS, float* __restrict__ out) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  float a[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int c = 0; c < FIN_CHUNKS; ++c)
-#pragma unroll
-    for (int k = 0; k < 5; ++k) a[k] += part2[((size_t)n * FIN_CHUNKS + c) * 5 + k];
-  const float hw = (float)HW;
-  out[4 * (size_t)n + 0] = (a[4] + a[0]) / hw;
-  out[4 * (size_t)n + 1] = a[1];
-  out[4 * (size_t)n + 2] = a[4] + a[2];
-  out[4 * (size_t)n + 3] = a[3] / hw;
-}
-
-// Fused texture render + masked MSE, finish: out[n] = (sum over the mesh's blocks of their partial
-// + sum_c sum_px (img_c m)^2) / (3 HW) -- the second term is what an uncovered pixel (tex = 0) contributes.
-__global__ __launch_bounds__(TPB) void k_tex_loss_finish1(const float4* __restrict__ lpart, const void* __restrict__ timg,
-                                                           const void* __restrict__ tmask, int tt, int HW, int RB,
-                                                           int h16, float* __restrict__ part2) {
-  __shared__ float s_red[TPB];
-  const int n = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x, FIN_CHUNKS = gridDim.x;
-  float acc = 0.f;
-  const float4* p = lpart + (size_t)n * tt * 4;
-  const int t_lo = (int)((long long)tt * ch / FIN_CHUNKS), t_hi = (int)((long long)tt * (ch + 1) / FIN_CHUNKS);
-  for (int i = t_lo + tid; i < t_hi; i += TPB) acc += p[4 * (size_t)i].x;
-  const size_t rn = (size_t)(n % RB);
-  const size_t mo = rn * HW, io = rn * 3 * HW;
-  if ((HW & 3) == 0) {
-    const int q = HW / 4, q_lo = (int)((long long)q * ch / FIN_CHUNKS), q_hi = (int)((long long)q * (ch + 1) / FIN_CHUNKS);
-    constexpr int U = 4;
-    for (int i0 = q_lo + tid; i0 < q_hi; i0 += TPB * U) {
-      float4 mk[U], c0[U], c1[U], c2[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int i = i0 + u * TPB;
-        const bool in = i < q_hi;
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        mk[u] = in ? ld4_real(tmask, mo / 4 + i, h16) : z;
-        c0[u] = in ? ld4_real(timg, io / 4 + i, h16) : z;
-        c1[u] = in ? ld4_real(timg, (io + HW) / 4 + i, h16) : z;
-        c2[u] = in ? ld4_real(timg, (io + 2 * (size_t)HW) / 4 + i, h16) : z;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        auto sq = [](float a, float b) { const float v = a * b; return v * v; };
-        acc += (sq(c0[u].x, mk[u].x) + sq(c1[u].x, mk[u].x) + sq(c2[u].x, mk[u].x)) +
-               (sq(c0[u].y, mk[u].y) + sq(c1[u].y, mk[u].y) + sq(c2[u].y, mk[u].y)) +
-               (sq(c0[u].z, mk[u].z) + sq(c1[u].z, mk[u].z) + sq(c2[u].z, mk[u].z)) +
-               (sq(c0[u].w, mk[u].w) + sq(c1[u].w, mk[u].w) + sq(c2[u].w, mk[u].w));
-      }
-    }
-  } else {
-    const int g_lo = (int)((long long)HW * ch / FIN_CHUNKS), g_hi = (int)((long long)HW * (ch + 1) / FIN_CHUNKS);
-    for (int i = g_lo + tid; i < g_hi; i += TPB) {
-      const float mk = ld_real(tmask, mo + i, h16);
-      const float b0 = ld_real(timg, io + i, h16) * mk, b1 = ld_real(timg, io + HW + i, h16) * mk,
-                  b2 = ld_real(timg, io + 2 * (size_t)HW + i, h16) * mk;
-      acc += b0 * b0 + b1 * b1 + b2 * b2;
-    }
-  }
-  s_red[tid] = acc;
-  __syncthreads();
-  for (int s = TPB / 2; s > 0; s >>= 1) {
-    if (tid < s) s_red[tid] += s_red[tid + s];
-    __syncthreads();
-  }
-  if (tid == 0) part2[(size_t)n * FIN_CHUNKS + ch] = s_red[0];
-}
-__global__ void k_tex_loss_finish2(const float* __restrict__ part2, int N, int HW, int FIN_CHUNKS, float* __restrict__ out) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  float a = 0.f;
-  for (int c = 0; c < FIN_CHUNKS; ++c) a += part2[(size_t)n * FIN_CHUNKS + c];
-  out[n] = a / (3.0f * (float)HW);
-}
-
-// ------------------------------------------------------------------------------- projection
-template <bool XY>   // XY: only (x, y) are stored, [N,V,2] (orthographic_proj / project_points)
-__global__ __launch_bounds__(TPB) void k_project(const float* __restrict__ verts,
-                                                 const float* __restrict__ cams, int V, float offset_z,
-                                                 float* __restrict__ proj) {
-  const int n = blockIdx.y;
-  const int v = blockIdx.x * TPB + threadIdx.x;
-  if (v >= V) return;
-  const float* x = verts + ((size_t)n * V + v) * 3;
-  float px, py, pz;
-  project_point(cams + 7 * (size_t)n, x[0], x[1], x[2], offset_z, px, py, pz);
-  if (XY) {
-    float* o = proj + ((size_t)n * V + v) * 2;
-    o[0] = px; o[1] = py;
-  } else {
-    float* o = proj + ((size_t)n * V + v) * 3;
-    o[0] = px; o[1] = py; o[2] = pz;
-  }
-}
-
-// Backward of proj = s * rot(q, X) + (tx, ty, offset_z), q not normalised here:
-//   r      = (q0^2 - u.u) X + 2 (u.X) u + 2 q0 (u x X)
-//   dL/ds  = g.r ; dL/dt = g.xy ; with G = s g:
-//   dL/dq0 = 2 q0 (G.X) + 2 G.(u x X)
-//   dL/du  = -2 (G.X) u + 2 (G.u) X + 2 (u.X) G + 2 q0 (X x G)
-//   dL/dX  = (q0^2 - u.u) G + 2 (G.u) u + 2 q0 (G x u)
-// MODE 1 (NDC2): the upstream gradient is grad_ndc [N,V,2] of the rasteriser
-// (x_ndc = -x_p, y_ndc = -y_p, no z gradient on the silhouette path); MODE 2: the gradient of the
-// (x, y) projection [N,V,2] as it is; MODE 0: all three components [N,V,3].
-template <int MODE>
-__global__ __launch_bounds__(TPB) void k_project_bwd(const float* __restrict__ verts,
-                                                     const float* __restrict__ cams,
-                                                     float* gin /* NDC2: cleared after reading */, int V,
-                                                     float* __restrict__ grad_verts,
-                                                     float* __restrict__ grad_cams,
-                                                     const float* __restrict__ gproj = nullptr /* NDC modes: + [N,V,2] */) {
-  __shared__ float s_red[4][7];
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const float* c = cams + 7 * (size_t)n;
-  const float s = c[0], q0 = c[3], ux = c[4], uy = c[5], uz = c[6];
-  const float uu = ux * ux + uy * uy + uz * uz;
-  const float a = q0 * q0 - uu;
-  float acc[7] = {0, 0, 0, 0, 0, 0, 0};
-  for (int v = tid; v < V; v += TPB) {
-    const float* x = verts + ((size_t)n * V + v) * 3;
-    const float X = x[0], Y = x[1], Z = x[2];
-    float gx, gy, gz;
-    if (MODE == 3) {            // NDC2 in 2^-36 fixed point (deterministic backward)
-      long long* g = reinterpret_cast<long long*>(gin) + ((size_t)n * V + v) * 2;
-      gx = -((float)g[0] * FIX_INV); gy = -((float)g[1] * FIX_INV); gz = 0.f;
-      g[0] = 0; g[1] = 0;
-      if (gproj) { gx += gproj[((size_t)n * V + v) * 2]; gy += gproj[((size_t)n * V + v) * 2 + 1]; }
-    } else if (MODE == 1) {
-      float* g = gin + ((size_t)n * V + v) * 2;
-      gx = -g[0]; gy = -g[1]; gz = 0.f;
-      g[0] = 0.f; g[1] = 0.f;   // the raster workspace's NDC-gradient scratch is left zeroed for the next backward
-      // the gradient of the projection the forward handed out (AcfmSilExtras.proj_xy: a second consumer of the same
-      // vertices and cameras, e.g. the boundary loss): one projection backward for both, no gradient sum afterwards
-      if (gproj) { gx += gproj[((size_t)n * V + v) * 2]; gy += gproj[((size_t)n * V + v) * 2 + 1]; }
-    } else if (MODE == 2) {
-      const float* g = gin + ((size_t)n * V + v) * 2;
-      gx = g[0]; gy = g[1]; gz = 0.f;
-    } else {
-      const float* g = gin + ((size_t)n * V + v) * 3;
-      gx = g[0]; gy = g[1]; gz = g[2];
-    }
-    const float uX = ux * X + uy * Y + uz * Z;
-    const float cx = uy * Z - uz * Y, cy = uz * X - ux * Z, cz = ux * Y - uy * X;  // u x X
-    const float rx = a * X + 2.f * uX * ux + 2.f * q0 * cx;
-    const float ry = a * Y + 2.f * uX * uy + 2.f * q0 * cy;
-    const float rz = a * Z + 2.f * uX * uz + 2.f * q0 * cz;
-    acc[0] += gx * rx + gy * ry + gz * rz;
-    acc[1] += gx;
-    acc[2] += gy;
-    const float Gx = s * gx, Gy = s * gy, Gz = s * gz;
-    const float GX = Gx * X + Gy * Y + Gz * Z;
-    const float Gu = Gx * ux + Gy * uy + Gz * uz;
-    acc[3] += 2.f * q0 * GX + 2.f * (Gx * cx + Gy * cy + Gz * cz);
-    const float xg_x = Y * Gz - Z * Gy, xg_y = Z * Gx - X * Gz, xg_z = X * Gy - Y * Gx;  // X x G
-    acc[4] += -2.f * GX * ux + 2.f * Gu * X + 2.f * uX * Gx + 2.f * q0 * xg_x;
-    acc[5] += -2.f * GX * uy + 2.f * Gu * Y + 2.f * uX * Gy + 2.f * q0 * xg_y;
-    acc[6] += -2.f * GX * uz + 2.f * Gu * Z + 2.f * uX * Gz + 2.f * q0 * xg_z;
-    if (grad_verts) {
-      const float gu_x = Gy * uz - Gz * uy, gu_y = Gz * ux - Gx * uz, gu_z = Gx * uy - Gy * ux;  // G x u
-      float* o = grad_verts + ((size_t)n * V + v) * 3;
-      o[0] = a * Gx + 2.f * Gu * ux + 2.f * q0 * gu_x;
-      o[1] = a * Gy + 2.f * Gu * uy + 2.f * q0 * gu_y;
-      o[2] = a * Gz + 2.f * Gu * uz + 2.f * q0 * gu_z;
-    }
-  }
-  if (!grad_cams) return;
-#pragma unroll
-  for (int i = 0; i < 7; ++i) acc[i] = wave_sum(acc[i]);
-  const int w = tid >> 6;
-  if ((tid & 63) == 0)
-    for (int i = 0; i < 7; ++i) s_red[w][i] = acc[i];
-  __syncthreads();
-  if (tid < 7) grad_cams[7 * (size_t)n + tid] = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
-}
-
-// ------------------------------------------------------------------------------- texture bwd
-__global__ void k_tex_bwd(const float* __restrict__ grad_imgs, const int32_t* __restrict__ tidx,
-                          size_t HW, size_t total, float* __restrict__ grad_atlas) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const int32_t t = tidx[i];
-  if (t < 0) return;
-  const size_t n = i / HW, p = i % HW;
-  const float* g = grad_imgs + n * 3 * HW + p;
-  // d rgb / d texel = wnum / (wnum + delta) = 1 in fp32 (wnum >= 0.5, delta = 1e-10)
-  atomicAdd(&grad_atlas[(size_t)t * 3 + 0], g[0]);
-  atomicAdd(&grad_atlas[(size_t)t * 3 + 1], g[HW]);
-  atomicAdd(&grad_atlas[(size_t)t * 3 + 2], g[2 * HW]);
-}
-// Gather form of the same gradient, one wave per four (atlas, face) slots: for each it visits the pixels of the
-// face's box in every mesh that samples this atlas (the G hypotheses of a frame), adds the
-// gradients of the pixels whose texel belongs to the face into 3 R^2 LDS accumulators and stores
-// the face's texels -- zeros included -- with plain coalesced stores.  No global atomics (agent-
-// scope float atomics execute at the memory side on this multi-XCD part: 2 M of them took 87 us)
-// and no zero fill of the 35 MB gradient.  Needs the face boxes of the forward's workspace.
-// i / w and i % w for 0 <= i < 2^23, 0 < w < 2^12 without the ~35-instruction integer division
-__device__ __forceinline__ void divmod_small(int i, int w, float rw, int& q, int& r) {
-  q = (int)((float)i * rw);
-  r = i - q * w;
-  if (r < 0) { --q; r += w; }
-  if (r >= w) { ++q; r -= w; }
-}
-constexpr int TEXG_MAX_R = 8;
-constexpr int TEXG_FPW = 4;      // faces per wave: their boxes, texel indices and gradients are loaded side by side
-constexpr int TEXG_U = 2;        // big boxes: 64 U pixels per round, all their loads in flight together
-constexpr int TEXG_WAVES = 8;    // waves per SIMD (U = 2 at 8 waves: 39.8 us per launch; U = 4 at 6 waves 41.4; U = 8 at 5 waves -- 92 VGPRs -- 45.2)
-// Upstream gradient of the rendered image: given ([N,3,H,H]) or, for the fused texture render + masked MSE, formed
-// on the fly from the rendered image, the reference image and mask and the per-mesh gradient of the loss --
-// k_tex_mse_bwd's expression: w (tex m - img m) m with w = go[n] 2 / (3 HW).
-struct TexGrad {
-  const float* grad_imgs;    // [N,3,H,H] (always float), or null: fused
-  const void* imgs;          // [N,3,H,H] real_t, the forward's output
-  const void* timg;          // [rb,3,H,H] real_t
-  const void* tmask;         // [rb,H,H] real_t
-  const float* go;           // [N]
-  int rb;
-  int h16;
-};
-struct TexGradN {            // the same for one mesh n
-  const float* g;
-  const void *im, *ri, *rm;
-  size_t io, ro, mo;
-  float w;
-  size_t HW;
-  int h16;
-  __device__ __forceinline__ void load(size_t p, float& r, float& gg, float& b) const {
-    if (g) { r = g[p]; gg = g[HW + p]; b = g[2 * HW + p]; return; }
-    const float mk = ld_real(rm, mo + p, h16);
-    r = w * (ld_real(im, io + p, h16) * mk - ld_real(ri, ro + p, h16) * mk) * mk;
-    gg = w * (ld_real(im, io + HW + p, h16) * mk - ld_real(ri, ro + HW + p, h16) * mk) * mk;
-    b = w * (ld_real(im, io + 2 * HW + p, h16) * mk - ld_real(ri, ro + 2 * HW + p, h16) * mk) * mk;
-  }
-};
-__device__ __forceinline__ TexGradN tex_grad_of(const TexGrad& tg, int n, size_t HW) {
-  TexGradN t = {};
-  t.HW = HW;
-  if (tg.grad_imgs) { t.g = tg.grad_imgs + (size_t)n * 3 * HW; return t; }
-  const size_t rn = (size_t)(n % tg.rb);
-  t.im = tg.imgs; t.ri = tg.timg; t.rm = tg.tmask; t.h16 = tg.h16;
-  t.io = (size_t)n * 3 * HW; t.ro = rn * 3 * HW; t.mo = rn * HW;
-  t.w = tg.go[n] * 2.0f / (3.0f * (float)HW);
-  return t;
-}
-__global__ __launch_bounds__(256, TEXG_WAVES) void k_tex_bwd_faces(RasterWs ws, TexGrad tgrad,
-                                                       const int32_t* __restrict__ tidx, int N, int F, int H,
-                                                       int R, int NA, float box_shrink,
-                                                       float* __restrict__ grad_atlas) {
-  __shared__ float s_acc[4][TEXG_FPW][3 * TEXG_MAX_R * TEXG_MAX_R];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // Wave q of the launch takes the faces q, q + Q, q + 2Q, q + 3Q of one atlas (Q = ceil(F / FPW)):
-  // neighbouring faces of a mesh tend to be large together, and a wave walks its faces' boxes one
-  // after the other, so they are dealt to different waves.
-  const int Q = (F + TEXG_FPW - 1) / TEXG_FPW;
-  const long long wq = (long long)blockIdx.x * 4 + wv;
-  if (wq >= (long long)NA * Q) return;                       // (whole wave; no workgroup barriers below)
-  const int a = (int)(wq / Q), f0 = (int)(wq % Q);
-  const int R2 = R * R, n3 = 3 * R2;
-  float (*acc)[3 * TEXG_MAX_R * TEXG_MAX_R] = s_acc[wv];
-#pragma unroll
-  for (int k = 0; k < TEXG_FPW; ++k)
-    for (int i = lane; i < n3; i += 64) acc[k][i] = 0.f;
-  wave_lds_sync();
-  const size_t HW = (size_t)H * H;
-  const float hf = (float)H;
-  // lane k < FPW looks after face f0 + k Q
-  const int my_f = f0 + (lane < TEXG_FPW ? lane : 0) * Q;
-  const bool my_live = lane < TEXG_FPW && my_f < F;
-  const int G = N / NA;
-  for (int g = 0; g < G; ++g) {
-    // the FPW boxes (mesh a + g NA), one per lane, turned into pixel ranges (k_setup's formula, one pixel of slack)
-    int xa = 0, ya = 0, w = 1, cnt = 0;
-    const int n = a + g * NA;
-    if (my_live && ws.fvis[(size_t)n * F + my_f]) {          // (a face no pixel shows has no gradient: zeros)
-      float4 b = ws.rec[(size_t)n * F + my_f].box;
-      b.x += box_shrink; b.y -= box_shrink; b.z += box_shrink; b.w -= box_shrink;
-      if (b.x <= b.y && b.z <= b.w) {                        // not a degenerate face (inf, -inf, ..) or an emptied box
-        // pixel range of the box: k_setup's formula with one pixel of slack, then tightened to the
-        // pixels that pass the forward's own test (pixel centre inside the box, same float expressions)
-        xa = (int)floorf(hf - 1.0f - ((b.y + 1.0f) * hf - 1.0f) * 0.5f) - 1;
-        int xb = (int)ceilf(hf - 1.0f - ((b.x + 1.0f) * hf - 1.0f) * 0.5f) + 1;
-        ya = (int)floorf(hf - 1.0f - ((b.w + 1.0f) * hf - 1.0f) * 0.5f) - 1;
-        int yb = (int)ceilf(hf - 1.0f - ((b.z + 1.0f) * hf - 1.0f) * 0.5f) + 1;
-        if (!(xb < 0 || yb < 0 || xa >= H || ya >= H)) {
-          xa = max(xa, 0); ya = max(ya, 0); xb = min(xb, H - 1); yb = min(yb, H - 1);
-          for (int it = 0; it < 3 && xa <= xb && pix_to_ndc(H - 1 - xa, H) > b.y; ++it) ++xa;
-          for (int it = 0; it < 3 && xa <= xb && pix_to_ndc(H - 1 - xb, H) < b.x; ++it) --xb;
-          for (int it = 0; it < 3 && ya <= yb && pix_to_ndc(H - 1 - ya, H) > b.w; ++it) ++ya;
-          for (int it = 0; it < 3 && ya <= yb && pix_to_ndc(H - 1 - yb, H) < b.z; ++it) --yb;
-          if (xa <= xb && ya <= yb) { w = xb - xa + 1; cnt = w * (yb - ya + 1); }
-        }
-      }
-    }
-    const int32_t* tn = tidx + (size_t)n * HW;
-    const TexGradN gn = tex_grad_of(tgrad, n, HW);
-    int cmax = 0;
-    int t[TEXG_FPW];
-    size_t pp[TEXG_FPW];
-#pragma unroll
-    for (int k = 0; k < TEXG_FPW; ++k) {                     // all texel-index loads first ...
-      const int kxa = __shfl(xa, k, 64), kya = __shfl(ya, k, 64), kw = __shfl(w, k, 64), kc = __shfl(cnt, k, 64);
-      const int kbase = (a * F + f0 + k * Q) * R2;           // first texel index of the face (< 2^31: host check)
-      cmax = max(cmax, kc);
-      t[k] = -1;
-      pp[k] = 0;
-      if (lane < kc) {
-        int qy, qx;
-        divmod_small(lane, kw, __builtin_amdgcn_rcpf((float)kw), qy, qx);
-        pp[k] = (size_t)(kya + qy) * H + (kxa + qx);
-        t[k] = tn[pp[k]] - kbase;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < TEXG_FPW; ++k) {                     // ... then the gradients of the pixels that belong to the face
-      if (t[k] >= 0 && t[k] < R2) {
-        // d rgb / d texel = wnum / (wnum + delta) = 1 in fp32 (wnum >= 0.5, delta = 1e-10)
-        float r, gg, bb;
-        gn.load(pp[k], r, gg, bb);
-        atomicAdd(&acc[k][3 * t[k] + 0], r);
-        atomicAdd(&acc[k][3 * t[k] + 1], gg);
-        atomicAdd(&acc[k][3 * t[k] + 2], bb);
-      }
-    }
-    if (cmax > 64) {   // boxes of more than 64 pixels (a third of the bird's): the rest face by face, 64 U pixels per round
-      for (int k = 0; k < TEXG_FPW; ++k) {
-        const int kxa = __shfl(xa, k, 64), kya = __shfl(ya, k, 64), kw = __shfl(w, k, 64), kc = __shfl(cnt, k, 64);
-        const int kbase = (a * F + f0 + k * Q) * R2;
-        const float rw = __builtin_amdgcn_rcpf((float)kw);
-        for (int i0 = 64 + lane; i0 < kc + lane; i0 += 64 * TEXG_U) {   // (i0 - lane is wave-uniform)
-          int tt[TEXG_U];
-          float cr[TEXG_U], cg[TEXG_U], cb[TEXG_U];
-#pragma unroll
-          for (int u = 0; u < TEXG_U; ++u) {
-            const int i = i0 + 64 * u;
-            tt[u] = -1; cr[u] = 0.f; cg[u] = 0.f; cb[u] = 0.f;
-            if (i < kc) {
-              int qy, qx;
-              divmod_small(i, kw, rw, qy, qx);
-              const size_t p = (size_t)(kya + qy) * H + (kxa + qx);
-              tt[u] = tn[p] - kbase;
-              gn.load(p, cr[u], cg[u], cb[u]);                              // unconditionally: one round trip per round
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < TEXG_U; ++u)
-            if (tt[u] >= 0 && tt[u] < R2) {
-              atomicAdd(&acc[k][3 * tt[u] + 0], cr[u]);
-              atomicAdd(&acc[k][3 * tt[u] + 1], cg[u]);
-              atomicAdd(&acc[k][3 * tt[u] + 2], cb[u]);
-            }
-        }
-      }
-    }
-  }
-  wave_lds_sync();
-#pragma unroll
-  for (int k = 0; k < TEXG_FPW; ++k) {
-    if (f0 + k * Q >= F) break;
-    float* o = grad_atlas + (size_t)(a * F + f0 + k * Q) * n3;
-    for (int i = lane; i < n3; i += 64) o[i] = acc[k][i];
-  }
-}
-
-// ------------------------------------------------------------------------------- fragments
-// acfm_rasterize_fragments: PyTorch3D's full rasterizer state per (pixel, slot) -- pix_to_face, zbuf, bary_coords,
-// dists -- over vertices already in NDC / view space (k_setup mode 2).  The K-nearest walk (k_raster_fwd, the very
-// instantiations the silhouette renders use, CLIP as asked) leaves the K packed ids of every pixel, empty blocks
-// included (fwd_fill_block*); k_frag_fwd then expands every slot from its face record with the walk's own expressions
-// (test_face_depth, clip_bary, bary_depth, test_face_dist), so zbuf is bit for bit the depth half of the walk's sort
-// key and every value is the oracle's (oracle_rasterize).  One thread per (pixel, slot), in memory order: the id
-// read and the zbuf / dists stores are contiguous across the wave, the 12-byte barycentric triples are regrouped in
-// LDS and leave as whole 16-byte pieces of one contiguous 3 KB run per workgroup.
-constexpr int FRAG_TPB = 256;
-template <bool CLIP>
-__global__ __launch_bounds__(FRAG_TPB) void k_frag_fwd(const FaceRec* __restrict__ rec, const int64_t* __restrict__ p2f,
-                                                       int H, int K, size_t total, float* __restrict__ zbuf,
-                                                       float* __restrict__ bary, float* __restrict__ dists) {
-  __shared__ float s_b[FRAG_TPB * 3];
-  const int tid = threadIdx.x;
-  const size_t i = (size_t)blockIdx.x * FRAG_TPB + tid;
-  float z = -1.0f, b0 = -1.0f, b1 = -1.0f, b2 = -1.0f, d = -1.0f;
-  if (i < total) {
-    const int64_t f = p2f[i];
-    if (f >= 0) {
-      const size_t p = i / (size_t)K;
-      const int xi = (int)(p % (size_t)H), yi = (int)((p / (size_t)H) % (size_t)H);
-      const float xf = pix_to_ndc(H - 1 - xi, H), yf = pix_to_ndc(H - 1 - yi, H);
-      const FaceRec& r = rec[f];
-      const float4 A = r.a, B = r.b, C = r.c;
-      Hit h;
-      bool inside = false;
-      test_face_depth<CLIP>(xf, yf, A, B, C.x, C.z, C.w, h, inside);
-      test_face_dist(xf, yf, A, B, 0.0f, inside, h);
-      z = h.pz + 0.0f;   // make_key's depth bits
-      b0 = h.c0; b1 = h.c1; b2 = h.c2; d = h.sd;
-    }
-    zbuf[i] = z;
-    dists[i] = d;
-  }
-  s_b[3 * tid] = b0; s_b[3 * tid + 1] = b1; s_b[3 * tid + 2] = b2;
-  __syncthreads();
-  // the workgroup's 3 x 256 floats are contiguous in `bary` (16-byte aligned: 3 KB per workgroup)
-  const size_t e0 = (size_t)blockIdx.x * FRAG_TPB * 3 + 4 * (size_t)tid, e_end = 3 * total;
-  if (tid < FRAG_TPB * 3 / 4) {
-    if (e0 + 4 <= e_end) {
-      *reinterpret_cast<float4*>(bary + e0) = make_float4(s_b[4 * tid], s_b[4 * tid + 1], s_b[4 * tid + 2], s_b[4 * tid + 3]);
-    } else {
-      for (int c = 0; c < 4; ++c)
-        if (e0 + c < e_end) bary[e0 + c] = s_b[4 * tid + c];
-    }
-  }
-}
-
-// acfm_rasterize_fragments_backward: grad_zbuf / grad_bary / grad_dists (each optional) -> d / d verts_ndc.
-// One thread per (pixel, slot) with a face, in memory order (FRAG_ITER x 256 consecutive slots per workgroup: a few
-// image rows, whose faces repeat from pixel to pixel).  The nine coordinate gradients of a (pixel, slot) go into an
-// LDS table of the workgroup's faces (open addressing on the packed id, LDS atomics); at the end every face of the
-// table is flushed with one global atomic per non-zero coordinate of its three vertices -- no per-lane global atomics
-// at scattered vertices.  A face that finds no table slot within FRAG_PROBES probes goes to memory directly (correct,
-// slower; not met at the sizes measured).  AccT = long long: deterministic mode, 2^-36 fixed point as k_sil_bwd.
-constexpr int FRAG_ITER = 8;
-constexpr int FRAG_PROBES = 32;
-// Accumulators.  Float mode: grad_verts [N,V,3] itself, float atomics (table of 512 faces in LDS).  Deterministic
-// mode (AcfmRasterTuning.flags bit 0): barycentric gradients scale like 1 / area -- near-degenerate faces reach 1e9
-// and more where blur_radius > 0 keeps pixels outside them -- which no single 64-bit fixed-point format covers
-// together with the 1e-6 resolution of small gradients.  Every contribution v is therefore split exactly into
-// v_hi = rint(v 2^4) 2^-4 and v_lo = v - v_hi, summed as two integers in units of 2^-4 and 2^-40: range |sum| < 2^59
-// (5.8e17), resolution 2^-40 (9.1e-13), integer atomics only (table of 256 faces in LDS, [N,V,3] x 2 in memory).
-// (FragFix / frag_split: acfm_common.h, shared with the shader backwards of acfm_shade.hip.)
-template <bool DET>
-__device__ __forceinline__ void frag_add(void* acc, size_t o, double v) {   // o: element [N,V,3] index (memory or LDS slot)
-  if constexpr (DET) {
-    const FragFix x = frag_split(v);
-    long long* a = reinterpret_cast<long long*>(acc) + 2 * o;
-    if (x.hi) atomicAdd(reinterpret_cast<unsigned long long*>(a), (unsigned long long)x.hi);
-    if (x.lo) atomicAdd(reinterpret_cast<unsigned long long*>(a + 1), (unsigned long long)x.lo);
-  } else {
-    atomicAdd(reinterpret_cast<float*>(acc) + o, (float)v);
-  }
-}
-// The per-(pixel, slot) gradient is formed in float64 from the float32 vertices and pixel centre: d w_i / d vertex is
-// a difference of terms of size 1 / area (and of z_i / area on the zbuf path) whose float32 rounding, not the result,
-// would set the error for small faces.
-template <bool DET, bool CLIP>
-__global__ __launch_bounds__(FRAG_TPB) void k_frag_bwd(const FaceRec* __restrict__ rec, const int4* __restrict__ vidx,
-                                                       const int64_t* __restrict__ p2f, const float* __restrict__ g_z,
-                                                       const float* __restrict__ g_b, const float* __restrict__ g_d,
-                                                       int V, int F, int H, int K, size_t total, void* acc) {
-  constexpr int TBL = DET ? 256 : 512, LOG_TBL = DET ? 8 : 9, W = DET ? 2 : 1;   // W: accumulator words per value
-  typedef typename std::conditional<DET, long long, float>::type AccT;
-  __shared__ int s_key[TBL];
-  __shared__ AccT s_acc[9 * W][TBL];
-  const int tid = threadIdx.x;
-  for (int s = tid; s < TBL; s += FRAG_TPB) {
-    s_key[s] = -1;
-#pragma unroll
-    for (int c = 0; c < 9 * W; ++c) s_acc[c][s] = (AccT)0;
-  }
-  __syncthreads();
-  const size_t base = (size_t)blockIdx.x * FRAG_TPB * FRAG_ITER;
-#pragma unroll 1
-  for (int it = 0; it < FRAG_ITER; ++it) {
-    const size_t i = base + (size_t)it * FRAG_TPB + tid;
-    if (i >= total) break;
-    const int64_t f = p2f[i];
-    if (f < 0) continue;
-    const size_t p = i / (size_t)K;
-    const int xi = (int)(p % (size_t)H), yi = (int)((p / (size_t)H) % (size_t)H);
-    const float pxf = pix_to_ndc(H - 1 - xi, H), pyf = pix_to_ndc(H - 1 - yi, H);
-    const FaceRec& r = rec[f];
-    const float4 A = r.a, B = r.b, C = r.c;
-    double g[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};   // (x, y, z) of v0, v1, v2
-    if (g_d) {
-      // dists: PointLineDistanceBackward of the arg-min edge, sign -1 inside (oracle_rasterize_backward_dists), in
-      // float32 like the forward's distances
-      const float gup = g_d[i];
-      if (gup != 0.0f) {
-        const float x0 = A.x, y0 = A.y, x1 = A.z, x2 = A.w, y1 = B.x, y2 = B.y;
-        const float denom = C.z, rden = C.w;
-        const float w0 = div_by(edge_fn(pxf, pyf, x1, y1, x2, y2), denom, rden);
-        const float w1 = div_by(edge_fn(pxf, pyf, x2, y2, x0, y0), denom, rden);
-        const float w2 = div_by(edge_fn(pxf, pyf, x0, y0, x1, y1), denom, rden);
-        const bool inside = (w0 > 0.0f) && (w1 > 0.0f) && (w2 > 0.0f);
-        const float gd = inside ? -gup : gup;
-        float t01, t02, t12;
-        const float d01 = point_line_dist(pxf, pyf, x0, y0, x1, y1, &t01);
-        const float d02 = point_line_dist(pxf, pyf, x0, y0, x2, y2, &t02);
-        const float d12 = point_line_dist(pxf, pyf, x1, y1, x2, y2, &t12);
-        float gax, gay, gbx, gby;
-        if (d01 <= d02 && d01 <= d12) {
-          point_line_dist_bwd(pxf, pyf, x0, y0, x1, y1, t01, gd, gax, gay, gbx, gby);
-          g[0] += gax; g[1] += gay; g[3] += gbx; g[4] += gby;
-        } else if (d02 <= d01 && d02 <= d12) {
-          point_line_dist_bwd(pxf, pyf, x0, y0, x2, y2, t02, gd, gax, gay, gbx, gby);
-          g[0] += gax; g[1] += gay; g[6] += gbx; g[7] += gby;
-        } else {
-          point_line_dist_bwd(pxf, pyf, x1, y1, x2, y2, t12, gd, gax, gay, gbx, gby);
-          g[3] += gax; g[4] += gay; g[6] += gbx; g[7] += gby;
-        }
-      }
-    }
-    if (g_z || g_b) {
-      const double px = pxf, py = pyf;
-      const double x0 = A.x, y0 = A.y, x1 = A.z, x2 = A.w, y1 = B.x, y2 = B.y, z0 = B.z, z1 = B.w, z2 = C.x;
-      auto edge = [](double qx, double qy, double ax, double ay, double bx, double by) {
-        return (qx - ax) * (by - ay) - (qy - ay) * (bx - ax);
-      };
-      const double D = edge(x2, y2, x0, y0, x1, y1) + 1e-8;   // area + kEps
-      const double w0 = edge(px, py, x1, y1, x2, y2) / D, w1 = edge(px, py, x2, y2, x0, y0) / D,
-                   w2 = edge(px, py, x0, y0, x1, y1) / D;
-      double b0 = w0, b1 = w1, b2 = w2, k0 = 0., k1 = 0., k2 = 0., sum = 0., s = 1.;
-      if (CLIP) {
-        // b_i = k_i / s, k_i = clamp(w_i, 0, 1), s = max(k0 + k1 + k2, 1e-5)
-        k0 = fmin(fmax(w0, 0.), 1.); k1 = fmin(fmax(w1, 0.), 1.); k2 = fmin(fmax(w2, 0.), 1.);
-        sum = k0 + k1 + k2; s = fmax(sum, 1e-5);
-        b0 = k0 / s; b1 = k1 / s; b2 = k2 / s;
-      }
-      double gb0 = 0., gb1 = 0., gb2 = 0.;
-      if (g_b) { gb0 = g_b[3 * i]; gb1 = g_b[3 * i + 1]; gb2 = g_b[3 * i + 2]; }
-      if (g_z) {
-        // zbuf = b0 z0 + b1 z1 + b2 z2: d / d z_i = b_i, and z_i into the gradient of b_i
-        const double gz = g_z[i];
-        g[2] += gz * b0; g[5] += gz * b1; g[8] += gz * b2;
-        gb0 += gz * z0; gb1 += gz * z1; gb2 += gz * z2;
-      }
-      double gw0 = gb0, gw1 = gb1, gw2 = gb2;
-      if (CLIP) {
-        const double dsum = sum >= 1e-5 ? (gb0 * k0 + gb1 * k1 + gb2 * k2) / (s * s) : 0.;
-        gw0 = (w0 >= 0. && w0 <= 1.) ? gb0 / s - dsum : 0.;
-        gw1 = (w1 >= 0. && w1 <= 1.) ? gb1 / s - dsum : 0.;
-        gw2 = (w2 >= 0. && w2 <= 1.) ? gb2 / s - dsum : 0.;
-      }
-      // w_i = e_i / D: dw_i = de_i / D - w_i dD / D.  edge(p, a, b) = (px - ax)(by - ay) - (py - ay)(bx - ax):
-      //   d/dax = py - by, d/day = bx - px, d/dbx = ay - py, d/dby = px - ax (and d/dpx = by - ay, d/dpy = ax - bx)
-      // e0 = edge(p, v1, v2), e1 = edge(p, v2, v0), e2 = edge(p, v0, v1), D - kEps = edge(v2, v0, v1)
-      const double gE0 = gw0 / D, gE1 = gw1 / D, gE2 = gw2 / D;
-      const double gD = -(gw0 * w0 + gw1 * w1 + gw2 * w2) / D;
-      g[3] += gE0 * (py - y2); g[4] += gE0 * (x2 - px); g[6] += gE0 * (y1 - py); g[7] += gE0 * (px - x1);
-      g[6] += gE1 * (py - y0); g[7] += gE1 * (x0 - px); g[0] += gE1 * (y2 - py); g[1] += gE1 * (px - x2);
-      g[0] += gE2 * (py - y1); g[1] += gE2 * (x1 - px); g[3] += gE2 * (y0 - py); g[4] += gE2 * (px - x0);
-      g[0] += gD * (y2 - y1); g[1] += gD * (x1 - x2); g[3] += gD * (y0 - y2); g[4] += gD * (x2 - x0);
-      g[6] += gD * (y1 - y0); g[7] += gD * (x0 - x1);
-    }
-    bool any = false;
-#pragma unroll
-    for (int c = 0; c < 9; ++c) any = any || g[c] != 0.;
-    if (!any) continue;
-    const int key = (int)f;   // packed ids fit an int (bad_dims: N F <= 2^31 - 1)
-    unsigned h = ((unsigned)key * 2654435761u) >> (32 - LOG_TBL);
-    int slot = -1;
-#pragma unroll 1
-    for (int probe = 0; probe < FRAG_PROBES; ++probe) {
-      const int old = atomicCAS(&s_key[h], -1, key);
-      if (old == -1 || old == key) { slot = (int)h; break; }
-      h = (h + 1) & (TBL - 1);
-    }
-    if (slot >= 0) {
-#pragma unroll
-      for (int c = 0; c < 9; ++c) {
-        if (g[c] == 0.) continue;
-        if constexpr (DET) {
-          const FragFix x = frag_split(g[c]);
-          if (x.hi) atomicAdd(reinterpret_cast<unsigned long long*>(&s_acc[2 * c][slot]), (unsigned long long)x.hi);
-          if (x.lo) atomicAdd(reinterpret_cast<unsigned long long*>(&s_acc[2 * c + 1][slot]), (unsigned long long)x.lo);
-        } else {
-          atomicAdd(&s_acc[c][slot], (float)g[c]);
-        }
-      }
-    } else {   // table full: straight to memory
-      const int4 vi = vidx[f];
-      const size_t row = (size_t)(f / F) * V;
-      const int vv[3] = {vi.x, vi.y, vi.z};
-#pragma unroll
-      for (int c = 0; c < 9; ++c)
-        if (g[c] != 0.) frag_add<DET>(acc, (row + vv[c / 3]) * 3 + c % 3, g[c]);
-    }
-  }
-  __syncthreads();
-  for (int s = tid; s < TBL; s += FRAG_TPB) {
-    const int f = s_key[s];
-    if (f < 0) continue;
-    const int4 vi = vidx[f];
-    const size_t row = (size_t)(f / F) * V;
-    const int vv[3] = {vi.x, vi.y, vi.z};
-#pragma unroll
-    for (int c = 0; c < 9; ++c) {
-      const size_t o = (row + vv[c / 3]) * 3 + c % 3;
-      if constexpr (DET) {
-        long long* a = reinterpret_cast<long long*>(acc) + 2 * o;
-        const long long hi = s_acc[2 * c][s], lo = s_acc[2 * c + 1][s];
-        if (hi) atomicAdd(reinterpret_cast<unsigned long long*>(a), (unsigned long long)hi);
-        if (lo) atomicAdd(reinterpret_cast<unsigned long long*>(a + 1), (unsigned long long)lo);
-      } else {
-        const float a = s_acc[c][s];
-        if (a != 0.f) atomicAdd(reinterpret_cast<float*>(acc) + o, a);
-      }
-    }
-  }
-}
-
-// deterministic mode: the (hi, lo) integer sums -> grad_verts [N,V,3]
-__global__ __launch_bounds__(TPB) void k_frag_fix_finish(const long long* __restrict__ fix, size_t n,
-                                                          float* __restrict__ grad_verts) {
-  const size_t j = (size_t)blockIdx.x * TPB + threadIdx.x;
-  if (j >= n) return;
-  grad_verts[j] = (float)((double)fix[2 * j] * 0.0625 + (double)fix[2 * j + 1] * (1.0 / 1099511627776.0));
-}
-
-// ------------------------------------------------------------------------------- profiling
-// One ring per process, shared by all devices and threads (a measurement aid, off by default): the
-// flag is atomic, the ring is guarded by a mutex held from prof_begin to prof_end of a launch.
-static std::atomic<bool> g_prof_on{false};
-static std::mutex g_prof_mu;
-static hipEvent_t g_ev[ACFM_PROF_RING][2];
-static int g_ev_id[ACFM_PROF_RING];
-static int g_ev_n = 0;
-static bool g_ev_made = false;
-static thread_local bool t_prof_open = false;
-
-void prof_begin(int id, hipStream_t st) {
-  if (!g_prof_on.load(std::memory_order_relaxed)) return;
-  g_prof_mu.lock();
-  if (!g_prof_on.load() || g_ev_n >= ACFM_PROF_RING) { g_prof_mu.unlock(); return; }
-  t_prof_open = true;
-  g_ev_id[g_ev_n] = id;
-  (void)hipEventRecord(g_ev[g_ev_n][0], st);
-}
-void prof_end(hipStream_t st) {
-  if (!t_prof_open) return;
-  (void)hipEventRecord(g_ev[g_ev_n][1], st);
-  g_ev_n++;
-  t_prof_open = false;
-  g_prof_mu.unlock();
-}
-
 // ------------------------------------------------------------------------------- host side
-static int launch_setup(const float* verts, const int64_t* faces, const float* cams, int N, int V,
-                        int F, int H, float offset_z, int mode, float blur, const RasterWs& ws,
-                        const Tune& tn, hipStream_t st, uint8_t* vis = nullptr, float* proj_xy = nullptr) {
-  const float margin = sqrtf(blur);
-  const int tiles = (H + CNT_TILE - 1) / CNT_TILE;
-  const int tt = tiles * tiles;                 // cost counters
-  const int blocks = (H + RBLK - 1) / RBLK;
-  const int ctiles = (H + CTILE - 1) / CTILE;
-  const size_t mwords = 2 * (((size_t)F + 63) / 64);
-  const size_t slice_words = (size_t)setup_slice_faces(F, ws.slices) / 32;
-  const size_t slice_mask_bytes = sizeof(unsigned) * (size_t)ctiles * ctiles * (slice_words < mwords ? slice_words : mwords);
-  const bool lds_mask = slice_mask_bytes <= (size_t)SETUP_LDS_MASK_BYTES;
-  const size_t lds = sizeof(float) * 3 * (size_t)V + (tt <= SETUP_LDS_TILES ? sizeof(int) * (size_t)tt : 0) +
-                     (lds_mask ? slice_mask_bytes : 0);
-  if (lds > 150 * 1024) return ACFM_E_BADARG;
-  if (!lds_mask && zero_async(ws.cmask, sizeof(unsigned) * (size_t)N * ctiles * ctiles * mwords, st)) return ACFM_E_LAUNCH;
-  // (counters in LDS: every slice of k_setup stores its own plane of ws.tile_part, nothing to zero)
-  if (tt > SETUP_LDS_TILES && zero_async(ws.tile_cnt, sizeof(int) * (size_t)N * tt, st)) return ACFM_E_LAUNCH;
-  ProfScope ps(ACFM_PROF_SETUP, st);
-  switch (ws.slices) {
-    case 4: hipLaunchKernelGGL(k_setup<4>, dim3(N, 4), dim3(TPB), lds, st, verts, faces, cams, V, F, H, offset_z, mode,
-                               margin, ws, vis, proj_xy); break;
-    case 8: hipLaunchKernelGGL(k_setup<8>, dim3(N, 8), dim3(TPB), lds, st, verts, faces, cams, V, F, H, offset_z, mode,
-                               margin, ws, vis, proj_xy); break;
-    default: hipLaunchKernelGGL(k_setup<16>, dim3(N, 16), dim3(TPB), lds, st, verts, faces, cams, V, F, H, offset_z, mode,
-                                margin, ws, vis, proj_xy); break;
-  }
-  if (ws.slices > 4)
-    hipLaunchKernelGGL(k_order<true>, dim3((N & 7) == 0 ? 8 : 1), dim3(1024), 0, st, ws, N, blocks * blocks, H, tn.split);
-  else
-    hipLaunchKernelGGL(k_order<false>, dim3((N & 7) == 0 ? 8 : 1), dim3(1024), 0, st, ws, N, blocks * blocks, H, tn.split);
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-static bool bad_dims(int N, int V, int F, int H) {
-  return N <= 0 || N > 65535 || V <= 0 || F <= 0 || F > ACFM_MAX_FACES || H <= 0 || H > 4096 ||
-         (size_t)N * F > 0x7fffffffull ||
-         (size_t)N * ((H + RBLK - 1) / RBLK) * ((H + RBLK - 1) / RBLK) > 0x7fffffffull;
-}
+// The launchers of acfm_raster.h: the only places these kernels are launched from.
+#ifdef ACFM_DIAG
+static unsigned long long* g_dbg = nullptr;   // acfm_debug_set_stamp_buffer
+#else
+static unsigned long long* const g_dbg = nullptr;
+#endif
+unsigned long long* stamp_buffer() { return g_dbg; }
 
 // workgroups of a raster launch: per XCD group ceil(entries / div) (+ 4 per split slot), see Sched
 static unsigned tile_grid(int N, int H, int div, int split_slots = 0) {
@@ -2755,12 +1489,52 @@ static int launch_sil_fwd(const RasterWs& ws, int N, int F, int H, float blur, f
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
 }
-
-// fragments (acfm_rasterize_fragments*): the walk of the forward, the backward launch
-static bool frag_k_ok(int K) {
-  return K == 1 || K == 2 || K == 4 || K == 8 || K == 10 || K == 20 || K == 32;
+int launch_sil_fwd(int K, const RasterWs& ws, int N, int F, int H, float blur, float sigma, const FwdOut& out,
+                   const Tune& tn, hipStream_t st) {
+  switch (K) {
+    case 20: return launch_sil_fwd<20>(ws, N, F, H, blur, sigma, out, tn, st);
+    case 10: return launch_sil_fwd<10>(ws, N, F, H, blur, sigma, out, tn, st);
+    case 8: return launch_sil_fwd<8>(ws, N, F, H, blur, sigma, out, tn, st);
+    case 4: return launch_sil_fwd<4>(ws, N, F, H, blur, sigma, out, tn, st);
+    case 2: return launch_sil_fwd<2>(ws, N, F, H, blur, sigma, out, tn, st);
+    case 32: return launch_sil_fwd<32>(ws, N, F, H, blur, sigma, out, tn, st);
+    default: return ACFM_E_BADARG;  // supported K: 2, 4, 8, 10, 20, 32
+  }
 }
 
+void launch_sil_bwd(const RasterWs& ws, const void* mask, const unsigned long long* kth, const BwdGrad& bg, int N,
+                    int V, int F, int H, float blur, float sigma, const Tune& tn, hipStream_t st) {
+  if (tn.deterministic)
+    hipLaunchKernelGGL(k_sil_bwd<long long>, dim3(tile_grid(N, H, tn.div[2], ws.split_slots)), dim3(RT), 0, st, ws,
+                       mask, kth, bg, N, V, F, H, blur, sigma);
+  else
+    hipLaunchKernelGGL(k_sil_bwd<float>, dim3(tile_grid(N, H, tn.div[2], ws.split_slots)), dim3(RT), 0, st, ws,
+                       mask, kth, bg, N, V, F, H, blur, sigma);
+}
+
+// the nearest-face walk (K = 1, blur 0): ids only (acfm_hard_raster), or the texture / vertex-colour render
+void launch_k1_fwd(bool tex, const RasterWs& ws, int N, int F, int H, float sigma, const FwdOut& out, const Tune& tn,
+                   hipStream_t st) {
+  if (tex)
+    hipLaunchKernelGGL((k_raster_fwd<1, true, true>), dim3(tile_grid(N, H, tn.div[1])), dim3(RT), 0, st, ws, N, F, H,
+                       0.f, sigma, out);
+  else
+    hipLaunchKernelGGL((k_raster_fwd<1, false, false>), dim3(tile_grid(N, H, tn.div[1])), dim3(RT), 0, st, ws, N, F,
+                       H, 0.f, sigma, out);
+}
+
+void launch_tex_cover(const RasterWs& ws, int N, int F, int H, float sigma, const FwdOut& out, const Tune& tn,
+                      hipStream_t st) {
+  // one wave per div entries of the order (measured at 64 frames @256^2, entries per wave 0.5 / 1 / 2 / 4 / 8:
+  // 47 / 35 / 31 / 43 / 45 us: fewer waves leave the stores of the empty blocks to too few issuers)
+  const size_t G = (N & 7) == 0 ? 8 : 1;
+  const size_t per = (size_t)((H + RBLK - 1) / RBLK) * ((H + RBLK - 1) / RBLK) * (N / G);
+  const size_t d = (size_t)(tn.div[1] < 1 ? 1 : tn.div[1]) * COVER_WPB;
+  hipLaunchKernelGGL((k_tex_cover<true>), dim3((unsigned)(G * ((per + d - 1) / d))), dim3(64 * COVER_WPB), 0, st, ws,
+                     N, F, H, sigma, out);
+}
+
+// fragments (acfm_rasterize_fragments, acfm_raster_frag.hip): the walk that leaves the K packed ids of every pixel
 template <int K, bool CLIP>
 static void launch_frag_walk(const RasterWs& ws, int N, int F, int H, float blur, const FwdOut& out, const Tune& tn,
                              hipStream_t st) {
@@ -2793,23 +1567,9 @@ static int frag_walk(const RasterWs& ws, int N, int F, int H, int K, float blur,
   }
   return ACFM_OK;
 }
-
-template <bool DET>
-static void launch_frag_bwd(bool clip, unsigned grid, const RasterWs& ws, const int64_t* p2f, const float* gz,
-                            const float* gb, const float* gd, int V, int F, int H, int K, size_t total, void* acc,
-                            hipStream_t st) {
-  if (clip)
-    hipLaunchKernelGGL((k_frag_bwd<DET, true>), dim3(grid), dim3(FRAG_TPB), 0, st, ws.rec, ws.vidx, p2f, gz, gb, gd, V,
-                       F, H, K, total, acc);
-  else
-    hipLaunchKernelGGL((k_frag_bwd<DET, false>), dim3(grid), dim3(FRAG_TPB), 0, st, ws.rec, ws.vidx, p2f, gz, gb, gd,
-                       V, F, H, K, total, acc);
-}
-
-// workspace of the fragments entry points: the raster workspace, then the deterministic backward's [N,V,3] x 2
-// integer accumulators
-static size_t frag_ws_bytes(const RasterWs& ws, int N, int V) {
-  return ws.bytes + align256(sizeof(long long) * 6 * (size_t)N * V);
+int frag_walk(bool clip, const RasterWs& ws, int N, int F, int H, int K, float blur, const FwdOut& out, const Tune& tn,
+              hipStream_t st) {
+  return clip ? frag_walk<true>(ws, N, F, H, K, blur, out, tn, st) : frag_walk<false>(ws, N, F, H, K, blur, out, tn, st);
 }
 
 }  // namespace acfm
@@ -2831,7 +1591,6 @@ int acfm_debug_counters(unsigned long long* host16, int reset) {
 }
 #endif
 #ifdef ACFM_DIAG
-static unsigned long long* g_dbg = nullptr;
 int acfm_debug_set_stamp_buffer(void* p) { g_dbg = (unsigned long long*)p; return 0; }
 int acfm_debug_occupancy(int which, int dyn_lds) {
   int n = -1;
@@ -2841,578 +1600,6 @@ int acfm_debug_occupancy(int which, int dyn_lds) {
   else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sil_bwd<float>, RT, 0);
   return e == hipSuccess ? n : -1;
 }
-#else
-static unsigned long long* const g_dbg = nullptr;
 #endif
-int acfm_version(void) { return 1001; }
-const char* acfm_arch(void) { return "gfx950"; }
-
-int acfm_stream_capture_id(void* stream, unsigned long long* id_host) {
-  if (!id_host) return ACFM_E_BADARG;
-  hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
-  unsigned long long id = 0;
-  if (hipStreamGetCaptureInfo((hipStream_t)stream, &status, &id) != hipSuccess) return ACFM_E_LAUNCH;
-  *id_host = status == hipStreamCaptureStatusActive ? (id ? id : ~0ull) : 0ull;
-  return ACFM_OK;
-}
-
-int acfm_prof_enable(int on) {
-  std::lock_guard<std::mutex> lk(g_prof_mu);
-  if (on && !g_ev_made) {
-    for (int i = 0; i < ACFM_PROF_RING; ++i)
-      if (hipEventCreate(&g_ev[i][0]) != hipSuccess || hipEventCreate(&g_ev[i][1]) != hipSuccess)
-        return ACFM_E_LAUNCH;
-    g_ev_made = true;
-  }
-  g_ev_n = 0;
-  g_prof_on = on != 0;
-  return ACFM_OK;
-}
-
-int acfm_prof_collect(float* ms_host, int* count_host, int n) {
-  if (!ms_host || !count_host || n < ACFM_PROF_NKERNELS) return ACFM_E_BADARG;
-  std::lock_guard<std::mutex> lk(g_prof_mu);
-  for (int i = 0; i < n; ++i) { ms_host[i] = 0.f; count_host[i] = 0; }
-  for (int i = 0; i < g_ev_n; ++i) {
-    if (hipEventSynchronize(g_ev[i][1]) != hipSuccess) return ACFM_E_LAUNCH;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, g_ev[i][0], g_ev[i][1]) != hipSuccess) return ACFM_E_LAUNCH;
-    ms_host[g_ev_id[i]] += ms;
-    count_host[g_ev_id[i]] += 1;
-  }
-  g_ev_n = 0;
-  return ACFM_OK;
-}
-
-const char* acfm_prof_name(int id) {
-  static const char* names[ACFM_PROF_NKERNELS] = {
-      "k_setup", "k_raster_fwd<K,soft>", "k_sil_bwd", "k_project_bwd", "k_raster_fwd<1,tex>",
-      "k_raster_fwd<1,hard>", "k_tex_bwd", "k_mask_losses", "k_mask_losses_bwd", "k_visible",
-      "k_bds_loss", "k_bds_loss_bwd", "k_project", "k_tex_mse", "k_tex_mse_bwd", "k_deform_apply",
-      "k_deform_bwd", "deform_solve", "deform_solve_bwd", "fragments_fwd", "k_frag_bwd", "", "", ""};
-  return (id >= 0 && id < ACFM_PROF_NKERNELS) ? names[id] : "";
-}
-
-size_t acfm_raster_workspace_bytes(int N, int V, int F, int H) {
-  if (N <= 0 || V <= 0 || F <= 0 || H <= 0) return 0;
-  return carve_ws(nullptr, N, V, F, H).bytes;
-}
-
-int acfm_project(const float* verts, const float* cams, int N, int V, float offset_z, float* proj,
-                 void* stream) {
-  if (!verts || !cams || !proj || N <= 0 || N > 65535 || V <= 0) return ACFM_E_BADARG;
-  ProfScope ps(ACFM_PROF_PROJECT, (hipStream_t)stream);
-  hipLaunchKernelGGL((k_project<false>), dim3((V + TPB - 1) / TPB, N), dim3(TPB), 0, (hipStream_t)stream, verts,
-                     cams, V, offset_z, proj);
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-int acfm_project_backward(const float* verts, const float* cams, const float* grad_proj, int N, int V,
-                          float* grad_verts, float* grad_cams, void* stream) {
-  if (!verts || !cams || !grad_proj || N <= 0 || V <= 0) return ACFM_E_BADARG;
-  ProfScope ps(ACFM_PROF_PROJ_BWD, (hipStream_t)stream);
-  hipLaunchKernelGGL((k_project_bwd<0>), dim3(N), dim3(TPB), 0, (hipStream_t)stream, verts, cams,
-                     const_cast<float*>(grad_proj), V, grad_verts, grad_cams);  // (read-only in this instantiation)
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-int acfm_project_xy(const float* verts, const float* cams, int N, int V, float offset_z, float* proj_xy,
-                    void* stream) {
-  if (!verts || !cams || !proj_xy || N <= 0 || N > 65535 || V <= 0) return ACFM_E_BADARG;
-  ProfScope ps(ACFM_PROF_PROJECT, (hipStream_t)stream);
-  hipLaunchKernelGGL((k_project<true>), dim3((V + TPB - 1) / TPB, N), dim3(TPB), 0, (hipStream_t)stream, verts,
-                     cams, V, offset_z, proj_xy);
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-int acfm_project_xy_backward(const float* verts, const float* cams, const float* grad_proj_xy, int N, int V,
-                             float* grad_verts, float* grad_cams, void* stream) {
-  if (!verts || !cams || !grad_proj_xy || N <= 0 || V <= 0) return ACFM_E_BADARG;
-  ProfScope ps(ACFM_PROF_PROJ_BWD, (hipStream_t)stream);
-  hipLaunchKernelGGL((k_project_bwd<2>), dim3(N), dim3(TPB), 0, (hipStream_t)stream, verts, cams,
-                     const_cast<float*>(grad_proj_xy), V, grad_verts, grad_cams);  // (read-only in this instantiation)
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-static int sil_forward_impl(const float* verts_world, const int64_t* faces, const float* cams, int N, int V,
-                            int F, int H, int K, int k_out, float blur_radius, float sigma, float offset_z,
-                            void* mask, void* pix_to_face, uint64_t* kth, uint8_t* vis, void* wsp,
-                            size_t ws_bytes, const AcfmRasterTuning* tuning, void* stream, bool fused,
-                            const void* gt, const void* edt, int ref_batch, float* losses,
-                            const AcfmSilExtras* ex = nullptr) {
-  float* pf_imgs = ex ? ex->tex_imgs : nullptr;
-  float* pf_sil = ex ? ex->tex_sil : nullptr;
-  int64_t* pf_p2f = ex ? ex->tex_pix_to_face : nullptr;
-  int32_t* pf_tidx = ex ? ex->tex_texel_idx : nullptr;
-  if (!verts_world || !faces || !cams || !mask || !pix_to_face || !wsp) return ACFM_E_BADARG;
-  if (fused && (!losses || ref_batch <= 0 || N % ref_batch != 0)) return ACFM_E_BADARG;
-  if (bad_dims(N, V, F, H) || K < 2 || K > ACFM_MAX_K || !(sigma > 0.f) || blur_radius < 0.f ||
-      (k_out != K && k_out != 1))
-    return ACFM_E_BADARG;
-  Tune tn;
-  if (!tune_from(tuning, tn)) return ACFM_E_BADARG;
-  if (tn.f16 && k_out != 1) return ACFM_E_BADARG;      // half storage goes with the int32 nearest-face plane
-  const RasterWs ws = carve_ws(wsp, N, V, F, H, tn.split);
-  if (ws.bytes > ws_bytes) return ACFM_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = launch_setup(verts_world, faces, cams, N, V, F, H, offset_z, 0, blur_radius, ws, tn, st, vis,
-                        ex ? ex->proj_xy : nullptr);
-  if (rc) return rc;
-  FwdOut out = {};
-  out.dbg = g_dbg;
-  out.h16 = tn.f16 ? 1 : 0;
-  out.mask = mask;
-  out.p2f = pix_to_face;
-  out.kout = k_out;
-  out.kth = reinterpret_cast<unsigned long long*>(kth);
-  out.vis = vis;
-  out.V = V;
-  out.sig_scale = 1.44269504088896341f / sigma;
-  out.lrb = 1;
-  if (tn.cover) out.cover_out = ws.cover;
-  if (pf_imgs || pf_sil || pf_p2f || pf_tidx) {   // all four or none; only with the cover plane (the texture render it prepares shades from it) and float storage
-    if (!pf_sil || !pf_p2f || !pf_tidx || !tn.cover || tn.f16) return ACFM_E_BADARG;
-    out.pf_imgs = pf_imgs; out.pf_sil = pf_sil; out.pf_p2f = pf_p2f; out.pf_tidx = pf_tidx;
-  }
-  if (fused) { out.lgt = gt; out.ledt = edt; out.lrb = ref_batch; out.lpart = ws.lpart; }
-  switch (K) {
-    case 20: rc = launch_sil_fwd<20>(ws, N, F, H, blur_radius, sigma, out, tn, st); break;
-    case 10: rc = launch_sil_fwd<10>(ws, N, F, H, blur_radius, sigma, out, tn, st); break;
-    case 8: rc = launch_sil_fwd<8>(ws, N, F, H, blur_radius, sigma, out, tn, st); break;
-    case 4: rc = launch_sil_fwd<4>(ws, N, F, H, blur_radius, sigma, out, tn, st); break;
-    case 2: rc = launch_sil_fwd<2>(ws, N, F, H, blur_radius, sigma, out, tn, st); break;
-    case 32: rc = launch_sil_fwd<32>(ws, N, F, H, blur_radius, sigma, out, tn, st); break;
-    default: return ACFM_E_BADARG;  // supported K: 2, 4, 8, 10, 20, 32
-  }
-  if (rc || !fused) return rc;
-  const int tiles = (H + RBLK - 1) / RBLK;
-  ProfScope ps(ACFM_PROF_MASK_LOSS, st);
-  const int fc = fin_chunks(N);
-  hipLaunchKernelGGL(k_sil_loss_finish1, dim3(fc, N), dim3(TPB), 0, st, ws.lpart, gt, tiles * tiles, H * H,
-                     ref_batch, out.h16, ws.lpart2);
-  hipLaunchKernelGGL(k_sil_loss_finish2, dim3((N + 63) / 64), dim3(64), 0, st, ws.lpart2, N, H * H, fc, losses);
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-int acfm_sil_forward(const float* verts_world, const int64_t* faces, const float* cams, int N, int V,
-                     int F, int H, int K, int k_out, float blur_radius, float sigma, float offset_z,
-                     void* mask, void* pix_to_face, uint64_t* kth, uint8_t* vis, void* wsp,
-                     size_t ws_bytes, const AcfmRasterTuning* tuning, void* stream) {
-  return sil_forward_impl(verts_world, faces, cams, N, V, F, H, K, k_out, blur_radius, sigma, offset_z, mask,
-                          pix_to_face, kth, vis, wsp, ws_bytes, tuning, stream, false, nullptr, nullptr, 1, nullptr);
-}
-
-int acfm_sil_forward_ex(const float* verts_world, const int64_t* faces, const float* cams, int N, int V,
-                        int F, int H, int K, int k_out, float blur_radius, float sigma, float offset_z,
-                        void* mask, void* pix_to_face, uint64_t* kth, uint8_t* vis, void* wsp,
-                        size_t ws_bytes, const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream) {
-  return sil_forward_impl(verts_world, faces, cams, N, V, F, H, K, k_out, blur_radius, sigma, offset_z, mask,
-                          pix_to_face, kth, vis, wsp, ws_bytes, tuning, stream, false, nullptr, nullptr, 1, nullptr, extras);
-}
-
-int acfm_sil_loss_forward_ex(const float* verts_world, const int64_t* faces, const float* cams, const void* gt,
-                             const void* edt, int ref_batch, int N, int V, int F, int H, int K, int k_out,
-                             float blur_radius, float sigma, float offset_z, void* mask, void* pix_to_face,
-                             uint64_t* kth, uint8_t* vis, float* losses, void* wsp, size_t ws_bytes,
-                             const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream) {
-  return sil_forward_impl(verts_world, faces, cams, N, V, F, H, K, k_out, blur_radius, sigma, offset_z, mask,
-                          pix_to_face, kth, vis, wsp, ws_bytes, tuning, stream, true, gt, edt, ref_batch, losses, extras);
-}
-
-int acfm_sil_loss_forward(const float* verts_world, const int64_t* faces, const float* cams, const void* gt,
-                          const void* edt, int ref_batch, int N, int V, int F, int H, int K, int k_out,
-                          float blur_radius, float sigma, float offset_z, void* mask, void* pix_to_face,
-                          uint64_t* kth, uint8_t* vis, float* losses, void* wsp, size_t ws_bytes,
-                          const AcfmRasterTuning* tuning, void* stream) {
-  return sil_forward_impl(verts_world, faces, cams, N, V, F, H, K, k_out, blur_radius, sigma, offset_z, mask,
-                          pix_to_face, kth, vis, wsp, ws_bytes, tuning, stream, true, gt, edt, ref_batch, losses);
-}
-
-static int sil_backward_impl(const float* verts_world, const int64_t* faces, const float* cams,
-                             const void* mask, const uint64_t* kth, BwdGrad bg, int N, int V,
-                             int F, int H, float blur_radius, float sigma, float offset_z, float* grad_verts,
-                             float* grad_cams, void* wsp, size_t ws_bytes, int ws_from_forward,
-                             const AcfmRasterTuning* tuning, void* stream, const float* gproj = nullptr) {
-  if (!verts_world || !faces || !cams || !mask || !kth || !wsp) return ACFM_E_BADARG;
-  if (!bg.grad_mask && (!bg.go || bg.lrb <= 0 || N % bg.lrb != 0)) return ACFM_E_BADARG;
-  if (bad_dims(N, V, F, H) || !(sigma > 0.f) || blur_radius < 0.f) return ACFM_E_BADARG;
-  Tune tn;
-  if (!tune_from(tuning, tn)) return ACFM_E_BADARG;
-  bg.h16 = tn.f16 ? 1 : 0;
-  const RasterWs ws = carve_ws(wsp, N, V, F, H, tn.split);   // (same tuning as the forward whose workspace this is)
-  if (ws.bytes > ws_bytes) return ACFM_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  if (!ws_from_forward) {
-    int rc = launch_setup(verts_world, faces, cams, N, V, F, H, offset_z, 0, blur_radius, ws, tn, st);
-    if (rc) return rc;
-  }
-  if (!grad_verts && !grad_cams) return ACFM_OK;   // nothing asked for
-  // ws.grad_ndc is zero here: k_setup cleared it, and every k_project_bwd<1> clears it again after reading
-  const size_t lds = 0;
-  {
-    ProfScope ps(ACFM_PROF_SIL_BWD, st);
-    if (tn.deterministic)
-      hipLaunchKernelGGL(k_sil_bwd<long long>, dim3(tile_grid(N, H, tn.div[2], ws.split_slots)), dim3(RT), lds, st, ws,
-                         mask, reinterpret_cast<const unsigned long long*>(kth), bg, N, V, F, H, blur_radius, sigma);
-    else
-      hipLaunchKernelGGL(k_sil_bwd<float>, dim3(tile_grid(N, H, tn.div[2], ws.split_slots)), dim3(RT), lds, st, ws,
-                         mask, reinterpret_cast<const unsigned long long*>(kth), bg, N, V, F, H, blur_radius, sigma);
-  }
-  ACFM_CHECK_LAUNCH();
-  if (grad_verts || grad_cams) {
-    ProfScope ps(ACFM_PROF_PROJ_BWD, st);
-    if (tn.deterministic)
-      hipLaunchKernelGGL((k_project_bwd<3>), dim3(N), dim3(TPB), 0, st, verts_world, cams,
-                         reinterpret_cast<float*>(ws.grad_fix), V, grad_verts, grad_cams, gproj);
-    else
-      hipLaunchKernelGGL((k_project_bwd<1>), dim3(N), dim3(TPB), 0, st, verts_world, cams,
-                         ws.grad_ndc, V, grad_verts, grad_cams, gproj);
-    ACFM_CHECK_LAUNCH();
-  }
-  return ACFM_OK;
-}
-
-int acfm_sil_backward(const float* verts_world, const int64_t* faces, const float* cams,
-                      const void* mask, const uint64_t* kth, const float* grad_mask, int N, int V,
-                      int F, int H, float blur_radius, float sigma, float offset_z, float* grad_verts,
-                      float* grad_cams, void* wsp, size_t ws_bytes, int ws_from_forward,
-                      const AcfmRasterTuning* tuning, void* stream) {
-  if (!grad_mask) return ACFM_E_BADARG;
-  BwdGrad bg = {};
-  bg.grad_mask = grad_mask;
-  bg.lrb = 1;
-  return sil_backward_impl(verts_world, faces, cams, mask, kth, bg, N, V, F, H, blur_radius, sigma, offset_z,
-                           grad_verts, grad_cams, wsp, ws_bytes, ws_from_forward, tuning, stream);
-}
-
-int acfm_sil_backward_ex(const float* verts_world, const int64_t* faces, const float* cams,
-                         const void* mask, const uint64_t* kth, const float* grad_mask, int N, int V,
-                         int F, int H, float blur_radius, float sigma, float offset_z, float* grad_verts,
-                         float* grad_cams, void* wsp, size_t ws_bytes, int ws_from_forward,
-                         const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream) {
-  if (!grad_mask) return ACFM_E_BADARG;
-  BwdGrad bg = {};
-  bg.grad_mask = grad_mask;
-  bg.lrb = 1;
-  return sil_backward_impl(verts_world, faces, cams, mask, kth, bg, N, V, F, H, blur_radius, sigma, offset_z,
-                           grad_verts, grad_cams, wsp, ws_bytes, ws_from_forward, tuning, stream,
-                           extras ? extras->grad_proj_xy : nullptr);
-}
-
-int acfm_sil_loss_backward_ex(const float* verts_world, const int64_t* faces, const float* cams, const void* mask,
-                              const uint64_t* kth, const void* gt, const void* edt, int ref_batch,
-                              const float* grad_losses, int N, int V, int F, int H, float blur_radius, float sigma,
-                              float offset_z, float* grad_verts, float* grad_cams, void* wsp, size_t ws_bytes,
-                              int ws_from_forward, const AcfmRasterTuning* tuning, const AcfmSilExtras* extras,
-                              void* stream) {
-  if (!grad_losses) return ACFM_E_BADARG;
-  BwdGrad bg = {};
-  bg.lgt = gt; bg.ledt = edt; bg.go = grad_losses; bg.lrb = ref_batch;
-  return sil_backward_impl(verts_world, faces, cams, mask, kth, bg, N, V, F, H, blur_radius, sigma, offset_z,
-                           grad_verts, grad_cams, wsp, ws_bytes, ws_from_forward, tuning, stream,
-                           extras ? extras->grad_proj_xy : nullptr);
-}
-
-int acfm_sil_loss_backward(const float* verts_world, const int64_t* faces, const float* cams, const void* mask,
-                           const uint64_t* kth, const void* gt, const void* edt, int ref_batch,
-                           const float* grad_losses, int N, int V, int F, int H, float blur_radius, float sigma,
-                           float offset_z, float* grad_verts, float* grad_cams, void* wsp, size_t ws_bytes,
-                           int ws_from_forward, const AcfmRasterTuning* tuning, void* stream) {
-  if (!grad_losses) return ACFM_E_BADARG;
-  BwdGrad bg = {};
-  bg.lgt = gt; bg.ledt = edt; bg.go = grad_losses; bg.lrb = ref_batch;
-  return sil_backward_impl(verts_world, faces, cams, mask, kth, bg, N, V, F, H, blur_radius, sigma, offset_z,
-                           grad_verts, grad_cams, wsp, ws_bytes, ws_from_forward, tuning, stream);
-}
-
-int acfm_hard_raster(const float* verts_proj, const int64_t* faces, int N, int V, int F, int H,
-                     int64_t* pix_to_face, uint8_t* vis, void* wsp, size_t ws_bytes,
-                     const AcfmRasterTuning* tuning, void* stream) {
-  if (!verts_proj || !faces || !pix_to_face || !wsp || bad_dims(N, V, F, H)) return ACFM_E_BADARG;
-  Tune tn;
-  if (!tune_from(tuning, tn) || tn.f16) return ACFM_E_BADARG;
-  const RasterWs ws = carve_ws(wsp, N, V, F, H, tn.split);
-  if (ws.bytes > ws_bytes) return ACFM_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = launch_setup(verts_proj, faces, nullptr, N, V, F, H, 0.f, 1, 0.f, ws, tn, st, vis);
-  if (rc) return rc;
-  FwdOut out = {};
-  out.dbg = g_dbg;
-  out.p2f = pix_to_face;
-  out.vis = vis;
-  out.V = V;
-  ProfScope ps(ACFM_PROF_HARD_FWD, st);
-  hipLaunchKernelGGL((k_raster_fwd<1, false, false>), dim3(tile_grid(N, H, tn.div[1])), dim3(RT), 0, st, ws, N, F,
-                     H, 0.f, 1e-4f, out);
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-// ---- fragments (PyTorch3D rasterize_meshes / RasterizeMeshesBackward over NDC vertices)
-size_t acfm_rasterize_fragments_workspace_bytes(int N, int V, int F, int H) {
-  if (N <= 0 || V <= 0 || F <= 0 || H <= 0) return 0;
-  return frag_ws_bytes(carve_ws(nullptr, N, V, F, H), N, V);
-}
-
-int acfm_rasterize_fragments(const float* verts_ndc, const int64_t* faces, int N, int V, int F, int H, int K,
-                             float blur_radius, int clip_bary, int64_t* pix_to_face, float* zbuf, float* bary,
-                             float* dists, void* wsp, size_t ws_bytes, const AcfmRasterTuning* tuning, void* stream) {
-  if (!verts_ndc || !faces || !pix_to_face || !zbuf || !bary || !dists || !wsp) return ACFM_E_BADARG;
-  if (bad_dims(N, V, F, H) || !frag_k_ok(K) || !(blur_radius >= 0.f)) return ACFM_E_BADARG;
-  if ((size_t)N * H * H * K > ((size_t)1 << 40)) return ACFM_E_BADARG;
-  if (((uintptr_t)bary & 15) != 0) return ACFM_E_BADARG;
-  Tune tn;
-  if (!tune_from(tuning, tn) || tn.f16) return ACFM_E_BADARG;   // float outputs only
-  const RasterWs ws = carve_ws(wsp, N, V, F, H, tn.split);
-  if (frag_ws_bytes(ws, N, V) > ws_bytes) return ACFM_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = launch_setup(verts_ndc, faces, nullptr, N, V, F, H, 0.f, 2, blur_radius, ws, tn, st);
-  if (rc) return rc;
-  FwdOut out = {};
-  out.dbg = g_dbg;
-  out.p2f = pix_to_face;
-  out.V = V;
-  out.lrb = 1;
-  {
-    ProfScope ps(ACFM_PROF_FRAG_FWD, st);
-    rc = clip_bary ? frag_walk<true>(ws, N, F, H, K, blur_radius, out, tn, st)
-                   : frag_walk<false>(ws, N, F, H, K, blur_radius, out, tn, st);
-    if (rc) return rc;
-    const size_t total = (size_t)N * H * H * K;
-    const unsigned grid = (unsigned)((total + FRAG_TPB - 1) / FRAG_TPB);
-    if (clip_bary)
-      hipLaunchKernelGGL(k_frag_fwd<true>, dim3(grid), dim3(FRAG_TPB), 0, st, ws.rec, pix_to_face, H, K, total, zbuf,
-                         bary, dists);
-    else
-      hipLaunchKernelGGL(k_frag_fwd<false>, dim3(grid), dim3(FRAG_TPB), 0, st, ws.rec, pix_to_face, H, K, total, zbuf,
-                         bary, dists);
-  }
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-int acfm_rasterize_fragments_backward(const float* verts_ndc, const int64_t* faces, const int64_t* pix_to_face,
-                                      const float* grad_zbuf, const float* grad_bary, const float* grad_dists, int N,
-                                      int V, int F, int H, int K, float blur_radius, int clip_bary, float* grad_verts,
-                                      void* wsp, size_t ws_bytes, int ws_from_forward,
-                                      const AcfmRasterTuning* tuning, void* stream) {
-  if (!verts_ndc || !faces || !pix_to_face || !grad_verts || !wsp) return ACFM_E_BADARG;
-  if (bad_dims(N, V, F, H) || !frag_k_ok(K) || !(blur_radius >= 0.f)) return ACFM_E_BADARG;
-  if ((size_t)N * H * H * K > ((size_t)1 << 40)) return ACFM_E_BADARG;
-  Tune tn;
-  if (!tune_from(tuning, tn) || tn.f16) return ACFM_E_BADARG;
-  const RasterWs ws = carve_ws(wsp, N, V, F, H, tn.split);
-  if (frag_ws_bytes(ws, N, V) > ws_bytes) return ACFM_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  if (!ws_from_forward) {
-    int rc = launch_setup(verts_ndc, faces, nullptr, N, V, F, H, 0.f, 2, blur_radius, ws, tn, st);
-    if (rc) return rc;
-  }
-  const size_t n3 = (size_t)N * V * 3;
-  if (!grad_zbuf && !grad_bary && !grad_dists) return zero_async(grad_verts, sizeof(float) * n3, st);
-  const size_t total = (size_t)N * H * H * K;
-  const unsigned grid = (unsigned)((total + (size_t)FRAG_TPB * FRAG_ITER - 1) / ((size_t)FRAG_TPB * FRAG_ITER));
-  {
-    ProfScope ps(ACFM_PROF_FRAG_BWD, st);
-    if (tn.deterministic) {
-      long long* fix = reinterpret_cast<long long*>((char*)wsp + ws.bytes);
-      if (zero_async(fix, sizeof(long long) * 2 * n3, st)) return ACFM_E_LAUNCH;
-      launch_frag_bwd<true>(clip_bary != 0, grid, ws, pix_to_face, grad_zbuf, grad_bary, grad_dists, V, F, H, K, total,
-                            fix, st);
-      hipLaunchKernelGGL(k_frag_fix_finish, dim3((unsigned)((n3 + TPB - 1) / TPB)), dim3(TPB), 0, st, fix, n3,
-                         grad_verts);
-    } else {
-      if (zero_async(grad_verts, sizeof(float) * n3, st)) return ACFM_E_LAUNCH;
-      launch_frag_bwd<false>(clip_bary != 0, grid, ws, pix_to_face, grad_zbuf, grad_bary, grad_dists, V, F, H, K,
-                             total, grad_verts, st);
-    }
-  }
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-static int tex_forward_impl(const float* verts_world, const int64_t* faces, const float* cams,
-                            const void* atlas, int N, int V, int F, int H, int R, float sigma, float gamma,
-                            float offset_z, void* imgs, void* sil, void* pix_to_face, int32_t* texel_idx,
-                            void* wsp, size_t ws_bytes, int ws_ready, float ws_blur, int atlas_batch,
-                            const AcfmRasterTuning* tuning, void* stream, const void* ref_img,
-                            const void* ref_mask, int ref_batch, float* loss) {
-  if (!verts_world || !faces || !cams || !atlas || !imgs || !sil || !pix_to_face || !texel_idx || !wsp)
-    return ACFM_E_BADARG;
-  if (bad_dims(N, V, F, H) || R <= 0 || R > 256 || !(sigma > 0.f) || !(gamma > 0.f)) return ACFM_E_BADARG;
-  if (atlas_batch <= 0 || N % atlas_batch != 0) return ACFM_E_BADARG;
-  if ((size_t)atlas_batch * F * R * R > 0x7fffffffull) return ACFM_E_BADARG;  // texel_idx is int32
-  Tune tn;
-  if (!tune_from(tuning, tn)) return ACFM_E_BADARG;
-  const RasterWs ws = carve_ws(wsp, N, V, F, H, tn.split);
-  if (ws.bytes > ws_bytes) return ACFM_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  if (ws_ready && !(ws_blur >= 0.f)) return ACFM_E_BADARG;
-  if (!ws_ready) {
-    int rc = launch_setup(verts_world, faces, cams, N, V, F, H, offset_z, 0, 0.f, ws, tn, st);
-    if (rc) return rc;
-  }
-  FwdOut out = {};
-  out.dbg = g_dbg;
-  out.p2f = pix_to_face;
-  out.atlas = atlas; out.imgs = imgs; out.sil = sil; out.tidx = texel_idx; out.R = R; out.gamma = gamma;
-  out.atlas_n = atlas_batch;
-  out.h16 = tn.f16 ? 1 : 0;
-  out.box_shrink = ws_ready ? sqrtf(ws_blur) * (1.0f - 1e-5f) : 0.f;
-  out.lrb = 1;
-  if (ws_ready < 0 || ws_ready > 3) return ACFM_E_BADARG;
-  if (ws_ready >= 2) {
-    if (!tn.cover) return ACFM_E_BADARG;   // the tuning of the render that filled the workspace says whether the plane is there
-    out.cover_in = ws.cover;
-    if (ws_ready == 3) {                   // ... and that render (acfm_sil_forward_prefill) stored the empty blocks' constants
-      if (tn.f16) return ACFM_E_BADARG;
-      out.prefilled = 1;
-    }
-  }
-  if (loss) {
-    if (!ref_img || !ref_mask || ref_batch <= 0 || N % ref_batch != 0) return ACFM_E_BADARG;
-    out.timg = ref_img; out.tmask = ref_mask; out.lrb = ref_batch; out.lpart = ws.lpart;
-  }
-  {
-    ProfScope ps(ACFM_PROF_TEX_FWD, st);
-    if (out.cover_in) {
-      // one wave per div entries of the order (measured at 64 frames @256^2, entries per wave 0.5 / 1 / 2 / 4 / 8:
-      // 47 / 35 / 31 / 43 / 45 us: fewer waves leave the stores of the empty blocks to too few issuers)
-      const size_t G = (N & 7) == 0 ? 8 : 1;
-      const size_t per = (size_t)((H + RBLK - 1) / RBLK) * ((H + RBLK - 1) / RBLK) * (N / G);
-      const size_t d = (size_t)(tn.div[1] < 1 ? 1 : tn.div[1]) * COVER_WPB;
-      hipLaunchKernelGGL((k_tex_cover<true>), dim3((unsigned)(G * ((per + d - 1) / d))), dim3(64 * COVER_WPB), 0, st, ws,
-                         N, F, H, sigma, out);
-    } else {
-      hipLaunchKernelGGL((k_raster_fwd<1, true, true>), dim3(tile_grid(N, H, tn.div[1])), dim3(RT), 0, st, ws, N, F, H,
-                         0.f, sigma, out);
-    }
-    ACFM_CHECK_LAUNCH();
-  }
-  if (loss) {
-    const int tiles = (H + RBLK - 1) / RBLK;
-    ProfScope ps(ACFM_PROF_TEX_MSE, st);
-    const int fc = fin_chunks(N);
-    hipLaunchKernelGGL(k_tex_loss_finish1, dim3(fc, N), dim3(TPB), 0, st, ws.lpart, ref_img, ref_mask,
-                       tiles * tiles, H * H, ref_batch, out.h16, ws.lpart2);
-    hipLaunchKernelGGL(k_tex_loss_finish2, dim3((N + 63) / 64), dim3(64), 0, st, ws.lpart2, N, H * H, fc, loss);
-    ACFM_CHECK_LAUNCH();
-  }
-  return ACFM_OK;
-}
-
-int acfm_tex_forward(const float* verts_world, const int64_t* faces, const float* cams,
-                     const void* atlas, int N, int V, int F, int H, int R, float sigma, float gamma,
-                     float offset_z, void* imgs, void* sil, void* pix_to_face, int32_t* texel_idx,
-                     void* wsp, size_t ws_bytes, int ws_ready, float ws_blur, int atlas_batch,
-                     const AcfmRasterTuning* tuning, void* stream) {
-  return tex_forward_impl(verts_world, faces, cams, atlas, N, V, F, H, R, sigma, gamma, offset_z, imgs, sil,
-                          pix_to_face, texel_idx, wsp, ws_bytes, ws_ready, ws_blur, atlas_batch, tuning, stream,
-                          nullptr, nullptr, 1, nullptr);
-}
-
-int acfm_tex_mse_forward(const float* verts_world, const int64_t* faces, const float* cams, const void* atlas,
-                         const void* ref_img, const void* ref_mask, int ref_batch, int N, int V, int F, int H, int R,
-                         float sigma, float gamma, float offset_z, void* imgs, void* sil, void* pix_to_face,
-                         int32_t* texel_idx, float* loss, void* wsp, size_t ws_bytes, int ws_ready, float ws_blur,
-                         int atlas_batch, const AcfmRasterTuning* tuning, void* stream) {
-  if (!loss) return ACFM_E_BADARG;
-  return tex_forward_impl(verts_world, faces, cams, atlas, N, V, F, H, R, sigma, gamma, offset_z, imgs, sil,
-                          pix_to_face, texel_idx, wsp, ws_bytes, ws_ready, ws_blur, atlas_batch, tuning, stream,
-                          ref_img, ref_mask, ref_batch, loss);
-}
-
-int acfm_vertex_color_forward(const float* verts_world, const int64_t* faces, const float* cams,
-                              const float* verts_rgb, int N, int V, int F, int H, float sigma, float gamma,
-                              float offset_z, float* imgs, float* sil, int64_t* pix_to_face, void* wsp,
-                              size_t ws_bytes, int ws_ready, float ws_blur, const AcfmRasterTuning* tuning,
-                              void* stream) {
-  if (!verts_world || !faces || !cams || !verts_rgb || !imgs || !sil || !pix_to_face || !wsp) return ACFM_E_BADARG;
-  if (bad_dims(N, V, F, H) || !(sigma > 0.f) || !(gamma > 0.f)) return ACFM_E_BADARG;
-  Tune tn;
-  if (!tune_from(tuning, tn) || tn.f16) return ACFM_E_BADARG;
-  const RasterWs ws = carve_ws(wsp, N, V, F, H, tn.split);
-  if (ws.bytes + sizeof(int32_t) * (size_t)N * H * H > ws_bytes) return ACFM_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  if (ws_ready && !(ws_blur >= 0.f)) return ACFM_E_BADARG;
-  if (!ws_ready) {
-    int rc = launch_setup(verts_world, faces, cams, N, V, F, H, offset_z, 0, 0.f, ws, tn, st);
-    if (rc) return rc;
-  }
-  FwdOut out = {};
-  out.dbg = g_dbg;
-  out.p2f = pix_to_face;
-  out.vrgb = verts_rgb; out.V = V; out.atlas_n = N;
-  out.box_shrink = ws_ready ? sqrtf(ws_blur) * (1.0f - 1e-5f) : 0.f;
-  out.imgs = imgs; out.sil = sil; out.tidx = (int32_t*)((char*)wsp + ws.bytes); out.R = 1; out.gamma = gamma;
-  out.atlas = verts_rgb;  // never dereferenced when vrgb is set
-  ProfScope ps(ACFM_PROF_TEX_FWD, st);
-  hipLaunchKernelGGL((k_raster_fwd<1, true, true>), dim3(tile_grid(N, H, tn.div[1])), dim3(RT), 0, st, ws, N, F, H,
-                     0.f, sigma, out);
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-int acfm_tex_backward(const float* grad_imgs, const int32_t* texel_idx, int N, int F, int H, int R,
-                      int atlas_batch, float* grad_atlas, void* stream) {
-  if (!grad_imgs || !texel_idx || !grad_atlas || N <= 0 || F <= 0 || H <= 0 || R <= 0 || atlas_batch <= 0 ||
-      N % atlas_batch != 0)
-    return ACFM_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t total = (size_t)N * H * H;
-  if (zero_async(grad_atlas, sizeof(float) * 3 * (size_t)atlas_batch * F * R * R, st) != ACFM_OK)
-    return ACFM_E_LAUNCH;
-  ProfScope ps(ACFM_PROF_TEX_BWD, st);
-  hipLaunchKernelGGL(k_tex_bwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, grad_imgs,
-                     texel_idx, (size_t)H * H, total, grad_atlas);
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-static int tex_backward_faces_impl(const TexGrad& tgrad, const int32_t* texel_idx, const void* wsp, size_t ws_bytes,
-                                   float ws_blur, int N, int V, int F, int H, int R, int atlas_batch,
-                                   float* grad_atlas, void* stream) {
-  if (!texel_idx || !grad_atlas || !wsp) return ACFM_E_BADARG;
-  if (bad_dims(N, V, F, H) || R <= 0 || R > TEXG_MAX_R || atlas_batch <= 0 || N % atlas_batch != 0 || !(ws_blur >= 0.f))
-    return ACFM_E_BADARG;
-  if ((size_t)atlas_batch * F * R * R > 0x7fffffffull) return ACFM_E_BADARG;
-  const RasterWs ws = carve_ws(const_cast<void*>(wsp), N, V, F, H);
-  if (ws.bytes > ws_bytes) return ACFM_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t waves = (size_t)atlas_batch * ((F + TEXG_FPW - 1) / TEXG_FPW);
-  ProfScope ps(ACFM_PROF_TEX_BWD, st);
-  hipLaunchKernelGGL(k_tex_bwd_faces, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, ws, tgrad, texel_idx,
-                     N, F, H, R, atlas_batch, ws_blur > 0.f ? sqrtf(ws_blur) * (1.0f - 1e-5f) : 0.f, grad_atlas);
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-int acfm_tex_backward_faces(const float* grad_imgs, const int32_t* texel_idx, const void* wsp, size_t ws_bytes,
-                            float ws_blur, int N, int V, int F, int H, int R, int atlas_batch, float* grad_atlas,
-                            void* stream) {
-  if (!grad_imgs) return ACFM_E_BADARG;
-  TexGrad tg = {};
-  tg.grad_imgs = grad_imgs;
-  tg.rb = 1;
-  return tex_backward_faces_impl(tg, texel_idx, wsp, ws_bytes, ws_blur, N, V, F, H, R, atlas_batch, grad_atlas, stream);
-}
-
-int acfm_tex_mse_backward_faces(const void* imgs, const void* ref_img, const void* ref_mask, int ref_batch,
-                                const float* grad_loss, const int32_t* texel_idx, const void* wsp, size_t ws_bytes,
-                                float ws_blur, int N, int V, int F, int H, int R, int atlas_batch, float* grad_atlas,
-                                const AcfmRasterTuning* tuning, void* stream) {
-  if (!imgs || !ref_img || !ref_mask || !grad_loss || ref_batch <= 0 || N <= 0 || N % ref_batch != 0) return ACFM_E_BADARG;
-  Tune tn;
-  if (!tune_from(tuning, tn)) return ACFM_E_BADARG;
-  TexGrad tg = {};
-  tg.h16 = tn.f16 ? 1 : 0;
-  tg.imgs = imgs; tg.timg = ref_img; tg.tmask = ref_mask; tg.go = grad_loss; tg.rb = ref_batch;
-  return tex_backward_faces_impl(tg, texel_idx, wsp, ws_bytes, ws_blur, N, V, F, H, R, atlas_batch, grad_atlas, stream);
-}
 
 }  // extern "C"
