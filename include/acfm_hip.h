@@ -222,6 +222,12 @@ size_t acfm_deform_solve_info_offset(int V);
  * Scratch of one render call of N meshes with V verts and F faces each at H x H pixels
  * (face records, NDC verts, per-mesh boxes, tile schedule, gradient scratch). */
 size_t acfm_raster_workspace_bytes(int N, int V, int F, int H);
+/* Vertices per mesh: the face setup of every render entry point (sil / sil_loss / tex / vertex_color / hard_raster /
+ * rasterize_fragments) keeps a mesh's projected vertices in dynamic LDS, 12 B each, next to its tile counters (4 B per
+ * 8x8-pixel block while H <= 512) and, while they fit in 64 KB, its face slice's coarse masks (4 B x ceil(H/16)^2 x
+ * slice faces / 32, a slice = F / 4, 8 or 16 faces rounded up to 64), and launches with at most 150 KB of it (the CU
+ * has 160 KB; launches past 64 KB need no opt-in on this runtime and are exercised by the tests).  Beyond that the
+ * call returns ACFM_E_BADARG.  Bird template (F = 1280), two meshes, H = 64: 12 V + 512 <= 153,600, V <= 12,757. */
 
 /* Per-call launch tuning of the raster entry points (pure speed: results never depend on it, `flags` apart).
  * NULL = the defaults.  There is no process-global tuning state in the library.
@@ -588,7 +594,9 @@ int acfm_visible_vertices(const int64_t* pix_to_face, const int64_t* faces, int 
                           int HW, int K, uint8_t* vis, void* stream);
 /* loss_utils.bds_loss (:204-237) given vis: for each boundary point the squared distance to
  * the nearest visible projected vertex (1000 where none), times the point's valid flag,
- * summed per mesh.  verts_xy [N,V,2], bds [ref_batch,P,3] -> loss [N], argmin [N,P] i32 (saved). */
+ * summed per mesh.  verts_xy [N,V,2], bds [ref_batch,P,3] -> loss [N], argmin [N,P] i32 (saved).
+ * The forward keeps 12 B per vertex in dynamic LDS, the backward 8 B, at most 150 KB: V <= 12,800 forward (so the
+ * backward's V <= 19,200 is never the limit); a larger V returns ACFM_E_BADARG. */
 int acfm_bds_loss(const float* verts_xy, const float* bds, const uint8_t* vis, int N, int V, int P,
                   int ref_batch, float* loss, int32_t* argmin, void* stream);
 int acfm_bds_loss_ws(const float* verts_xy, const float* bds, const uint8_t* vis, int N, int V, int P,
@@ -609,7 +617,9 @@ int acfm_cot_laplacian(const float* verts, const int64_t* faces, int V, int F, f
  *   vweight [P] = 1 / (verts of the vertex's mesh); the caller divides the sum by the mesh count.
  *   verts_per_mesh / faces_per_mesh > 0 (method 0): the packed arrays are equal-sized meshes one after the
  *   other (mesh m = vertices [m vpm, (m+1) vpm), faces [m fpm, (m+1) fpm)): one workgroup per mesh accumulates
- *   in LDS, one launch each way; 0 = unknown layout (global atomics).
+ *   in LDS, one launch each way; 0 = unknown layout (global atomics).  16 B of dynamic LDS per vertex, at most
+ *   150 KB: verts_per_mesh <= 9,600.  Larger meshes, and hints that do not describe the arrays (verts_per_mesh not
+ *   dividing P, P / verts_per_mesh != F / faces_per_mesh), take the global-atomic kernels: same result, no error.
  *   loss: 1 float (device); state: acfm_laplacian_smoothing_state_floats(P, F) floats kept for
  *   the backward, which takes the upstream gradient as a DEVICE scalar. */
 size_t acfm_laplacian_smoothing_state_floats(int P, int F);
@@ -627,7 +637,9 @@ int acfm_edge_rigidity_backward(const float* verts, const int64_t* edges, const 
                                 const int64_t* edges_t, int E, int P, int Pt, int verts_per_mesh,
                                 const float* grad_loss, float* grad_verts, float* grad_verts_t, void* stream);
 /* verts_per_mesh > 0: equal-sized meshes and `edges` sorted by its first vertex (Meshes.edges_packed()):
- * one workgroup per mesh accumulates in LDS (used when only grad_verts is asked for); 0: unknown layout. */
+ * one workgroup per mesh accumulates in LDS (used when only grad_verts is asked for); 0: unknown layout.
+ * 12 B of dynamic LDS per vertex, at most 150 KB: verts_per_mesh <= 12,800; larger meshes, and a verts_per_mesh that
+ * does not divide P, take the global-atomic kernel: same result, no error. */
 
 /* ---- on-device input preparation ----------------------------------------
  * replaces the per-batch CPU work of ShapeTrainer.set_input (multiframe/main.py:365-377) and

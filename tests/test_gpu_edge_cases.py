@@ -14,7 +14,7 @@ def _dev():
     return torch.device("cuda:0")
 
 
-def _check_sil(verts, f, cams, H, K=20, check_bwd=True, seed=0):
+def _check_sil(verts, f, cams, H, K=20, check_bwd=True, seed=0, zero_rows=None):
     from acfm_video_3d_reconstruction_amd import ops
     d = _dev()
     n = verts.shape[0]
@@ -35,6 +35,8 @@ def _check_sil(verts, f, cams, H, K=20, check_bwd=True, seed=0):
         for got, want in ((tv.grad.cpu().numpy(), gv), (tc.grad.cpu().numpy(), gc)):
             rel = np.linalg.norm(got.astype(np.float64) - want) / max(np.linalg.norm(want.astype(np.float64)), 1e-30)
             assert rel < 1e-5, rel
+        if zero_rows is not None:                         # vertices of no face: exactly no gradient
+            assert not tv.grad[:, zero_rows].cpu().numpy().any()
     return ref_p2f
 
 
@@ -292,3 +294,32 @@ def test_face_setup_slices_per_mesh(meshes, n):
     cams = make_cams(n, rng, extent=float(np.abs(v).max()))
     cams[::3, 1:3] += 0.4                       # some meshes partly outside
     _check_sil(verts, f, cams, 40, seed=n)
+
+
+# k_setup keeps the projected vertices in dynamic LDS, 12 B each, next to its tile counters and its slice of the coarse
+# face masks, and accepts up to 150 KB in all.  For the bird (F = 1280) at H = 64 with 2 meshes: 16 face slices per mesh
+# (fewer than 32 meshes, 80 faces per slice >= 64), 8 x 8 blocks of 8 pixels -> 64 counters = 256 B; 4 x 4 coarse tiles
+# of 16 pixels, a slice of ceil(80 / 64) * 64 = 128 faces = 4 mask words per tile -> 16 * 4 * 4 B = 256 B.  So
+# 12 V + 512 <= 153,600: V <= 12,757 (153,596 B); V = 12,758 needs 153,608 B and is refused.  V = 5600: 67,712 B, past
+# 64 KB.
+SETUP_LDS_MAX_V = (150 * 1024 - 256 - 256) // 12
+
+
+@pytest.mark.parametrize("V", [5600, SETUP_LDS_MAX_V, SETUP_LDS_MAX_V + 1])
+def test_vertex_counts_past_64_kb_of_setup_lds(meshes, V):
+    """The bird's 1280 faces with unreferenced vertices appended up to V: pix_to_face, mask and gradients at the bars
+    of every other case, exactly zero gradient rows for the appended vertices, and an error one vertex past the bound."""
+    from acfm_video_3d_reconstruction_amd import ops
+    assert SETUP_LDS_MAX_V == 12757 and 12 * 5600 > 64 * 1024
+    rng = np.random.default_rng(V)
+    v, f = meshes["bird_v"], meshes["bird_f"]
+    n, H, V0 = 2, 64, v.shape[0]
+    verts = np.concatenate([batch_verts(v, n, rng), rng.uniform(-1, 1, (n, V - V0, 3)).astype(np.float32)], 1)
+    cams = make_cams(n, rng, extent=float(np.abs(v).max()))
+    if V <= SETUP_LDS_MAX_V:
+        p = _check_sil(verts, f, cams, H, seed=V, zero_rows=slice(V0, V))
+        assert (p[..., 0] >= 0).mean() > 0.02
+    else:
+        d = _dev()
+        with pytest.raises(RuntimeError):
+            ops.sil_render(torch.tensor(verts, device=d), torch.from_numpy(f).to(d), torch.tensor(cams, device=d), H)

@@ -283,6 +283,30 @@ def test_bds_loss_vertex_and_point_counts(V):
         assert np.all(arg[3] == -1), what
 
 
+@pytest.mark.parametrize("V", [5462, 12800, 12801])
+def test_bds_loss_vertex_counts_past_64_kb_of_lds(V):
+    """k_bds_loss keeps 12 B per vertex in dynamic LDS (k_bds_loss_bwd 8 B) and accepts up to 150 KB: V = 5462
+    (65,544 B, the first size past 64 KB) and V = 12800 (153,600 B, the bound) at the bars of the smaller sizes, P = 65,
+    two meshes; V = 12801 is refused with an error."""
+    from acfm_video_3d_reconstruction_amd import ops
+    assert 12 * 5461 <= 64 * 1024 < 12 * 5462 and 12 * 12800 == 150 * 1024
+    rng = np.random.default_rng(V)
+    N, RB, P = 2, 2, 65
+    xy = rng.uniform(-1, 1, (N, V, 2)).astype(np.float32)
+    bds = np.concatenate([rng.uniform(-1, 1, (RB, P, 2)), np.ones((RB, P, 1))], -1).astype(np.float32)
+    bds[:, (P * 4) // 5:, 2] = 0.0                              # padding rows
+    vis = (rng.uniform(size=(N, V)) > 0.3).astype(np.uint8)
+    vis[0, :3], vis[0, V - 1], vis[1, V - 1] = 0, 1, 1          # the last LDS row is in use
+    w = rng.uniform(0.5, 1.5, N)
+    if V <= 12800:
+        _run_bds(xy, bds, vis, w, "V=%d P=%d" % (V, P))
+        return
+    d = _d()
+    txy, tb, tv = torch.tensor(xy, device=d, requires_grad=True), torch.tensor(bds, device=d), torch.tensor(vis, device=d)
+    with pytest.raises(RuntimeError):
+        ops.bds_loss_per_mesh(txy, tb, tv)
+
+
 @pytest.mark.parametrize("V", [65, 642, 2562])
 def test_bds_loss_exact_ties_go_to_the_lowest_vertex(V):
     """Duplicated visible vertices: inside one quarter and one 64-vertex compaction round, across a round, across the
