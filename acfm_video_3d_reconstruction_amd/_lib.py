@@ -114,6 +114,14 @@ SIGNATURES = {
     "acfm_visible_vertices": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "acfm_bds_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "acfm_bds_loss_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_chamfer_partial_floats": (_sz, [_i, _i, _i]),
+    "acfm_chamfer": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "acfm_chamfer_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "acfm_mesh_term_partial_floats": (_sz, [_i]),
+    "acfm_edge_length_loss": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "acfm_edge_length_loss_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
+    "acfm_normal_consistency": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "acfm_normal_consistency_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
 }
 
 _ERR = {1: "ACFM_E_BADARG (shape/parameter outside what the kernels support)",

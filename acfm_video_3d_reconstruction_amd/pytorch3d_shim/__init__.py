@@ -1,6 +1,8 @@
 """The slice of the PyTorch3D 0.3.0 API that the reference's callers import
 (multiframe/main.py:29-38, nnutils/predictor.py:9,21,64, nnutils/mesh_net.py:16):
-`structures.Meshes`, `loss.mesh_laplacian_smoothing`, `ops.SubdivideMeshes`, `io.load_obj`,
+`structures.Meshes`, `loss.mesh_laplacian_smoothing`, `ops.SubdivideMeshes`, `io.load_obj`, and what
+utils/geometry.py:63-72 imports for the template fit (`io.save_obj`, `utils.ico_sphere`,
+`ops.sample_points_from_meshes`, `loss.{chamfer_distance, mesh_edge_loss, mesh_normal_consistency}`),
 `transforms.{standardize_quaternion, quaternion_multiply, matrix_to_quaternion, ...}`.
 
 It is a shape-compatible shim (same names, arguments, return types), not PyTorch3D.  Of the
@@ -13,7 +15,7 @@ shader)` compositions run as written; nnutils.nmr keeps the hand-fused renders o
 Meshes` in unmodified caller code resolves to it when the real package is absent."""
 import sys
 
-from . import io, loss, ops, renderer, structures, transforms  # noqa: F401
+from . import io, loss, ops, renderer, structures, transforms, utils  # noqa: F401
 
 _RENDERER_MODULES = ("renderer", "renderer.blending", "renderer.cameras", "renderer.lighting", "renderer.materials",
                      "renderer.mesh", "renderer.mesh.rasterizer", "renderer.mesh.rasterize_meshes",
@@ -26,7 +28,7 @@ def install(force=False):
         return sys.modules["pytorch3d"]
     me = sys.modules[__name__]
     sys.modules["pytorch3d"] = me
-    for name in ("io", "loss", "ops", "structures", "transforms"):
+    for name in ("io", "loss", "ops", "structures", "transforms", "utils"):
         sys.modules["pytorch3d." + name] = getattr(me, name)
     for name in _RENDERER_MODULES:
         sys.modules["pytorch3d." + name] = sys.modules[__name__ + "." + name]

@@ -1,5 +1,6 @@
 """pytorch3d.io.load_obj as used at multiframe/main.py:159-160 and predictor.py:64:
-returns (verts [V,3] f32, faces namedtuple with .verts_idx [F,3] i64, aux)."""
+returns (verts [V,3] f32, faces namedtuple with .verts_idx [F,3] i64, aux); save_obj as imported by
+utils/geometry.py:63."""
 from collections import namedtuple
 
 import torch
@@ -39,3 +40,22 @@ def load_obj(f, load_textures=False, **kwargs):
     uv = torch.tensor(vts, dtype=torch.float32).reshape(-1, 2) if vts else None
     return v, Faces(fi, torch.full_like(fi, -1), ti, torch.full((fi.shape[0],), -1, dtype=torch.int64)), \
         Properties(None, uv, None, None, None)
+
+
+def save_obj(f, verts, faces, decimal_places=None):
+    """Writes 'v x y z' lines, then 1-based 'f i j k' lines.  f: a path or an open text file.  decimal_places=None
+    writes nine significant digits, which load_obj reads back to the same float32 values."""
+    if verts.numel() and not (verts.dim() == 2 and verts.shape[1] == 3):
+        raise ValueError("Argument 'verts' should either be empty or of shape (num_verts, 3).")
+    if faces.numel() and not (faces.dim() == 2 and faces.shape[1] == 3):
+        raise ValueError("Argument 'faces' should either be empty or of shape (num_faces, 3).")
+    fmt = "%.9g" if decimal_places is None else "%%.%df" % decimal_places
+    v = verts.detach().cpu().reshape(-1, 3).tolist()
+    fi = (faces.detach().cpu().long().reshape(-1, 3) + 1).tolist()
+    lines = ["v " + " ".join(fmt % c for c in row) for row in v] + ["f %d %d %d" % tuple(row) for row in fi]
+    text = "\n".join(lines) + ("\n" if lines else "")
+    if hasattr(f, "write"):
+        f.write(text)
+    else:
+        with open(f, "w") as fh:
+            fh.write(text)

@@ -1,5 +1,7 @@
 """pytorch3d.loss.mesh_laplacian_smoothing (called at multiframe/main.py:703 with 'cot',
-monocular/main.py:276 with 'uniform'); semantics: SURVEY App-A.7."""
+monocular/main.py:276 with 'uniform'); semantics: SURVEY App-A.7.  chamfer_distance, mesh_edge_loss and
+mesh_normal_consistency as utils/geometry.py:75-140 (fit_verts_to_mesh) calls them.  GPU tensors take the kernels of
+csrc/acfm_fit.hip, host tensors the torch formulations below."""
 import torch
 
 
@@ -59,3 +61,113 @@ def mesh_laplacian_smoothing(meshes, method: str = "uniform"):
         raise ValueError("Method should be one of {uniform, cot, cotcurv}")
     loss = loss.norm(dim=1) * weights
     return loss.sum() / N
+
+
+def _zero(meshes):
+    return torch.tensor([0.0], dtype=torch.float32, device=meshes.device, requires_grad=True)
+
+
+def _chamfer_sums_host(x, y, xl, yl):
+    """[N,2] as ops.chamfer_sums, with torch ops: the nearest index is chosen under no_grad (first occurrence of the
+    minimum), the distance to it is differentiable."""
+    N, P1, _ = x.shape
+    P2 = y.shape[1]
+    with torch.no_grad():
+        dx = x[:, :, None, 0] - y[:, None, :, 0]
+        dy = x[:, :, None, 1] - y[:, None, :, 1]
+        dz = x[:, :, None, 2] - y[:, None, :, 2]
+        d = (dx * dx + dy * dy) + dz * dz                                  # [N,P1,P2]
+        vx = torch.arange(P1, device=x.device)[None] < xl[:, None]         # [N,P1] rows that count
+        vy = torch.arange(P2, device=x.device)[None] < yl[:, None]
+        inf = torch.full_like(d, float("inf"))
+        d = torch.where(vx[:, :, None] & vy[:, None, :], d, inf)           # (padding may hold NaN: never compared)
+        ix = torch.from_numpy(d.numpy().argmin(2))                         # numpy: the first minimum, as documented
+        iy = torch.from_numpy(d.numpy().argmin(1))
+        vx = vx & (yl > 0)[:, None]
+        vy = vy & (xl > 0)[:, None]
+    zero = torch.zeros((), dtype=x.dtype)
+    ex = torch.where(vx[:, :, None], x, zero) - torch.where(vx[:, :, None], y.gather(1, ix[:, :, None].expand(-1, -1, 3)), zero)
+    ey = torch.where(vy[:, :, None], y, zero) - torch.where(vy[:, :, None], x.gather(1, iy[:, :, None].expand(-1, -1, 3)), zero)
+    cx = ((ex[..., 0] * ex[..., 0] + ex[..., 1] * ex[..., 1]) + ex[..., 2] * ex[..., 2]).sum(1)
+    cy = ((ey[..., 0] * ey[..., 0] + ey[..., 1] * ey[..., 1]) + ey[..., 2] * ey[..., 2]).sum(1)
+    return torch.stack([cx, cy], 1)
+
+
+def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
+                     batch_reduction="mean", point_reduction="mean"):
+    """-> (loss, None).  x [N,P1,3], y [N,P2,3] float32 tensors (Pointclouds are not supported); cham_x[n] =
+    sum_{i < x_lengths[n]} min_{j < y_lengths[n]} |x_i - y_j|^2 and cham_y its mirror image, times weights[n]; divided by
+    the lengths for point_reduction "mean"; summed over the batch for batch_reduction "sum", and divided by N (by
+    weights.sum() with weights) for "mean"; loss = cham_x + cham_y.  A length of 0 gives a sum of 0 (and 0 / 0 under
+    "mean").  Among equal distances the lowest index is the nearest neighbour."""
+    if x_normals is not None or y_normals is not None:
+        raise ValueError("chamfer_distance: x_normals / y_normals are not supported (the reference passes none)")
+    if batch_reduction is not None and batch_reduction not in ("mean", "sum"):
+        raise ValueError('batch_reduction must be one of ["mean", "sum"] or None')
+    if point_reduction not in ("mean", "sum"):
+        raise ValueError('point_reduction must be one of ["mean", "sum"]')
+    if not torch.is_tensor(x) or not torch.is_tensor(y):
+        raise ValueError("chamfer_distance: x and y must be tensors (Pointclouds are not supported)")
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise ValueError("chamfer_distance: x must have shape (N, P1, 3), got %s" % (tuple(x.shape),))
+    if y.dim() != 3 or y.shape[2] != 3 or y.shape[0] != x.shape[0]:
+        raise ValueError("chamfer_distance: y must have shape (N, P2, 3) with x's N, got %s" % (tuple(y.shape),))
+    N, P1, P2 = x.shape[0], x.shape[1], y.shape[1]
+    for name, t in (("x_lengths", x_lengths), ("y_lengths", y_lengths), ("weights", weights)):
+        if t is not None and tuple(t.shape) != (N,):
+            raise ValueError("chamfer_distance: %s must have shape (N,) = (%d,)" % (name, N))
+    if x.is_cuda:
+        from .. import ops
+        sums = ops.chamfer_sums(x, y, x_lengths, y_lengths)
+    else:
+        xl = torch.full((N,), P1, dtype=torch.int64) if x_lengths is None else x_lengths.long().clamp(0, P1)
+        yl = torch.full((N,), P2, dtype=torch.int64) if y_lengths is None else y_lengths.long().clamp(0, P2)
+        sums = _chamfer_sums_host(x.float(), y.float(), xl, yl)
+    cham_x, cham_y = sums[:, 0], sums[:, 1]
+    if weights is not None:
+        cham_x, cham_y = cham_x * weights, cham_y * weights
+    if point_reduction == "mean":
+        cham_x = cham_x / (float(P1) if x_lengths is None else x_lengths.to(cham_x.dtype))
+        cham_y = cham_y / (float(P2) if y_lengths is None else y_lengths.to(cham_y.dtype))
+    if batch_reduction is not None:
+        cham_x, cham_y = cham_x.sum(), cham_y.sum()
+        if batch_reduction == "mean":
+            div = weights.sum() if weights is not None else float(N)
+            cham_x, cham_y = cham_x / div, cham_y / div
+    return cham_x + cham_y, None
+
+
+def mesh_edge_loss(meshes, target_length: float = 0.0):
+    """sum_e w_e (|v_a - v_b| - target_length)^2 / N over edges_packed(), w_e = 1 / (edges of the edge's mesh)."""
+    if meshes.isempty():
+        return _zero(meshes)
+    N = len(meshes)
+    verts, edges = meshes.verts_packed(), meshes.edges_packed()
+    if edges.shape[0] == 0:
+        return _zero(meshes)
+    w = meshes.inv_num_edges_packed()
+    if verts.is_cuda:
+        from .. import ops
+        return ops.edge_length_sum(verts, edges, w, target_length) / N
+    d = verts[edges[:, 0]] - verts[edges[:, 1]]
+    return (((d.norm(dim=1) - target_length) ** 2.0) * w).sum() / N
+
+
+def mesh_normal_consistency(meshes):
+    """sum over the pairs of faces that share an edge of (1 - cos(n0, n1)) / (pairs of the mesh), / N; an edge in m
+    faces gives m (m - 1) / 2 pairs (Meshes.normal_pairs_packed())."""
+    if meshes.isempty():
+        return _zero(meshes)
+    N = len(meshes)
+    verts = meshes.verts_packed()
+    quads, w = meshes.normal_pairs_packed()
+    if quads.shape[0] == 0:
+        return _zero(meshes)
+    if verts.is_cuda:
+        from .. import ops
+        return ops.normal_consistency_sum(verts, quads, w) / N
+    a = verts[quads[:, 0]]
+    eb, ec, ed = verts[quads[:, 1]] - a, verts[quads[:, 2]] - a, verts[quads[:, 3]] - a
+    n0, n1 = torch.cross(ec, eb, dim=1), -torch.cross(ed, eb, dim=1)
+    cos = (n0 * n1).sum(1) / (n0.norm(dim=1) * n1.norm(dim=1)).clamp(min=1e-8)
+    return ((1.0 - cos) * w).sum() / N

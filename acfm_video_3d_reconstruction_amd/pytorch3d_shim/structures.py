@@ -19,6 +19,14 @@ def _may_keep(t):
 
 _FACES_PACKED_CACHE = {}   # same keying and lifetime rule as _EDGE_CACHE: (padded faces tensor, V) -> packed faces
 _WEIGHT_CACHE = {}         # (meshes, verts per mesh, device) -> 1 / V per packed vertex
+# same keying and lifetime rule again, for everything else that depends on topology only (the edge / face index maps
+# and the pair table of mesh_normal_consistency): faces tensor(s) -> (the tensors, {name: result}).  Here a Meshes built
+# from a LIST of faces tensors has a key too (one entry per tensor): fit_verts_to_mesh builds its meshes that way.
+_TOPO_CACHE = {}
+
+
+def _tensor_key(t):
+    return (t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version, str(t.device), str(t.dtype))
 
 
 class Meshes:
@@ -144,6 +152,8 @@ class Meshes:
     def edges_packed(self):
         """Unique (min, max) vertex pairs of all packed faces in lexicographic order
         (SURVEY App-A.9)."""
+        if "edges_packed" not in self._cache and self._faces_padded is None:
+            self._topology()      # a batch given as a list of faces tensors: the table kept for those tensors, if any
         if "edges_packed" not in self._cache:
             ck = None
             if self._faces_padded is not None and self._equal_sized():
@@ -167,7 +177,110 @@ class Meshes:
                     if len(_EDGE_CACHE) > 16:
                         _EDGE_CACHE.clear()
                     _EDGE_CACHE[ck] = (fp_, self._cache["edges_packed"])
+                if self._faces_padded is None and _may_keep(self._cache["edges_packed"]):
+                    self._topology().setdefault("edges_packed", self._cache["edges_packed"])
         return self._cache["edges_packed"]
+
+    # ---- topology-only tables, memoised on the faces tensor(s) like the edges above
+    def _topology(self):
+        if "topology" not in self._cache:
+            src = [self._faces_padded] if self._faces_padded is not None and self._equal_sized() else list(self._faces_list)
+            ck = (tuple(_tensor_key(t) for t in src), tuple(v.shape[0] for v in self._verts_list))
+            hit = _TOPO_CACHE.get(ck)
+            if hit is None:
+                hit = (src, {})
+                if all(_may_keep(t) for t in src):
+                    if len(_TOPO_CACHE) > 16:
+                        _TOPO_CACHE.clear()
+                    _TOPO_CACHE[ck] = hit
+            self._cache["topology"] = hit[1]
+            if "edges_packed" in hit[1]:
+                self._cache.setdefault("edges_packed", hit[1]["edges_packed"])
+        return self._cache["topology"]
+
+    def _topo(self, name, make):
+        t = self._topology()
+        if name not in t:
+            if "edges_packed" not in t:
+                e = self.edges_packed()
+                if _may_keep(e):
+                    t["edges_packed"] = e
+            val = make()
+            if not all(_may_keep(x) for x in (val if isinstance(val, tuple) else (val,))):
+                return val
+            t[name] = val
+        return t[name]
+
+    def get_mesh_verts_faces(self, index):
+        if not isinstance(index, int):
+            raise ValueError("Mesh index must be an integer.")
+        if index < 0 or index >= len(self):
+            raise ValueError("Mesh index must be in the range [0, N) where N is the number of meshes in the batch.")
+        return self._verts_list[index], self._faces_list[index]
+
+    def mesh_to_faces_packed_first_idx(self):
+        n = self.num_faces_per_mesh()
+        return torch.cumsum(n, 0) - n
+
+    def edges_packed_to_mesh_idx(self):
+        """[E] the mesh every edge of edges_packed() belongs to."""
+        def make():
+            return self.verts_packed_to_mesh_idx()[self.edges_packed()[:, 0]]
+        return self._topo("edges_packed_to_mesh_idx", make)
+
+    def num_edges_per_mesh(self):
+        def make():
+            return torch.bincount(self.edges_packed_to_mesh_idx(), minlength=len(self))
+        return self._topo("num_edges_per_mesh", make)
+
+    def inv_num_edges_packed(self):
+        """1 / (edges of its mesh) per packed edge, float32: the weights of mesh_edge_loss."""
+        def make():
+            return 1.0 / self.num_edges_per_mesh().gather(0, self.edges_packed_to_mesh_idx()).float()
+        return self._topo("inv_num_edges_packed", make)
+
+    def faces_packed_to_edges_packed(self):
+        """[F,3]: for every packed face (v0, v1, v2) the rows of edges_packed() of its edges v1v2, v2v0, v0v1."""
+        def make():
+            f, e = self.faces_packed(), self.edges_packed()
+            V = sum(v.shape[0] for v in self._verts_list)
+            key = e[:, 0] * V + e[:, 1]
+            a, b = f[:, [1, 2, 0]], f[:, [2, 0, 1]]
+            return torch.searchsorted(key, (torch.minimum(a, b) * V + torch.maximum(a, b)).reshape(-1)).reshape(-1, 3)
+        return self._topo("faces_packed_to_edges_packed", make)
+
+    def normal_pairs_packed(self):
+        """-> (quads [Q,4] int64 = (a, b, c, d), weights [Q] float32) for mesh_normal_consistency: for every edge
+        (a, b), a < b, that lies in m >= 2 faces, every unordered pair of those faces, c and d being the faces' third
+        vertices; weight = 1 / (pairs of the edge's mesh).  Topology only: built once per faces tensor, on the host."""
+        def make():
+            import numpy as np
+            f = self.faces_packed().cpu().numpy()
+            sizes = np.array([v.shape[0] for v in self._verts_list], np.int64)
+            V = int(sizes.sum())
+            a = np.concatenate([f[:, 1], f[:, 2], f[:, 0]])
+            b = np.concatenate([f[:, 2], f[:, 0], f[:, 1]])
+            opp = np.concatenate([f[:, 0], f[:, 1], f[:, 2]])
+            lo, hi = np.minimum(a, b), np.maximum(a, b)
+            keep = lo != hi
+            key, opp = (lo * V + hi)[keep], opp[keep]
+            order = np.argsort(key, kind="stable")
+            key, opp = key[order], opp[order]
+            uniq, start, count = np.unique(key, return_index=True, return_counts=True)
+            quads = []
+            for m in np.unique(count[count >= 2]):
+                g = np.nonzero(count == m)[0]
+                third = opp[start[g][:, None] + np.arange(m)[None]]          # [G, m]
+                i, j = np.triu_indices(int(m), 1)
+                k = np.repeat(uniq[g], i.size)
+                quads.append(np.stack([k // V, k % V, third[:, i].reshape(-1), third[:, j].reshape(-1)], 1))
+            q = np.concatenate(quads, 0) if quads else np.zeros((0, 4), np.int64)
+            q = q[np.argsort(q[:, 0] * V + q[:, 1], kind="stable")]
+            mesh = np.searchsorted(np.cumsum(sizes), q[:, 0], side="right")
+            per_mesh = np.bincount(mesh, minlength=len(self))
+            w = (1.0 / per_mesh[mesh]).astype(np.float32)
+            return torch.from_numpy(q).to(self.device), torch.from_numpy(w).to(self.device)
+        return self._topo("normal_pairs_packed", make)
 
     def laplacian_packed(self):
         """Uniform Laplacian, sparse [sum V, sum V]: L[i,j] = 1/deg(i) on edges, L[i,i] = -1."""

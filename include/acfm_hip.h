@@ -641,6 +641,49 @@ int acfm_edge_rigidity_backward(const float* verts, const int64_t* edges, const 
  * 12 B of dynamic LDS per vertex, at most 150 KB: verts_per_mesh <= 12,800; larger meshes, and a verts_per_mesh that
  * does not divide P, take the global-atomic kernel: same result, no error. */
 
+/* ---- template fit (utils/geometry.py:75-140, fit_verts_to_mesh) ------------------------------
+ * acfm_chamfer: the sums of pytorch3d.loss.chamfer_distance.  x [N,P1,3], y [N,P2,3] f32; x_len, y_len [N] i64 on the
+ *   device or NULL (= P1 / P2; values are clamped to [0, P]).  Rows at or past a length are never read.
+ *     sums[n,0] = sum_{i < x_len[n]} min_{j < y_len[n]} |x_i - y_j|^2,   sums[n,1] = the same with x and y exchanged,
+ *     idx_x [N,P1], idx_y [N,P2] i32: the index of that nearest point, the lowest one among equal distances, -1 if the
+ *     other cloud has length 0 (then the sum is 0); rows at or past the length are not written.
+ *   |.|^2 = (dx dx + dy dy) + dz dz in f32, each operation rounded.  Both directions are one launch; the candidates
+ *   stream through a fixed 16 KB of LDS, so P1 and P2 are bounded by int only; N <= 65535.
+ *   Scratch as for acfm_mask_losses_ws, but 2 N ticket words (all zero before the first use, zero again after every
+ *   launch) and acfm_chamfer_partial_floats(N, P1, P2) floats of any contents, both required: no zero fill of
+ *   `sums`, no float atomics, the same bits on every run.
+ * acfm_chamfer_backward: grad_sums [N,2] (device) -> grad_x [N,P1,3], grad_y [N,P2,3]; EVERY row is written (zeros
+ *   at and past the lengths).  A point receives 2 g (p - nn(p)) for its own nearest neighbour and 2 g' (p - r) from
+ *   every point r of the other cloud that chose it.  One workgroup per (pair, side) sums in LDS, 12 B per point, at
+ *   most 150 KB: max(P1, P2) <= 12,800; larger clouds take two launches with global atomics, same result.  Either way
+ *   the order of the float additions varies from run to run: the gradients are NOT bit-reproducible. */
+size_t acfm_chamfer_partial_floats(int N, int P1, int P2);
+int acfm_chamfer(const float* x, const float* y, const int64_t* x_len, const int64_t* y_len, int N, int P1, int P2,
+                 float* sums, int32_t* idx_x, int32_t* idx_y, uint32_t* tickets, float* partials,
+                 size_t partial_floats, void* stream);
+int acfm_chamfer_backward(const float* x, const float* y, const int64_t* x_len, const int64_t* y_len,
+                          const int32_t* idx_x, const int32_t* idx_y, const float* grad_sums, int N, int P1, int P2,
+                          float* grad_x, float* grad_y, void* stream);
+/* acfm_edge_length_loss: pytorch3d.loss.mesh_edge_loss on packed meshes: loss = sum_e eweight[e] (|v_a - v_b| - target)^2
+ *   (eweight = 1 / edges of the edge's mesh; the caller divides by the mesh count).  verts [P,3], edges [E,2] i64,
+ *   eweight [E].  An edge with a vertex outside [0, P) is skipped; the subgradient at a zero-length edge is 0.
+ * acfm_normal_consistency: pytorch3d.loss.mesh_normal_consistency: quads [Q,4] i64 = (a, b, c, d), the two faces
+ *   (a, b, c) and (a, b, d) on the edge a-b; loss = sum_q qweight[q] (1 - n0.n1 / max(|n0| |n1|, 1e-8)) with
+ *   n0 = (c - a) x (b - a), n1 = -((d - a) x (b - a)).
+ * Both: one launch, the workgroups' sums meet in a ticket finish (1 ticket word, zero between launches, and
+ *   acfm_mesh_term_partial_floats(E or Q) floats, both required); loss is 1 float on the device.  The backward takes
+ *   the upstream gradient as a device scalar and adds into grad_verts [P,3], which it zeroes first (float atomics). */
+size_t acfm_mesh_term_partial_floats(int count);
+int acfm_edge_length_loss(const float* verts, const int64_t* edges, const float* eweight, int P, int E, float target,
+                          float* loss, uint32_t* tickets, float* partials, size_t partial_floats, void* stream);
+int acfm_edge_length_loss_backward(const float* verts, const int64_t* edges, const float* eweight,
+                                   const float* grad_loss, int P, int E, float target, float* grad_verts,
+                                   void* stream);
+int acfm_normal_consistency(const float* verts, const int64_t* quads, const float* qweight, int P, int Q, float* loss,
+                            uint32_t* tickets, float* partials, size_t partial_floats, void* stream);
+int acfm_normal_consistency_backward(const float* verts, const int64_t* quads, const float* qweight,
+                                     const float* grad_loss, int P, int Q, float* grad_verts, void* stream);
+
 /* ---- on-device input preparation ----------------------------------------
  * replaces the per-batch CPU work of ShapeTrainer.set_input (multiframe/main.py:365-377) and
  * its device->host->device round trip of the masks.
