@@ -122,6 +122,9 @@ SIGNATURES = {
     "acfm_edge_length_loss_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
     "acfm_normal_consistency": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "acfm_normal_consistency_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "acfm_uv_atlas_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_uv_atlas_taps": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "acfm_uv_atlas_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _ERR = {1: "ACFM_E_BADARG (shape/parameter outside what the kernels support)",

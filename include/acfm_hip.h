@@ -684,6 +684,32 @@ int acfm_normal_consistency(const float* verts, const int64_t* quads, const floa
 int acfm_normal_consistency_backward(const float* verts, const int64_t* quads, const float* qweight,
                                      const float* grad_loss, int P, int Q, float* grad_verts, void* stream);
 
+/* ---- texture head: UV image -> face atlas (multiframe/nnutils/mesh_net.py:169-179) ---------------
+ * replaces F.grid_sample(uvimage, uv_sampler.repeat(B,1,1,1), align_corners=True) -> reshape / permute to
+ * [B,Fp,T,T,3] -> (tanh + 1) / 2 -> cat([tex, tex[:, -nsym:]], 1), and its backward.  float32, 3 channels.
+ *   uvimage [B,3,Hu,Wu]; sampler [Fp,T,T,2] = (u, v) in the grid_sample convention (utils/mesh.py:206-232), finite,
+ *   constant for the life of the model; atlas [B,Fp+nsym,T,T,3]: face Fp + j holds what face Fp - nsym + j holds.
+ *   B, Fp, T >= 1; 0 <= nsym <= Fp; Hu, Wu >= 2; Fp T T <= 2^28, Hu Wu <= 2^30.
+ *   Bilinear taps with zero padding: x = ((u + 1) / 2) (Wu - 1), y likewise, corners nw, ne, sw, se of (floor x,
+ *   floor y), weights as ATen's, accumulated in that order by fused multiply-adds (as ATen's HIP kernel is built); a
+ *   corner outside the image contributes nothing.
+ * acfm_uv_atlas_forward: one launch; every element of the atlas is written (no fill needed before it).
+ * acfm_uv_atlas_taps: tap_pixel [n_samples,4] i32 = pixel y Wu + x of each sample's four corners, -1 outside -- by
+ *   the same device function the forward evaluates.  The caller transposes it ONCE per sampler into the per-pixel
+ *   lists the backward walks: pix_start [Hu Wu + 1] i32 (offsets), pix_taps [n_entries] i32 = sample * 4 + corner.
+ * acfm_uv_atlas_backward: grad_uvimage[b,c,p] = sum over pixel p's entries, in list order, of
+ *   weight * 2 y (1 - y) * (grad_atlas[b,f',t,c] + grad_atlas[b,mirror of f',t,c]), y = atlas[b,f',t,c] as the forward
+ *   left it.  One launch, a gather: no float atomics, no zero fill, EVERY pixel written (0 for an empty list), the same
+ *   bits on every run.  A list of more than 32 entries is summed by a whole wave (lane-strided partial sums, then a
+ *   fixed butterfly); lists may have any length.  n_entries = pix_start[Hu Wu] <= 4 Fp T T; entries outside
+ *   [0, 4 Fp T T) are skipped. */
+int acfm_uv_atlas_forward(const float* uvimage, const float* sampler, int B, int Hu, int Wu, int Fp, int T, int nsym,
+                          float* atlas, void* stream);
+int acfm_uv_atlas_taps(const float* sampler, int n_samples, int Hu, int Wu, int32_t* tap_pixel, void* stream);
+int acfm_uv_atlas_backward(const float* grad_atlas, const float* atlas, const float* sampler, const int32_t* pix_start,
+                           const int32_t* pix_taps, int n_entries, int B, int Hu, int Wu, int Fp, int T, int nsym,
+                           float* grad_uvimage, void* stream);
+
 /* ---- on-device input preparation ----------------------------------------
  * replaces the per-batch CPU work of ShapeTrainer.set_input (multiframe/main.py:365-377) and
  * its device->host->device round trip of the masks.
