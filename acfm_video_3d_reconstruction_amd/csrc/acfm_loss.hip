@@ -20,6 +20,19 @@ static inline int fwd_pix_per_block(int N, int HW) {
   return (size_t)N * ((HW + PIX_PER_BLOCK_WIDE - 1) / PIX_PER_BLOCK_WIDE) >= 2 * CUS ? PIX_PER_BLOCK_WIDE : PIX_PER_BLOCK;
 }
 
+// A workgroup's run of at most 8192 consecutive floats as a raw buffer: a 16-byte load whose byte offset does not lie
+// inside [0, bytes - 16] returns zeros and touches no memory.  (word 3: 32-bit data format, as for every untyped
+// buffer access on gfx9)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t pixel_range(const float* base, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
+}
+constexpr int OUT_OF_RANGE = 0x7ffffff0;   // a byte offset past every such range, and adding 15 to it does not wrap
+__device__ __forceinline__ float4 load16_in_range(__amdgpu_buffer_rsrc_t r, int byte_offset) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  const f4 v = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_offset, 0, 0));
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+
 // out[n] = (sum|m-gt|/HW, sum m*gt, sum(m+gt-m*gt), sum edt*m/HW); one pass over the mask.
 // (prediction n is compared with reference n % RB: the G camera hypotheses of a frame share the
 // frame's ground truth, so the trainer's gt.repeat(G, ...) copies are never made)
@@ -38,6 +51,7 @@ __global__ __launch_bounds__(LTPB) void k_mask_losses(const float* __restrict__ 
   if (vec) {
     // the block's two 16-byte pieces per thread and array are loaded before any of them is used
     constexpr int U = PIX_FWD / (LTPB * 4);
+    static_assert(PIX_FWD % (LTPB * 4) == 0, "whole rounds of one 16-byte piece per thread");
     float4 m[U], g[U], e[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -45,7 +59,20 @@ __global__ __launch_bounds__(LTPB) void k_mask_losses(const float* __restrict__ 
       const bool in = i < end;
       m[u] = in ? *reinterpret_cast<const float4*>(mask + base + i) : make_float4(0, 0, 0, 0);
       g[u] = (in && gt) ? *reinterpret_cast<const float4*>(gt + rbase + i) : make_float4(0, 0, 0, 0);
-      e[u] = (in && edt) ? *reinterpret_cast<const float4*>(edt + rbase + i) : make_float4(0, 0, 0, 0);
+    }
+    // edt m is +0 wherever the rendered mask is 0 (most of a frame): edt is fetched only for the pieces whose four mask
+    // values are not all zero -- the other lanes present an offset outside the workgroup's range and get zeros back
+    // without a memory access (load16_in_range), and a3 + (+0) == a3
+    if (edt) {
+      const __amdgpu_buffer_rsrc_t re = pixel_range(edt + rbase + start, (unsigned)(end - start) * 4u);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const bool want = m[u].x != 0.f || m[u].y != 0.f || m[u].z != 0.f || m[u].w != 0.f;
+        e[u] = load16_in_range(re, want ? (u * LTPB + tid) * 16 : OUT_OF_RANGE);
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) e[u] = make_float4(0, 0, 0, 0);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -123,20 +150,55 @@ __global__ __launch_bounds__(LTPB) void k_tex_mse(const float* __restrict__ tex,
   const int end = min(start + PIX_FWD, HW);
   float acc = 0.f;
   if ((HW & 3) == 0) {   // 16-byte loads
-    for (int i = start + tid * 4; i < end; i += LTPB * 4) {
-      const float4 mk = *reinterpret_cast<const float4*>(m + b1 + i);
+    // The mask first: where a piece's four mask values are all zero, (t m - g m)^2 is +0 for finite t and g and
+    // acc + (+0) == acc, so the piece's six colour loads fetch nothing (the reference mask covers about a sixth of
+    // a frame).  No branch does that: the colours come through buffer loads over the workgroup's pixel range, and a
+    // lane whose piece is not wanted (or lies past the end) presents an offset outside the range, for which the
+    // hardware returns zeros without a memory access.  Every piece then goes through the same expression in the
+    // same order as before; an unread piece contributes (0 * 0 - 0 * 0)^2 = +0.
+    constexpr int U = PIX_FWD / (LTPB * 4);
+    constexpr int UB = U < 4 ? U : 4;   // pieces whose colour loads are in flight together (24 VGPRs each)
+    static_assert(PIX_FWD % (LTPB * 4) == 0 && U % UB == 0, "a workgroup's pixels are whole rounds of one 16-byte piece per thread");
+    const unsigned range_bytes = (unsigned)(end - start) * 4u;   // <= PIX_FWD * 4
+    const __amdgpu_buffer_rsrc_t rm = pixel_range(m + b1 + start, range_bytes);
+    float4 mk[U];   // (the same way: a piece past the end reads as zeros, and no branch splits the loads up)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float4 t = *reinterpret_cast<const float4*>(tex + b3 + (size_t)c * HW + i);
-        const float4 g = *reinterpret_cast<const float4*>(img + r3 + (size_t)c * HW + i);
-        const float d0 = t.x * mk.x - g.x * mk.x, d1 = t.y * mk.y - g.y * mk.y;
-        const float d2 = t.z * mk.z - g.z * mk.z, d3 = t.w * mk.w - g.w * mk.w;
-        acc += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+    for (int u = 0; u < U; ++u) mk[u] = load16_in_range(rm, (u * LTPB + tid) * 16);
+    __amdgpu_buffer_rsrc_t rt[3], rg[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      rt[c] = pixel_range(tex + b3 + (size_t)c * HW + start, range_bytes);
+      rg[c] = pixel_range(img + r3 + (size_t)c * HW + start, range_bytes);
+    }
+#pragma unroll
+    for (int u0 = 0; u0 < U; u0 += UB) {
+      float4 t[UB][3], g[UB][3];
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        const float4 k = mk[u0 + u];
+        const bool want = k.x != 0.f || k.y != 0.f || k.z != 0.f || k.w != 0.f;
+        const int off = want ? ((u0 + u) * LTPB + tid) * 16 : OUT_OF_RANGE;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          t[u][c] = load16_in_range(rt[c], off);
+          g[u][c] = load16_in_range(rg[c], off);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        const float4 k = mk[u0 + u];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float d0 = t[u][c].x * k.x - g[u][c].x * k.x, d1 = t[u][c].y * k.y - g[u][c].y * k.y;
+          const float d2 = t[u][c].z * k.z - g[u][c].z * k.z, d3 = t[u][c].w * k.w - g[u][c].w * k.w;
+          acc += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+        }
       }
     }
   } else
   for (int i = start + tid; i < end; i += LTPB) {
     const float mk = m[b1 + i];
+    if (mk == 0.f) continue;   // adds +0 for finite colours: not read
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float d = tex[b3 + (size_t)c * HW + i] * mk - img[r3 + (size_t)c * HW + i] * mk;

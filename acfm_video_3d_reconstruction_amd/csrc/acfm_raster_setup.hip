@@ -189,6 +189,7 @@ __global__ __launch_bounds__(TPB) void k_setup(const float* __restrict__ verts,
 // near: the entry is flagged and the raster kernels write that block's zeros without looking at
 // the mesh at all.
 constexpr int NCLASS = 10;
+constexpr int ORDER_MAX_WGS = 128;   // workgroups of a k_order launch (launch_setup)
 // (the classes above 160 exist to ORDER the heaviest blocks: at 64 frames the blocks of >= 240 face boxes -- 89 of
 // 15 474, 3 % of the work -- start first and still run for the whole launch; see the split rule in k_order.  Every
 // class costs k_order a ballot per entry and pass: 12 classes measured 18.1 us per launch against 13.3 with 8)
@@ -196,23 +197,30 @@ __device__ __forceinline__ int cost_class(int c) {
   return c >= 240 ? 0 : c >= 200 ? 1 : c >= 160 ? 2 : c >= 112 ? 3 : c >= 80 ? 4 : c >= 56 ? 5 : c >= 36 ? 6 : c >= 20 ? 7 : c >= 1 ? 8 : 9;
 }
 template <bool MORE>   // MORE: k_setup ran 8 or 16 face slices per mesh (few meshes); false: the usual four
-__global__ __launch_bounds__(1024) void k_order(RasterWs ws, int N, int tt, int H, int g_split_dev) {
-  // counting sort by cost class without atomics: every wave counts its entries per class (ballots,
-  // wave-uniform counters), the counts are prefix-summed over (class, wave), and every wave then
-  // scatters its entries from its own running offsets.  Deterministic order.
+__global__ __launch_bounds__(1024) void k_order(RasterWs ws, int N, int tt, int H, int g_split_dev, int mpw) {
+  // Counting sort by cost class without atomics.  Grid (G, W): workgroup (g, w) places the entries of the meshes
+  // w mpw .. w mpw + mpw - 1 of XCD group g (mpw = 1, a workgroup per mesh, up to ORDER_MAX_WGS workgroups in the
+  // launch; one workgroup per group beyond N = 8 ORDER_MAX_WGS).  An entry's position is
+  //     the class's base in the group  +  the entries of that class in the group's earlier meshes  +  its rank among
+  //     the workgroup's own entries
+  // The first two come from the cost planes of the group's OTHER meshes, which every workgroup of the group classifies
+  // for itself (ballots, wave-uniform counters): no workgroup waits for another.  The rank is the old scheme on the
+  // workgroup's own entries: every wave counts its entries per class, the counts are prefix-summed over (class, wave),
+  // every wave scatters from its own running offsets.  Deterministic order: class, workgroup, wave, entry.
+  // Every cost plane is loaded once per workgroup, as it was when one workgroup per group did all of this (18.7 us on 8
+  // CUs at 64 frames @256^2; 10.7 us with 64 workgroups); the launch as a whole reads them W times, from L2.
   constexpr int NW = 16;   // waves of the workgroup
-  __shared__ int s_cnt[NCLASS][NW], s_off[NCLASS][NW], s_hist[NCLASS], s_split;
+  __shared__ int s_cnt[NCLASS][NW], s_off[NCLASS][NW], s_all[NCLASS][NW], s_bef[NCLASS][NW], s_hist[NCLASS], s_before[NCLASS], s_split;
   const int G = gridDim.x, g = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int per = (N / G) * tt;
-  const int iters = (per + (int)blockDim.x - 1) / (int)blockDim.x;
+  const int M = N / G, per = M * tt;
+  const int m_lo = (int)blockIdx.y * mpw, m_hi = min(M, m_lo + mpw);
+  const int lo = m_lo * tt, hi = m_hi * tt;   // this workgroup's entries: lo .. hi - 1
   // entry e = m tt + bl  <->  mesh m G + g, block bl; its cost is tile_cnt[mesh][bl] (CNT_TILE == RBLK).
-  // (m, bl) advance with e: no integer divisions in the loops (they were 2000 VALU instructions per wave).
   static_assert(CNT_TILE == RBLK, "cost counters are per raster block");
-  const int m_first = (int)threadIdx.x / tt, bl_first = (int)threadIdx.x % tt;
   if constexpr (MORE) {
     // the mesh boxes: k_setup left one box per face slice; the raster kernels test a block against the mesh's box: with
     // more than four slices it is joined here, once, into the first slot
-    for (int m = threadIdx.x; m < N / G; m += blockDim.x) {
+    for (int m = m_lo + (int)threadIdx.x; m < m_hi; m += blockDim.x) {
       float4* mb = ws.mbox + (size_t)(m * G + g) * ws.slices;
       float4 u = mb[0];
       for (int i = 1; i < ws.slices; ++i) {
@@ -222,71 +230,110 @@ __global__ __launch_bounds__(1024) void k_order(RasterWs ws, int N, int tt, int 
       mb[0] = u;
     }
   }
-  constexpr int OCH = 8;   // entries per thread whose cost loads are in flight together
   const bool parts = tt <= SETUP_LDS_TILES;   // k_setup kept its counters in LDS: one plane per face slice
+  // cost of block bl of the group's mesh mm: the sum of the face slices' planes (k_setup), or the finished counter
+  auto cost = [&](int mm, int bl) {
+    const size_t o = (size_t)(mm * G + g) * tt + bl;
+    if (!parts) return ws.tile_cnt[o];
+    const size_t plane = (size_t)N * tt;
+    int c = (ws.tile_part[o] + ws.tile_part[plane + o]) + (ws.tile_part[2 * plane + o] + ws.tile_part[3 * plane + o]);
+    if constexpr (MORE)
+      for (int sl = 4; sl < ws.slices; sl += 4)     // 8 or 16 planes
+        c += (ws.tile_part[sl * plane + o] + ws.tile_part[(sl + 1) * plane + o]) +
+             (ws.tile_part[(sl + 2) * plane + o] + ws.tile_part[(sl + 3) * plane + o]);
+    return c;
+  };
+  // (mm, bl) advance with e: no integer divisions in the loops (they were 2000 VALU instructions per wave)
+  // pass 1a, the workgroup's own entries: one per thread while there are at most 1024, a loop above that.  The sum of the
+  // planes is kept for the later readers (k_tex_cover, the stamps) and for the scatter below.
+  const int own_iters = (hi - lo + (int)blockDim.x - 1) / (int)blockDim.x;
   int cnt[NCLASS];
 #pragma unroll
   for (int c = 0; c < NCLASS; ++c) cnt[c] = 0;
-  int m1 = m_first, bl1 = bl_first;
-  int cst0[OCH];          // the costs of the first OCH entries of this thread: all of them up to 8192 entries per group
-                          // (64 frames @256^2), so that the scatter pass below does not load them again
+  int cst_first = -1;
+  {
+    int m1 = m_lo + (int)threadIdx.x / tt, bl1 = (int)threadIdx.x % tt;
+    for (int it = 0; it < own_iters; ++it) {
+      const int e = lo + it * (int)blockDim.x + (int)threadIdx.x;
+      int cs = -1;
+      if (e < hi) {
+        cs = cost(m1, bl1);
+        if (parts) ws.tile_cnt[(size_t)(m1 * G + g) * tt + bl1] = cs;
+      }
+      bl1 += blockDim.x;
+      while (bl1 >= tt) { bl1 -= tt; ++m1; }
+      if (it == 0) cst_first = cs;
+      const int cl = cs < 0 ? -1 : cost_class(cs);
+#pragma unroll
+      for (int c = 0; c < NCLASS; ++c) cnt[c] += __popcll(__ballot(cl == c));
+    }
+  }
+  // pass 1b, the other meshes of the group: entries per class, and of those the ones of the earlier meshes (e < lo).
+  // (nothing to do for a workgroup that owns the whole group)
+  constexpr int OCH = 8;   // entries per thread whose cost loads are in flight together
+  const int iters = (lo == 0 && hi == per) ? 0 : (per + (int)blockDim.x - 1) / (int)blockDim.x;
+  int all[NCLASS], bef[NCLASS];
+#pragma unroll
+  for (int c = 0; c < NCLASS; ++c) { all[c] = 0; bef[c] = 0; }
+  int m1 = (int)threadIdx.x / tt, bl1 = (int)threadIdx.x % tt;
   for (int it0 = 0; it0 < iters; it0 += OCH) {
     int cst[OCH];
 #pragma unroll
     for (int u = 0; u < OCH; ++u) {
       const int e = (it0 + u) * blockDim.x + threadIdx.x;
-      cst[u] = -1;
-      if (it0 + u < iters && e < per) {
-        const size_t o = (size_t)(m1 * G + g) * tt + bl1;
-        if (parts) {   // the four face slices' planes (k_setup); the sum is kept for the later readers (k_tex_cover)
-          const size_t plane = (size_t)N * tt;
-          cst[u] = (ws.tile_part[o] + ws.tile_part[plane + o]) + (ws.tile_part[2 * plane + o] + ws.tile_part[3 * plane + o]);
-          if constexpr (MORE)
-            for (int sl = 4; sl < ws.slices; sl += 4)     // 8 or 16 planes
-              cst[u] += (ws.tile_part[sl * plane + o] + ws.tile_part[(sl + 1) * plane + o]) +
-                        (ws.tile_part[(sl + 2) * plane + o] + ws.tile_part[(sl + 3) * plane + o]);
-          ws.tile_cnt[o] = cst[u];
-        } else {
-          cst[u] = ws.tile_cnt[o];
-        }
-      }
+      cst[u] = (it0 + u < iters && e < per && (e < lo || e >= hi)) ? cost(m1, bl1) : -1;
       bl1 += blockDim.x;
       while (bl1 >= tt) { bl1 -= tt; ++m1; }
-      if (it0 == 0) cst0[u] = cst[u];
     }
 #pragma unroll
     for (int u = 0; u < OCH; ++u) {
-      const int cl = cst[u] < 0 ? -1 : cost_class(cst[u]);
+      const int e = (it0 + u) * blockDim.x + threadIdx.x;
+      const int e_w0 = (it0 + u) * (int)blockDim.x + wv * 64;   // the wave's first entry (wave-uniform)
+      const int cl = cst[u] < 0 ? -1 : cost_class(cst[u]);      // (-1: no entry, or one of the workgroup's own)
+      if (e_w0 + 63 < lo) {            // the whole wave stands before the workgroup's entries
 #pragma unroll
-      for (int c = 0; c < NCLASS; ++c) cnt[c] += __popcll(__ballot(cl == c));
+        for (int c = 0; c < NCLASS; ++c) { const int k = __popcll(__ballot(cl == c)); all[c] += k; bef[c] += k; }
+      } else if (e_w0 >= lo) {         // none of it does
+#pragma unroll
+        for (int c = 0; c < NCLASS; ++c) all[c] += __popcll(__ballot(cl == c));
+      } else {
+#pragma unroll
+        for (int c = 0; c < NCLASS; ++c) {
+          all[c] += __popcll(__ballot(cl == c));
+          bef[c] += __popcll(__ballot(cl == c && e < lo));
+        }
+      }
     }
   }
   if (lane == 0) {
 #pragma unroll
-    for (int c = 0; c < NCLASS; ++c) s_cnt[c][wv] = cnt[c];
+    for (int c = 0; c < NCLASS; ++c) { s_cnt[c][wv] = cnt[c]; s_all[c][wv] = all[c]; s_bef[c][wv] = bef[c]; }
   }
   __syncthreads();
-  if (threadIdx.x < NCLASS) {   // per class: total, then (below) the offsets of the waves inside the class
-    int t = 0;
-    for (int w = 0; w < NW; ++w) t += s_cnt[threadIdx.x][w];
+  const int nwaves = (int)blockDim.x >> 6;
+  if (threadIdx.x < NCLASS) {   // per class: the group's total (the other meshes' and the own entries) and the share of the earlier meshes
+    int t = 0, b = 0;
+    for (int w = 0; w < nwaves; ++w) { t += s_all[threadIdx.x][w] + s_cnt[threadIdx.x][w]; b += s_bef[threadIdx.x][w]; }
     s_hist[threadIdx.x] = t;
+    s_before[threadIdx.x] = b;
   }
   __syncthreads();
-  if (threadIdx.x < NCLASS) {
-    int acc = 0;
+  if (threadIdx.x < NCLASS) {   // the offsets of this mesh's waves inside the class
+    int acc = s_before[threadIdx.x];
     for (int c = 0; c < (int)threadIdx.x; ++c) acc += s_hist[c];
-    for (int w = 0; w < NW; ++w) { s_off[threadIdx.x][w] = acc; acc += s_cnt[threadIdx.x][w]; }
+    for (int w = 0; w < nwaves; ++w) { s_off[threadIdx.x][w] = acc; acc += s_cnt[threadIdx.x][w]; }
   }
   if (threadIdx.x == 0) {
     int nw = 0;
     for (int c = 0; c < NCLASS - 1; ++c) nw += s_hist[c];
-    ws.n_work[g] = nw;   // the flagged-empty class sits at the end of the order
+    if (blockIdx.y == 0) ws.n_work[g] = nw;   // the flagged-empty class sits at the end of the order; one workgroup per group publishes
     // Split the heaviest blocks over four workgroups each?  It adds ~25 % work to those blocks and shortens them about
     // 3x.  A launch lasts at least as long as its longest block (per-block stamps at 64 frames @256^2: the blocks of
     // ~300 face boxes start at t = 0 and end with the kernel, 225 us, while the work spread over the wave slots comes to
     // 195 us), so a block is split when its cost exceeds `ratio` x the group's mean work per wave slot (512 slots per
     // XCD at 16 one-wave workgroups per CU): a whole small launch, the top few dozen blocks of a large one.
     // split_mode < 0: ratio = -split_mode / 4 (default -5: 1.25).
+    // (a function of the group's histogram alone: every workgroup of the group arrives at the same class)
     const int mid[NCLASS] = {290, 220, 180, 136, 96, 68, 46, 28, 10, 0};
     long total = 0;
     for (int c = 0; c < NCLASS; ++c) total += (long)s_hist[c] * mid[c];
@@ -301,36 +348,27 @@ __global__ __launch_bounds__(1024) void k_order(RasterWs ws, int N, int tt, int 
   }
   __syncthreads();
   const int split_slots = ws.split_slots, split_class = s_split;
-  // pass 2: scatter (order inside a class is arbitrary: results never depend on it)
+  // pass 2: scatter the workgroup's own entries (order inside a class is arbitrary: results never depend on it)
   int off[NCLASS];
 #pragma unroll
   for (int c = 0; c < NCLASS; ++c) off[c] = s_off[c][wv];
   const unsigned long long lt = (1ull << lane) - 1ull;
   int* ord = ws.order + (size_t)g * per;
-  m1 = m_first; bl1 = bl_first;
-  for (int it0 = 0; it0 < iters; it0 += OCH) {
-    int cst[OCH];
+  m1 = m_lo + (int)threadIdx.x / tt; bl1 = (int)threadIdx.x % tt;
+  for (int it = 0; it < own_iters; ++it) {
+    const int e = lo + it * (int)blockDim.x + (int)threadIdx.x;
+    const int cs = it == 0 ? cst_first : (e < hi ? ws.tile_cnt[(size_t)(m1 * G + g) * tt + bl1] : -1);
+    bl1 += blockDim.x;
+    while (bl1 >= tt) { bl1 -= tt; ++m1; }
+    const int cls = cs < 0 ? -1 : cost_class(cs);
 #pragma unroll
-    for (int u = 0; u < OCH; ++u) {
-      const int e = (it0 + u) * blockDim.x + threadIdx.x;
-      if (it0 == 0) cst[u] = cst0[u];
-      else cst[u] = (it0 + u < iters && e < per) ? ws.tile_cnt[(size_t)(m1 * G + g) * tt + bl1] : -1;
-      bl1 += blockDim.x;
-      while (bl1 >= tt) { bl1 -= tt; ++m1; }
-    }
-#pragma unroll
-    for (int u = 0; u < OCH; ++u) {
-      const int e = (it0 + u) * blockDim.x + threadIdx.x;
-      const int cls = cst[u] < 0 ? -1 : cost_class(cst[u]);
-#pragma unroll
-      for (int c = 0; c < NCLASS; ++c) {
-        const unsigned long long m = __ballot(cls == c);
-        if (cls == c) {
-          const int pos = off[c] + __popcll(m & lt);
-          ord[pos] = e | (c == NCLASS - 1 ? ENTRY_EMPTY : 0) | ((c <= split_class && pos < split_slots) ? ENTRY_SPLIT : 0);
-        }
-        off[c] += __popcll(m);
+    for (int c = 0; c < NCLASS; ++c) {
+      const unsigned long long mk = __ballot(cls == c);
+      if (cls == c) {
+        const int pos = off[c] + __popcll(mk & lt);
+        ord[pos] = e | (c == NCLASS - 1 ? ENTRY_EMPTY : 0) | ((c <= split_class && pos < split_slots) ? ENTRY_SPLIT : 0);
       }
+      off[c] += __popcll(mk);
     }
   }
 }
@@ -363,10 +401,17 @@ int launch_setup(const float* verts, const int64_t* faces, const float* cams, in
     default: hipLaunchKernelGGL(k_setup<16>, dim3(N, 16), dim3(TPB), lds, st, verts, faces, cams, V, F, H, offset_z, mode,
                                 margin, ws, vis, proj_xy); break;
   }
+  // one workgroup per mesh while that is at most ORDER_MAX_WGS workgroups: all of them are resident at once (two
+  // 1024-thread workgroups per CU), each loads the group's planes once, and the launch reads them W times from L2
+  // (8 MB at 64 frames @256^2, 33 MB at 128).  Larger batches: mpw meshes per workgroup, the same number of workgroups.
+  const int groups = (N & 7) == 0 ? 8 : 1, M = N / groups;
+  const int wmax = ORDER_MAX_WGS / groups < 1 ? 1 : ORDER_MAX_WGS / groups;   // workgroups per group
+  const int mpw = (M + wmax - 1) / wmax;
+  const dim3 order_grid(groups, (M + mpw - 1) / mpw);
   if (ws.slices > 4)
-    hipLaunchKernelGGL(k_order<true>, dim3((N & 7) == 0 ? 8 : 1), dim3(1024), 0, st, ws, N, blocks * blocks, H, tn.split);
+    hipLaunchKernelGGL(k_order<true>, order_grid, dim3(1024), 0, st, ws, N, blocks * blocks, H, tn.split, mpw);
   else
-    hipLaunchKernelGGL(k_order<false>, dim3((N & 7) == 0 ? 8 : 1), dim3(1024), 0, st, ws, N, blocks * blocks, H, tn.split);
+    hipLaunchKernelGGL(k_order<false>, order_grid, dim3(1024), 0, st, ws, N, blocks * blocks, H, tn.split, mpw);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
 }

@@ -546,6 +546,8 @@ int acfm_texture_cycle_backward(const float* textures, const float* scratch, con
  * replaces loss_utils.l1_loss / iou / iou_loss / edt_loss with reduce=False
  * (multiframe/nnutils/loss_utils.py:18-32, 72-77, 245-253) in one pass over the mask:
  *   out [N,4] = (mean|m-gt|, sum m*gt, sum (m+gt-m*gt), mean edt*m); gt / edt may be NULL.
+ * With HW % 4 == 0 edt is read only where the four mask values of an aligned group of four pixels are not all zero
+ * (edt*m is +0 elsewhere for finite edt: the same bits); a NaN or infinity in edt under such a group does not reach out[3].
  * ref_batch (here and in the losses below): the number of distinct references; prediction n is
  * compared with reference n % ref_batch (gt, edt [ref_batch,HW]).  The trainer scores G camera
  * hypotheses per frame against the frame's one ground truth (masks.repeat(G, 1, 1) at
@@ -577,7 +579,12 @@ int acfm_mask_losses_backward(const float* mask, const float* gt, const float* e
 /* ---- masked texture MSE ---------------------------------------------------------------
  * replaces the inline texture term of multiframe/main.py:655-662,
  * F.mse_loss(texture_pred * mask, imgs * mask, reduction='none').mean((1,2,3)):
- *   tex [N,3,HW], img [ref_batch,3,HW], mask [ref_batch,HW] f32 -> out [N]; backward -> grad_tex [N,3,HW]. */
+ *   tex [N,3,HW], img [ref_batch,3,HW], mask [ref_batch,HW] f32 -> out [N]; backward -> grad_tex [N,3,HW].
+ * The forward reads the mask first and tex / img only where it is not zero: with HW % 4 == 0 where the four mask
+ * values of an aligned group of four pixels are not all zero, else per pixel.  For finite tex and img the result is
+ * bit for bit the sum over every pixel ((t m - g m)^2 is +0 under m == 0).  A NaN or infinity in tex or img where
+ * the mask is zero does NOT reach the result unless a non-zero mask value shares its group of four, whereas
+ * F.mse_loss(tex * mask, img * mask) returns NaN for it.  acfm_tex_mse_backward reads every pixel. */
 int acfm_tex_mse(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,
                  float* out, void* stream);
 int acfm_tex_mse_ws(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,

@@ -1,0 +1,165 @@
+"""GPU: k_tex_mse reads the mask first and the colour planes only where the mask is not zero (acfm_tex_mse_ws behind
+ops.tex_mse / loss_utils.masked_texture_mse).  The result is what it was for finite inputs: against the float64 torch
+expression at the tolerance of tests/test_gpu_losses.py::test_masked_texture_mse, bit for bit against itself when the
+colours under a zero mask change, and exactly 0 for an all-zero mask.  Masks put single pixels on both sides of a
+16-byte piece (pixels 3 | 4) and of a 128-byte line (31 | 32)."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+# (N, RB, H, W): vector path; 80 px; scalar path (HW % 4 != 0); shared references; two workgroups of the narrow form
+# (2048 px each); the wide form (N * ceil(HW / 8192) >= 512)
+SHAPES = [(2, 2, 16, 16), (3, 3, 8, 10), (2, 2, 7, 9), (4, 2, 64, 64), (1, 1, 96, 96), (512, 512, 8, 8)]
+MASKS = ["zero", "one", "px0", "px3", "px4", "px31", "px32", "last", "checker", "blob"]
+TOL = dict(rtol=1e-5, atol=1e-8)      # tests/test_gpu_losses.py::test_masked_texture_mse
+GTOL = dict(rtol=1e-4, atol=1e-9)
+
+
+def _d():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def _mask(kind, RB, H, W, rng):
+    HW = H * W
+    m = np.zeros((RB, HW), np.float32)
+    if kind == "one":
+        m[:] = 1.0
+    elif kind.startswith("px"):
+        m[:, int(kind[2:])] = 1.0
+    elif kind == "last":
+        m[:, HW - 1] = 1.0
+    elif kind == "checker":
+        yy, xx = np.mgrid[:H, :W]
+        m[:] = ((yy + xx) & 1).astype(np.float32).reshape(-1)
+    elif kind == "blob":
+        yy, xx = np.mgrid[:H, :W]
+        r2 = ((yy - 0.4 * H) / (0.3 * H)) ** 2 + ((xx - 0.55 * W) / (0.3 * W)) ** 2
+        b = np.clip(1.2 - r2, 0.0, 1.0).astype(np.float32)      # fractional rim, 0 outside
+        b = np.broadcast_to(b.reshape(-1), (RB, HW)).copy()
+        z = np.flatnonzero(b[0] == 0)
+        b[:, z[::3]] = 1e-30                                      # non-zero: these pixels count
+        m = b
+    return m.reshape(RB, H, W)
+
+
+def _inputs(N, RB, H, W, kind, seed=0):
+    rng = np.random.default_rng(seed)
+    tex = rng.uniform(size=(N, 3, H, W)).astype(np.float32)
+    img = rng.uniform(size=(RB, 3, H, W)).astype(np.float32)
+    m = _mask(kind, RB, H, W, rng)
+    if kind == "blob":
+        # where the mask is 1e-30 a colour of 1e28 contributes (1e-2)^2: skipping those pixels would show
+        tiny = np.tile(m, (N // RB, 1, 1)) == np.float32(1e-30)
+        tex[:, 0][tiny] = 1e28
+    return tex, img, m
+
+
+def _ref(tex, img, m, N, RB):
+    idx = np.arange(N) % RB
+    t, i, k = (torch.tensor(x, dtype=torch.float64) for x in (tex, img[idx], m[idx]))
+    return ((t * k[:, None] - i * k[:, None]) ** 2).mean((1, 2, 3))
+
+
+def _run(tex, img, m):
+    from acfm_video_3d_reconstruction_amd import ops
+    d = _d()
+    return ops.tex_mse(torch.tensor(tex, device=d), torch.tensor(img, device=d), torch.tensor(m, device=d))
+
+
+@pytest.mark.parametrize("kind", MASKS)
+@pytest.mark.parametrize("N,RB,H,W", SHAPES)
+def test_tex_mse_against_float64(N, RB, H, W, kind):
+    tex, img, m = _inputs(N, RB, H, W, kind)
+    out = _run(tex, img, m).cpu()
+    assert out.shape == (N,)
+    if kind == "zero":
+        assert torch.equal(out, torch.zeros(N)), "an all-zero mask gives exactly 0"
+        return
+    ref = _ref(tex, img, m, N, RB)
+    assert float(ref.min()) > 0.0
+    np.testing.assert_allclose(out.numpy(), ref.numpy(), **TOL)
+
+
+@pytest.mark.parametrize("kind", ["px3", "px32", "checker", "blob", "zero"])
+@pytest.mark.parametrize("N,RB,H,W", SHAPES)
+def test_colours_under_a_zero_mask_do_not_change_a_bit(N, RB, H, W, kind):
+    tex, img, m = _inputs(N, RB, H, W, kind)
+    idx = np.arange(N) % RB
+    zt = np.broadcast_to((m[idx] == 0)[:, None], tex.shape)
+    zi = np.broadcast_to((m == 0)[:, None], img.shape)
+    rng = np.random.default_rng(7)
+    clean_t, clean_i = tex.copy(), img.copy()
+    clean_t[zt] = 0.0
+    clean_i[zi] = 0.0
+    pois_t, pois_i = tex.copy(), img.copy()
+    pois_t[zt] = np.where(rng.uniform(size=int(zt.sum())) < 0.5, -1e30, 1e30).astype(np.float32)
+    pois_i[zi] = np.where(rng.uniform(size=int(zi.sum())) < 0.5, -1e30, 1e30).astype(np.float32)
+    a = _run(clean_t, clean_i, m)
+    b = _run(pois_t, pois_i, m)
+    assert torch.isfinite(b).all()
+    assert torch.equal(a, b)
+    np.testing.assert_allclose(a.cpu().numpy(), _ref(clean_t, clean_i, m, N, RB).numpy(), **TOL)
+
+
+@pytest.mark.parametrize("N,RB,H,W", [(2, 2, 16, 16), (4, 2, 64, 64), (2, 2, 7, 9), (512, 512, 8, 8)])
+def test_non_finite_colours_where_the_mask_is_zero_are_not_read(N, RB, H, W):
+    """The documented contract (include/acfm_hip.h, acfm_tex_mse): colours are not read where the mask is zero -- on the
+    16-byte path (HW % 4 == 0) where all four mask values of an aligned group of four pixels are zero, else per pixel."""
+    rng = np.random.default_rng(3)
+    HW = H * W
+    tex = rng.uniform(size=(N, 3, HW)).astype(np.float32)
+    img = rng.uniform(size=(RB, 3, HW)).astype(np.float32)
+    m = np.zeros((RB, HW), np.float32)
+    m[:, HW // 2:] = rng.uniform(0.1, 1.0, size=(RB, HW - HW // 2)).astype(np.float32)
+    if HW % 4 == 0:
+        unread = np.repeat(~(m.reshape(RB, HW // 4, 4) != 0).any(-1), 4, axis=1)     # whole groups of four
+    else:
+        unread = m == 0
+    assert unread.any()
+    idx = np.arange(N) % RB
+    clean = tex.copy()
+    clean[np.broadcast_to(unread[idx][:, None], tex.shape)] = 0.0
+    bad = tex.copy()
+    bad[np.broadcast_to(unread[idx][:, None], tex.shape)] = np.nan
+    bad_i = img.copy()
+    bad_i[np.broadcast_to(unread[:, None], img.shape)] = np.inf
+    sh = lambda x, B: x.reshape(B, 3, H, W)
+    a = _run(sh(clean, N), sh(img, RB), m.reshape(RB, H, W))
+    b = _run(sh(bad, N), sh(bad_i, RB), m.reshape(RB, H, W))
+    assert torch.isfinite(b).all()
+    assert torch.equal(a, b)
+
+
+def test_gradient_is_unchanged():
+    """_TexMSE.backward (k_tex_mse_bwd, not edited) behind the forward's launcher, against float64 autograd."""
+    from acfm_video_3d_reconstruction_amd import ops
+    d = _d()
+    N, RB, H, W = 4, 2, 12, 10
+    tex, img, m = _inputs(N, RB, H, W, "blob", seed=2)
+    tex = np.minimum(tex, 1.0)
+    w = np.random.default_rng(4).uniform(size=N)
+    idx = np.arange(N) % RB
+    a = torch.tensor(tex, dtype=torch.float64, requires_grad=True)
+    k = torch.tensor(m[idx], dtype=torch.float64)[:, None]
+    ref = ((a * k - torch.tensor(img[idx], dtype=torch.float64) * k) ** 2).mean((1, 2, 3))
+    (ref * torch.tensor(w)).sum().backward()
+    b = torch.tensor(tex, device=d, requires_grad=True)
+    out = ops.tex_mse(b, torch.tensor(img, device=d), torch.tensor(m, device=d))
+    (out * torch.tensor(w, dtype=torch.float32, device=d)).sum().backward()
+    np.testing.assert_allclose(out.detach().cpu().numpy(), ref.detach().numpy(), **TOL)
+    np.testing.assert_allclose(b.grad.cpu().numpy(), a.grad.numpy(), **GTOL)
+
+
+@pytest.mark.parametrize("kind", ["px4095", "px4096", "px5000", "px8191", "px8192", "last", "blob"])
+def test_wide_form_fetches_the_upper_pieces(kind):
+    """8192 pixels per workgroup, eight 16-byte pieces per thread in two rounds of four: pixels from 4096 on are fetched
+    in the second round; 8192 is the first pixel of the second workgroup.  (256 meshes x two workgroups = the wide form)"""
+    N, RB, H, W = 256, 256, 96, 96
+    tex, img, m = _inputs(N, RB, H, W, kind)
+    out = _run(tex, img, m).cpu()
+    ref = _ref(tex, img, m, N, RB)
+    assert float(ref.min()) > 0.0
+    np.testing.assert_allclose(out.numpy(), ref.numpy(), **TOL)
