@@ -690,6 +690,39 @@ def correlation(f1, f2, max_displacement):
     return out
 
 
+# ------------------------------------------------------------------------------ deformable convolution
+def deform_conv2d(input, offset, weight, bias=None, shared_offset=False):
+    """torchvision's deform_conv2d in MaskFlownet's configuration (3x3, stride 1, padding 1, dilation 1, one group,
+    one offset group, no mask): input [N,Cin,H,W], offset [N,18,H,W] (channel 2t the row offset, 2t+1 the column
+    offset of tap t = 3 ky + kx), weight [Cout,Cin,3,3], bias [Cout] or None -> [N,Cout,H,W].  shared_offset: offset
+    is [N,2,H,W] and every tap reads it -- offset.repeat(1, 9, 1, 1), which is what MaskFlownet's unsqueeze(1) /
+    repeat_interleave(.., 9, 1) / view builds, without the copy and with the same bits.  Forward only (the flow
+    network is frozen in ACFM)."""
+    _lib.require_gpu(input, offset, weight, bias)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, offset, weight, bias)):
+        raise RuntimeError("deform_conv2d: forward only (frozen flow network); wrap the call in torch.no_grad()")
+    x, o, w = _f32c(input), _f32c(offset), _f32c(weight)
+    b = None if bias is None else _f32c(bias)
+    if x.dim() != 4:
+        raise ValueError("deform_conv2d: input must be [N,Cin,H,W], got %s" % (tuple(x.shape),))
+    N, Cin, H, W = x.shape
+    if w.dim() != 4 or w.shape[1] != Cin or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError("deform_conv2d: weight must be [Cout,%d,3,3], got %s" % (Cin, tuple(w.shape)))
+    Cout = w.shape[0]
+    och = 2 if shared_offset else 18
+    if tuple(o.shape) != (N, och, H, W):
+        raise ValueError("deform_conv2d: offset must be [%d,%d,%d,%d]%s, got %s"
+                         % (N, och, H, W, " (shared_offset)" if shared_offset else "", tuple(o.shape)))
+    if b is not None and tuple(b.shape) != (Cout,):
+        raise ValueError("deform_conv2d: bias must be [%d], got %s" % (Cout, tuple(b.shape)))
+    if min(N, Cin, H, W, Cout) < 1:
+        raise ValueError("deform_conv2d: empty input %s or weight %s" % (tuple(x.shape), tuple(w.shape)))
+    out = torch.empty((N, Cout, H, W), dtype=torch.float32, device=x.device)
+    _lib.call("acfm_deform_conv2d_forward", x.device, _lib.ptr(x), _lib.ptr(o), _lib.ptr(w), _lib.ptr(b), N, Cin, H, W,
+              Cout, 1 if shared_offset else 0, _lib.ptr(out))
+    return out
+
+
 # ------------------------------------------------------------------------------ lazy pix_to_face
 class LazyPixToFace(torch.Tensor):
     """`pix_to_face [N,H,W,K]` int64 as the reference's renderer returns it, with the K-1 planes nobody in the training

@@ -134,6 +134,22 @@ int acfm_deform_presolve_sums_f64(const float* delta, const float* grad_verts, i
 int acfm_correlation_forward(const float* f1, const float* f2, int N, int C, int H, int W, int md, float* out,
                              void* stream);
 
+/* ---- deformable convolution (forward only) ----------------------------------------------
+ * replaces torchvision.ops.deform_conv2d as MaskFlownet calls it (MaskFlownet.py:36-37, 488-492, 558-640: kernel 3x3,
+ * stride 1, padding 1, dilation 1, groups 1, one offset group, no mask), fp32:
+ *   input [N,Cin,H,W], offset [N,18,H,W], weight [Cout,Cin,3,3] (torchvision's layout, read as it is), bias [Cout] or
+ *   NULL -> out [N,Cout,H,W],
+ *   out[n,co,y,x] = bias[co] + sum_{ci,ky,kx} weight[co,ci,ky,kx] S(input[n,ci], y+ky-1+off[n,2t,y,x], x+kx-1+off[n,2t+1,y,x]),
+ *   t = 3 ky + kx; S(plane,h,w) = 0 for h <= -1, h >= H, w <= -1 or w >= W, else the bilinear interpolation of the four
+ *   neighbours with those outside the map counted as 0.
+ * shared_offset != 0: offset is [N,2,H,W] and every tap reads its channels 0 (rows) and 1 (columns): the result of
+ * offset.repeat(1, 9, 1, 1) (MaskFlownet's unsqueeze(1), repeat_interleave(.., 9, 1), view) handed to the 18-channel
+ * form, bit for bit, without that copy.
+ * Cin, Cout >= 1 arbitrary.  The columns are never written to device memory and nothing is added atomically: results
+ * are bit-reproducible.  The flow network is frozen in ACFM: no backward. */
+int acfm_deform_conv2d_forward(const float* input, const float* offset, const float* weight, const float* bias, int N,
+                               int Cin, int H, int W, int Cout, int shared_offset, float* out, void* stream);
+
 /* ---- optical-flow loss -----------------------------------------------------------------
  * replaces the tail of loss_utils.optical_flow_loss (multiframe/nnutils/loss_utils.py:445-474):
  *   proj [B*T,V,3] projected vertices (proj_fn output, x/y in [-1,1]), flows [B*T,H,W,2] GT flow
