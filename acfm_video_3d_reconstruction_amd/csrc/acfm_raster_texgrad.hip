@@ -23,7 +23,9 @@ __global__ void k_tex_bwd(const float* __restrict__ grad_imgs, const int32_t* __
 // Gather form of the same gradient, one wave per four (atlas, face) slots: for each it visits the pixels of the
 // face's box in every mesh that samples this atlas (the G hypotheses of a frame), adds the
 // gradients of the pixels whose texel belongs to the face into 3 R^2 LDS accumulators and stores
-// the face's texels -- zeros included -- with plain coalesced stores.  No global atomics (agent-
+// the face's texels -- zeros included -- with plain coalesced stores.  Per mesh a wave makes two load round
+// trips: the four flags and boxes together, then -- the four boxes as one list of (face, pixel) items, 64 U
+// items per round -- the texel indices and gradient operands of a round's items together.  No global atomics (agent-
 // scope float atomics execute at the memory side on this multi-XCD part: 2 M of them took 87 us)
 // and no zero fill of the 35 MB gradient.  Needs the face boxes of the forward's workspace.
 // i / w and i % w for 0 <= i < 2^23, 0 < w < 2^12 without the ~35-instruction integer division
@@ -34,9 +36,10 @@ __device__ __forceinline__ void divmod_small(int i, int w, float rw, int& q, int
   if (r >= w) { ++q; r -= w; }
 }
 constexpr int TEXG_MAX_R = 8;
-constexpr int TEXG_FPW = 4;      // faces per wave: their boxes, texel indices and gradients are loaded side by side
-constexpr int TEXG_U = 2;        // big boxes: 64 U pixels per round, all their loads in flight together
-constexpr int TEXG_WAVES = 8;    // waves per SIMD (U = 2 at 8 waves: 39.8 us per launch; U = 4 at 6 waves 41.4; U = 8 at 5 waves -- 92 VGPRs -- 45.2)
+// (us per launch below: the fused-MSE form on the 64-frame bird launch, by events; profiles/r06_atlas_grad_ab.txt)
+constexpr int TEXG_FPW = 4;      // faces per wave: their box pixels form ONE list that the wave walks (4: 38.1 us; 8: 40.2; 2: 45)
+constexpr int TEXG_U = 2;        // 64 U items of the list per round, all their loads in flight together (U = 1: 39.5 us, 2: 38.4, 3: 38.6, 4: 38.8, 8 -- spills -- 76)
+constexpr int TEXG_WAVES = 8;    // waves per SIMD: a wave's load chain is hidden by occupancy, not by deeper unrolling
 // Upstream gradient of the rendered image: given ([N,3,H,H]) or, for the fused texture render + masked MSE, formed
 // on the fly from the rendered image, the reference image and mask and the per-mesh gradient of the loss --
 // k_tex_mse_bwd's expression: w (tex m - img m) m with w = go[n] 2 / (3 HW).
@@ -49,62 +52,102 @@ struct TexGrad {
   int rb;
   int h16;
 };
-struct TexGradN {            // the same for one mesh n
-  const float* g;
-  const void *im, *ri, *rm;
-  size_t io, ro, mo;
+// element p (< H^2 <= 2^24) of a plane whose base is wave-uniform: a 32-bit byte offset, so that every load of a pixel
+// shares one offset register (scalar base + vector offset addressing)
+__device__ __forceinline__ float ld_plane(const char* base, unsigned p, int h16) {
+  return h16 ? (float)*reinterpret_cast<const half_t*>(base + p * 2u) : *reinterpret_cast<const float*>(base + p * 4u);
+}
+enum { TEXG_GIVEN = 0, TEXG_MSE_F32 = 1, TEXG_MSE_F16 = 2 };   // the kernel's three forms: one instantiation each
+struct TexGradN {            // the same for one mesh n: the planes' bases
+  const char *g0, *g1, *g2;            // given gradient (float), or null
+  const char *rm, *im0, *im1, *im2, *ri0, *ri1, *ri2;
   float w;
-  size_t HW;
-  int h16;
-  __device__ __forceinline__ void load(size_t p, float& r, float& gg, float& b) const {
-    if (g) { r = g[p]; gg = g[HW + p]; b = g[2 * HW + p]; return; }
-    const float mk = ld_real(rm, mo + p, h16);
-    r = w * (ld_real(im, io + p, h16) * mk - ld_real(ri, ro + p, h16) * mk) * mk;
-    gg = w * (ld_real(im, io + HW + p, h16) * mk - ld_real(ri, ro + HW + p, h16) * mk) * mk;
-    b = w * (ld_real(im, io + 2 * HW + p, h16) * mk - ld_real(ri, ro + 2 * HW + p, h16) * mk) * mk;
+  // The operands of pixel p as loaded (fetch) and the gradient formed from them (grad): two steps, so that a wave
+  // can request the operands of many pixels before it waits for the first.
+  template <int MODE> struct Raw { float v[MODE == TEXG_GIVEN ? 3 : 7]; };   // rgb (image or given gradient); rgb of the reference, mask
+  template <int MODE>
+  __device__ __forceinline__ void fetch(unsigned p, Raw<MODE>& x) const {
+    if (MODE == TEXG_GIVEN) { x.v[0] = ld_plane(g0, p, 0); x.v[1] = ld_plane(g1, p, 0); x.v[2] = ld_plane(g2, p, 0); return; }
+    constexpr int h16 = MODE == TEXG_MSE_F16;
+    x.v[0] = ld_plane(im0, p, h16); x.v[1] = ld_plane(im1, p, h16); x.v[2] = ld_plane(im2, p, h16);
+    // (MODE ? k : 0: a constant index inside the given form's three floats, on lines that form never reaches)
+    x.v[MODE ? 3 : 0] = ld_plane(ri0, p, h16); x.v[MODE ? 4 : 0] = ld_plane(ri1, p, h16); x.v[MODE ? 5 : 0] = ld_plane(ri2, p, h16);
+    x.v[MODE ? 6 : 0] = ld_plane(rm, p, h16);
+  }
+  template <int MODE>
+  __device__ __forceinline__ void grad(const Raw<MODE>& x, float& r, float& gg, float& b) const {
+    if (MODE == TEXG_GIVEN) { r = x.v[0]; gg = x.v[1]; b = x.v[2]; return; }
+    const float mk = x.v[MODE ? 6 : 0];
+    r = w * (x.v[0] * mk - x.v[MODE ? 3 : 0] * mk) * mk;
+    gg = w * (x.v[1] * mk - x.v[MODE ? 4 : 0] * mk) * mk;
+    b = w * (x.v[2] * mk - x.v[MODE ? 5 : 0] * mk) * mk;
   }
 };
-__device__ __forceinline__ TexGradN tex_grad_of(const TexGrad& tg, int n, size_t HW) {
+__device__ __forceinline__ TexGradN tex_grad_of(const TexGrad& tg, int n, size_t HW, float gon) {   // gon = tg.go[n]
   TexGradN t = {};
-  t.HW = HW;
-  if (tg.grad_imgs) { t.g = tg.grad_imgs + (size_t)n * 3 * HW; return t; }
-  const size_t rn = (size_t)(n % tg.rb);
-  t.im = tg.imgs; t.ri = tg.timg; t.rm = tg.tmask; t.h16 = tg.h16;
-  t.io = (size_t)n * 3 * HW; t.ro = rn * 3 * HW; t.mo = rn * HW;
-  t.w = tg.go[n] * 2.0f / (3.0f * (float)HW);
+  if (tg.grad_imgs) {
+    t.g0 = reinterpret_cast<const char*>(tg.grad_imgs + (size_t)n * 3 * HW);
+    t.g1 = t.g0 + 4 * HW; t.g2 = t.g1 + 4 * HW;
+    return t;
+  }
+  const size_t rn = (size_t)(n % tg.rb), es = tg.h16 ? 2 : 4;
+  t.rm = reinterpret_cast<const char*>(tg.tmask) + es * rn * HW;
+  t.im0 = reinterpret_cast<const char*>(tg.imgs) + es * (size_t)n * 3 * HW;
+  t.im1 = t.im0 + es * HW; t.im2 = t.im1 + es * HW;
+  t.ri0 = reinterpret_cast<const char*>(tg.timg) + es * rn * 3 * HW;
+  t.ri1 = t.ri0 + es * HW; t.ri2 = t.ri1 + es * HW;
+  t.w = gon * 2.0f / (3.0f * (float)HW);
   return t;
 }
+// Dynamic LDS: [4 waves][FPW][3 R^2] floats (sized by the launch's R).  place: workgroup b belongs to XCD group b % 8
+// and takes the atlases a % 8 == b % 8, whose texture outputs that XCD has just written (needs NA % 8 == 0); any
+// mapping gives the same result.
+template <int MODE>
 __global__ __launch_bounds__(256, TEXG_WAVES) void k_tex_bwd_faces(RasterWs ws, TexGrad tgrad,
                                                        const int32_t* __restrict__ tidx, int N, int F, int H,
-                                                       int R, int NA, float box_shrink,
+                                                       int R, int NA, int place, float box_shrink,
                                                        float* __restrict__ grad_atlas) {
-  __shared__ float s_acc[4][TEXG_FPW][3 * TEXG_MAX_R * TEXG_MAX_R];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // Wave q of the launch takes the faces q, q + Q, q + 2Q, q + 3Q of one atlas (Q = ceil(F / FPW)):
-  // neighbouring faces of a mesh tend to be large together, and a wave walks its faces' boxes one
-  // after the other, so they are dealt to different waves.
+  extern __shared__ float s_acc[];
+  // (the wave's number through readfirstlane: everything derived from it -- atlas, faces, plane bases, box
+  // parameters -- is then kept in scalar registers)
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  // A wave takes the faces f0, f0 + Q, .., f0 + (FPW - 1) Q of one atlas (Q = ceil(F / FPW)): neighbouring faces
+  // of a mesh tend to be large together, so they are dealt to different waves.
   const int Q = (F + TEXG_FPW - 1) / TEXG_FPW;
-  const long long wq = (long long)blockIdx.x * 4 + wv;
-  if (wq >= (long long)NA * Q) return;                       // (whole wave; no workgroup barriers below)
-  const int a = (int)(wq / Q), f0 = (int)(wq % Q);
+  int a, f0;
+  if (place) {
+    const long long wg = (long long)(blockIdx.x >> 3) * 4 + wv;
+    if (wg >= (long long)(NA >> 3) * Q) return;              // (whole wave; no workgroup barriers below)
+    a = (int)(blockIdx.x & 7) + 8 * (int)(wg / Q); f0 = (int)(wg % Q);
+  } else {
+    const long long wq = (long long)blockIdx.x * 4 + wv;
+    if (wq >= (long long)NA * Q) return;
+    a = (int)(wq / Q); f0 = (int)(wq % Q);
+  }
   const int R2 = R * R, n3 = 3 * R2;
-  float (*acc)[3 * TEXG_MAX_R * TEXG_MAX_R] = s_acc[wv];
-#pragma unroll
-  for (int k = 0; k < TEXG_FPW; ++k)
-    for (int i = lane; i < n3; i += 64) acc[k][i] = 0.f;
+  float* acc = s_acc + wv * TEXG_FPW * n3;
+  for (int i = lane; i < TEXG_FPW * n3; i += 64) acc[i] = 0.f;
   wave_lds_sync();
   const size_t HW = (size_t)H * H;
   const float hf = (float)H;
   // lane k < FPW looks after face f0 + k Q
   const int my_f = f0 + (lane < TEXG_FPW ? lane : 0) * Q;
   const bool my_live = lane < TEXG_FPW && my_f < F;
+  const int base0 = (a * F + f0) * R2;                       // first texel index of face f0 (< 2^31: host check)
   const int G = N / NA;
   for (int g = 0; g < G; ++g) {
     // the FPW boxes (mesh a + g NA), one per lane, turned into pixel ranges (k_setup's formula, one pixel of slack)
     int xa = 0, ya = 0, w = 1, cnt = 0;
     const int n = a + g * NA;
-    if (my_live && ws.fvis[(size_t)n * F + my_f]) {          // (a face no pixel shows has no gradient: zeros)
-      float4 b = ws.rec[(size_t)n * F + my_f].box;
+    // Flag, box and (fused form) the mesh's loss gradient together: one round trip.  Lanes without a face read face
+    // f0's, which exists.
+    const size_t fi = (size_t)n * F + (my_live ? my_f : f0);
+    int visi = ws.fvis[fi];
+    float4 b = ws.rec[fi].box;
+    float gon = MODE == TEXG_GIVEN ? 0.f : tgrad.go[n];
+    asm volatile("" : "+v"(visi), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w), "+v"(gon));   // (all issued before the first is waited for)
+    if (!my_live) visi = 0;
+    if (visi) {                                               // (a face no pixel shows has no gradient: zeros)
       b.x += box_shrink; b.y -= box_shrink; b.z += box_shrink; b.w -= box_shrink;
       if (b.x <= b.y && b.z <= b.w) {                        // not a degenerate face (inf, -inf, ..) or an emptied box
         // pixel range of the box: k_setup's formula with one pixel of slack, then tightened to the
@@ -123,63 +166,53 @@ __global__ __launch_bounds__(256, TEXG_WAVES) void k_tex_bwd_faces(RasterWs ws, 
         }
       }
     }
-    const int32_t* tn = tidx + (size_t)n * HW;
-    const TexGradN gn = tex_grad_of(tgrad, n, HW);
-    int cmax = 0;
-    int t[TEXG_FPW];
-    size_t pp[TEXG_FPW];
+    const char* tn = reinterpret_cast<const char*>(tidx + (size_t)n * HW);
+    const TexGradN gn = tex_grad_of(tgrad, n, HW, gon);
+    // One list of the wave's (face k, pixel i) items, faces in order and the pixels of a face in order: item j belongs
+    // to the face k with pre[k] <= j < pre[k + 1].  Every texel so receives its addends in pixel order.
+    int sp0[TEXG_FPW], sw[TEXG_FPW], pre[TEXG_FPW + 1];
+    pre[0] = 0;
 #pragma unroll
-    for (int k = 0; k < TEXG_FPW; ++k) {                     // all texel-index loads first ...
-      const int kxa = __shfl(xa, k, 64), kya = __shfl(ya, k, 64), kw = __shfl(w, k, 64), kc = __shfl(cnt, k, 64);
-      const int kbase = (a * F + f0 + k * Q) * R2;           // first texel index of the face (< 2^31: host check)
-      cmax = max(cmax, kc);
-      t[k] = -1;
-      pp[k] = 0;
-      if (lane < kc) {
+    for (int k = 0; k < TEXG_FPW; ++k) {
+      sp0[k] = __builtin_amdgcn_readlane(ya, k) * H + __builtin_amdgcn_readlane(xa, k);   // first pixel of the box
+      sw[k] = __builtin_amdgcn_readlane(w, k);
+      pre[k + 1] = pre[k] + __builtin_amdgcn_readlane(cnt, k);
+    }
+    const int total = pre[TEXG_FPW];
+    for (int j0 = 0; j0 < total; j0 += 64 * TEXG_U) {
+      int tr[TEXG_U], kq[TEXG_U];
+      TexGradN::Raw<MODE> raw[TEXG_U];
+#pragma unroll
+      for (int u = 0; u < TEXG_U; ++u) {
+        const int j = j0 + 64 * u + lane;
+        int kp0 = sp0[0], kw = sw[0], i = j;
+        kq[u] = 0;
+#pragma unroll
+        for (int q = 1; q < TEXG_FPW; ++q) {
+          const bool ge = j >= pre[q];
+          kp0 = ge ? sp0[q] : kp0; kw = ge ? sw[q] : kw; i = ge ? j - pre[q] : i; kq[u] = ge ? q : kq[u];
+        }
         int qy, qx;
-        divmod_small(lane, kw, __builtin_amdgcn_rcpf((float)kw), qy, qx);
-        pp[k] = (size_t)(kya + qy) * H + (kxa + qx);
-        t[k] = tn[pp[k]] - kbase;
+        divmod_small(i, kw, __builtin_amdgcn_rcpf((float)kw), qy, qx);
+        const unsigned p = (unsigned)(kp0 + qy * H + qx);
+        tr[u] = -1;
+        raw[u] = {};
+        if (j < total) {      // texel index and gradient operands together, unconditionally: one round trip per round
+          tr[u] = *reinterpret_cast<const int32_t*>(tn + p * 4u);
+          gn.template fetch<MODE>(p, raw[u]);
+        }
       }
-    }
 #pragma unroll
-    for (int k = 0; k < TEXG_FPW; ++k) {                     // ... then the gradients of the pixels that belong to the face
-      if (t[k] >= 0 && t[k] < R2) {
-        // d rgb / d texel = wnum / (wnum + delta) = 1 in fp32 (wnum >= 0.5, delta = 1e-10)
-        float r, gg, bb;
-        gn.load(pp[k], r, gg, bb);
-        atomicAdd(&acc[k][3 * t[k] + 0], r);
-        atomicAdd(&acc[k][3 * t[k] + 1], gg);
-        atomicAdd(&acc[k][3 * t[k] + 2], bb);
-      }
-    }
-    if (cmax > 64) {   // boxes of more than 64 pixels (a third of the bird's): the rest face by face, 64 U pixels per round
-      for (int k = 0; k < TEXG_FPW; ++k) {
-        const int kxa = __shfl(xa, k, 64), kya = __shfl(ya, k, 64), kw = __shfl(w, k, 64), kc = __shfl(cnt, k, 64);
-        const int kbase = (a * F + f0 + k * Q) * R2;
-        const float rw = __builtin_amdgcn_rcpf((float)kw);
-        for (int i0 = 64 + lane; i0 < kc + lane; i0 += 64 * TEXG_U) {   // (i0 - lane is wave-uniform)
-          int tt[TEXG_U];
-          float cr[TEXG_U], cg[TEXG_U], cb[TEXG_U];
-#pragma unroll
-          for (int u = 0; u < TEXG_U; ++u) {
-            const int i = i0 + 64 * u;
-            tt[u] = -1; cr[u] = 0.f; cg[u] = 0.f; cb[u] = 0.f;
-            if (i < kc) {
-              int qy, qx;
-              divmod_small(i, kw, rw, qy, qx);
-              const size_t p = (size_t)(kya + qy) * H + (kxa + qx);
-              tt[u] = tn[p] - kbase;
-              gn.load(p, cr[u], cg[u], cb[u]);                              // unconditionally: one round trip per round
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < TEXG_U; ++u)
-            if (tt[u] >= 0 && tt[u] < R2) {
-              atomicAdd(&acc[k][3 * tt[u] + 0], cr[u]);
-              atomicAdd(&acc[k][3 * tt[u] + 1], cg[u]);
-              atomicAdd(&acc[k][3 * tt[u] + 2], cb[u]);
-            }
+      for (int u = 0; u < TEXG_U; ++u) {
+        const int t = tr[u] - (base0 + kq[u] * (Q * R2));    // texel of the item's own face?  (-1: no texel, or no item)
+        if (t >= 0 && t < R2) {
+          // d rgb / d texel = wnum / (wnum + delta) = 1 in fp32 (wnum >= 0.5, delta = 1e-10)
+          float cr, cg, cb;
+          gn.template grad<MODE>(raw[u], cr, cg, cb);
+          float* o = acc + kq[u] * n3 + 3 * t;
+          atomicAdd(o + 0, cr);
+          atomicAdd(o + 1, cg);
+          atomicAdd(o + 2, cb);
         }
       }
     }
@@ -189,7 +222,7 @@ __global__ __launch_bounds__(256, TEXG_WAVES) void k_tex_bwd_faces(RasterWs ws, 
   for (int k = 0; k < TEXG_FPW; ++k) {
     if (f0 + k * Q >= F) break;
     float* o = grad_atlas + (size_t)(a * F + f0 + k * Q) * n3;
-    for (int i = lane; i < n3; i += 64) o[i] = acc[k][i];
+    for (int i = lane; i < n3; i += 64) o[i] = acc[k * n3 + i];
   }
 }
 
@@ -225,10 +258,15 @@ static int tex_backward_faces_impl(const TexGrad& tgrad, const int32_t* texel_id
   const RasterWs ws = carve_ws(const_cast<void*>(wsp), N, V, F, H);
   if (ws.bytes > ws_bytes) return ACFM_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const size_t waves = (size_t)atlas_batch * ((F + TEXG_FPW - 1) / TEXG_FPW);
+  const size_t Q = (size_t)(F + TEXG_FPW - 1) / TEXG_FPW;
+  const int place = atlas_batch % 8 == 0;    // per XCD group its own atlases, as the raster kernels deal meshes
+  const size_t wgs = place ? 8 * (((size_t)(atlas_batch / 8) * Q + 3) / 4) : ((size_t)atlas_batch * Q + 3) / 4;
+  const size_t lds = sizeof(float) * 4 * TEXG_FPW * 3 * (size_t)R * R;
   ProfScope ps(ACFM_PROF_TEX_BWD, st);
-  hipLaunchKernelGGL(k_tex_bwd_faces, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, ws, tgrad, texel_idx,
-                     N, F, H, R, atlas_batch, ws_blur > 0.f ? sqrtf(ws_blur) * (1.0f - 1e-5f) : 0.f, grad_atlas);
+  const float shrink = ws_blur > 0.f ? sqrtf(ws_blur) * (1.0f - 1e-5f) : 0.f;
+  auto kern = tgrad.grad_imgs ? k_tex_bwd_faces<TEXG_GIVEN> : tgrad.h16 ? k_tex_bwd_faces<TEXG_MSE_F16> : k_tex_bwd_faces<TEXG_MSE_F32>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(256), lds, st, ws, tgrad, texel_idx, N, F, H, R, atlas_batch,
+                     place, shrink, grad_atlas);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
 }
