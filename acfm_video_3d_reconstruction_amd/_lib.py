@@ -126,6 +126,13 @@ SIGNATURES = {
     "acfm_uv_atlas_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "acfm_uv_atlas_taps": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "acfm_uv_atlas_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_lpips_input_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_lpips_input_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_lpips_layer_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "acfm_lpips_layer_backward": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_lpips_mask_weights": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "acfm_lpips_masked_mean_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "acfm_lpips_masked_mean_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
 }
 
 _ERR = {1: "ACFM_E_BADARG (shape/parameter outside what the kernels support)",

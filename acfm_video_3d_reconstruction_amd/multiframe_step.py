@@ -181,8 +181,10 @@ class MultiframeStep(nn.Module):
 
     # ------------------------------------------------------------------ main.py:523-765
     def forward(self, batch, delta_v_res, textures=None, imgs=None, detach_camera=False, drop_deform=False,
-                predicted_camera=None, exchange=None):
+                predicted_camera=None, exchange=None, perceptual=None):
         """delta_v_res [N,K_h,3]: handle offsets predicted by the (out-of-scope) encoder head;
+        perceptual (optional, off by default): a perceptual.PerceptualTextureLoss; with it the texture branch adds the
+        reference's two LPIPS terms, 0.5 each (main.py:647-654), beside the two MSE terms; every other term keeps its bits;
         predicted_camera [N,7] (optional): output of its camera head, pulled towards the most
         probable hypothesis (main.py:753-762).  Returns (total_loss, dict of the reference's named terms)."""
         o = self.opts
@@ -257,8 +259,8 @@ class MultiframeStep(nn.Module):
             tl.append(kp); tw.append(o.kp_loss_wt); tg.append(-1); ta.append(0.0)
         have_tex = textures is not None and imgs is not None
         if have_tex:
-            # texture branch on detached geometry, original + mirrored camera (main.py:627-636, 655-662;
-            # the LPIPS part of the reference's texture loss is out of scope)
+            # texture branch on detached geometry, original + mirrored camera (main.py:627-636, 655-662); the LPIPS
+            # part of the reference's texture loss (main.py:647-654) is added below when `perceptual` is given
             tex = textures    # [N,...] shared by the G hypotheses of a frame: the op indexes n % N (= repeat(G))
             tex_pred, _, _ = self.tex_renderer(pred_v.detach(), faces, cam, textures=tex)
             # main.py:97-110 (mirror_sample) without flipping the rendered masks nobody reads
@@ -272,6 +274,14 @@ class MultiframeStep(nn.Module):
             tl += [loss_utils.masked_texture_mse(tex_pred, imgs, batch["masks"]),
                    loss_utils.masked_texture_mse(tex_pred_f, imgs_f, masks_f)]          # mse = their mean
             tw += [0.5 * o.tex_loss_wt] * 2; tg += [1, 1]; ta += [0.5, 0.5]
+            if perceptual is not None:
+                # one term = 0.5 LPIPS + 0.5 LPIPS(flipped), [G N]; images and masks go in once per frame (batch N)
+                lp = 0.5 * perceptual(tex_pred, imgs, None, batch["masks"], reduce=False) \
+                    + 0.5 * perceptual(tex_pred_f, imgs_f, None, masks_f, reduce=False)
+                if len(tl) >= 8:
+                    raise ValueError("hypothesis_total takes 8 terms; %d are active besides the perceptual one" % len(tl))
+                lp_at = len(tl)
+                tl.append(lp); tw.append(o.tex_loss_wt); tg.append(-1); ta.append(0.0)
             cycle = texture_cycle_loss(textures, T)              # main.py:705-711, added at :749
         weighted, total, probs, aux, means = harness.hypothesis_total(tl, tw, G, N, tg, ta)
         cam_loss = means[1]
@@ -280,6 +290,8 @@ class MultiframeStep(nn.Module):
         if have_tex:
             terms["tex_mse"] = means[3]
             terms["tex_mse_per_hyp"] = aux[1]
+            if perceptual is not None:
+                terms["tex_lpips"] = means[4 + lp_at]
         if selected is not None:                   # probabilities go back to the embeddings they came from (:737-742)
             with torch.no_grad():
                 fi = batch["frames_idx"]

@@ -246,12 +246,28 @@ def kp_l2_loss(kp_pred, kp_gt, reduction='mean'):
 
 class PerceptualTextureLoss_v2(object):
     """loss_utils.py:359-383: LPIPS (AlexNet features, spatial map) between the masked rendered texture and the masked
-    image, times the ground-truth mask, mean over the pixels.  The network is the third-party `lpips` package, kept as
-    the torch module it is and imported when the loss is constructed: without the package the
-    constructor raises an ImportError naming it, with it predictor.py:103-108 and main.py:333-335 construct and call
-    this class unchanged.  The module lives on the GPU the process uses (the reference: `.cuda()` + nn.DataParallel)."""
+    image, times the ground-truth mask, mean over the pixels.
+    weights=None: the network is the third-party `lpips` package, imported when the loss is constructed: without the
+    package the constructor raises an ImportError naming it, with it predictor.py:103-108 and main.py:333-335 construct
+    and call this class unchanged.  The module lives on the GPU the process uses (the reference: `.cuda()` +
+    nn.DataParallel).
+    weights=<state dict or local path> (not in the reference): the same loss from this package's own kernels
+    (perceptual.PerceptualTextureLoss) -- nothing is imported or fetched; AlexNet's weights under torchvision's or lpips's
+    names (perceptual.feature_state_dict), lpips_f=True also needs lpips's lin weights in the same state dict.  Then
+    img_gt / mask_gt may have batch N/G (once per frame), and prepare / against are available."""
 
-    def __init__(self, net='alex', lpips_f=False):
+    def __init__(self, net='alex', lpips_f=False, weights=None):
+        self.native = None
+        if weights is not None:
+            from .. import perceptual
+            if net != 'alex':
+                raise ValueError("PerceptualTextureLoss_v2(weights=...) builds AlexNet only, got net=%r" % (net,))
+            sd = perceptual._load_state(weights)
+            self.native = perceptual.PerceptualTextureLoss(perceptual.AlexFeatures(sd),
+                                                           lin=perceptual.lin_weights(sd) if lpips_f else None)
+            if torch.cuda.is_available():
+                self.native.cuda()
+            return
         try:
             import lpips
         except ImportError as exc:
@@ -263,8 +279,16 @@ class PerceptualTextureLoss_v2(object):
             fn = fn.cuda()
         self.loss_fn_alex = nn.DataParallel(fn)
 
+    def prepare(self, img_gt, mask_gt):
+        return self.native.prepare(img_gt, mask_gt)
+
+    def against(self, prepared, img_pred, reduce=True):
+        return self.native.against(prepared, img_pred, reduce=reduce)
+
     def __call__(self, img_pred, img_gt, mask_pred, mask_gt, reduce=True):
         """img_pred, img_gt [B,3,H,W]; mask_pred (unused, as in the reference), mask_gt [B,H,W] -> scalar or [B]."""
+        if self.native is not None:
+            return self.native(img_pred, img_gt, mask_pred, mask_gt, reduce=reduce)
         mask_gt = mask_gt.unsqueeze(1)
         pred = 2 * (img_pred * mask_gt) - 1
         target = 2 * (img_gt * mask_gt) - 1

@@ -733,6 +733,42 @@ int acfm_uv_atlas_backward(const float* grad_atlas, const float* atlas, const fl
                            const int32_t* pix_taps, int n_entries, int B, int Hu, int Wu, int Fp, int T, int nsym,
                            float* grad_uvimage, void* stream);
 
+/* ---- perceptual texture loss: the tail of LPIPS (multiframe/nnutils/loss_utils.py:359-383) --------
+ * replaces everything lpips.LPIPS(net='alex', lpips=False, spatial=True) and its caller do around AlexNet's five
+ * convolutions (which stay with the framework).  float32, contiguous NCHW.  The definition is restated in DESIGN.md
+ * ("Perceptual texture loss"); it could not be checked against the lpips package.
+ * References broadcast: prediction n reads reference n mod Nr, N % Nr == 0 (Nr = N / G: once per frame).
+ * acfm_lpips_input_forward: x[n,c] = ((2 (img[n,c] m) - 1) - shift_c) / scale_c, m = mask[n mod Nr] [H,W],
+ *   shift = (-.030, -.088, -.188), scale = (.458, .448, .450): the bits of that chain of operations.  img is not
+ *   read where m == 0 (a NaN there does not propagate, unlike img * 0).
+ * acfm_lpips_input_backward: grad_img = ((grad_x / scale_c) 2) m; grad_x is not read where m == 0.
+ * acfm_lpips_layer_forward: fa [N,C,hw], fb [Nr,C,hw], lin [C] or NULL (= 1) ->
+ *   d[n * d_row_stride + p] = sum_c lin_c (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2, |.| over the channels of
+ *   the pixel.  d_row_stride >= hw: d may be a column block of a wider [N,P] buffer.  C, hw >= 1 arbitrary.
+ * acfm_lpips_layer_backward: grad_fa [N,C,hw] from grad_d (same addressing as d), every element written:
+ *   q_c = 2 lin_c (u_c - v_c) g,  grad_a_c = q_c / (|a| + eps) - a_c (sum_k q_k a_k) / (|a| (|a| + eps)^2), the second
+ *   term 0 where |a| = 0 (there u = 0 by definition and the gradient stays finite; lpips's autograd gives NaN).
+ *   d is symmetric: with Nr == N the reference's gradient is the same call with fa and fb exchanged.
+ * acfm_lpips_mask_weights: mask [Nr,H,W]; layer_hw = n_layers (<= 8) pairs (h_l, w_l) in HOST memory, read before
+ *   the call returns -> M [Nr,P], P = sum h_l w_l, layer l at column sum_{k<l} h_k w_k:
+ *   M_l = U_l^T (mask / (H W)), U_l = bilinear upsampling (h_l,w_l) -> (H,W) with align_corners=False as PyTorch
+ *   defines it.  Then mean_{H,W}(mask sum_l U_l d_l) = sum_p d[p] M[p].  One launch, every element written.
+ * acfm_lpips_masked_mean_forward: loss[n] = sum_p d[n,p] M[n mod Nr,p], d [N,P]; written, never accumulated.
+ * acfm_lpips_masked_mean_backward: grad_d[n,p] = grad_loss[n] M[n mod Nr,p].
+ * No float atomics, fixed summation orders (bit-reproducible), nothing allocated: every call can be captured. */
+int acfm_lpips_input_forward(const float* img, const float* mask, int N, int Nr, int H, int W, float* x, void* stream);
+int acfm_lpips_input_backward(const float* grad_x, const float* mask, int N, int Nr, int H, int W, float* grad_img,
+                              void* stream);
+int acfm_lpips_layer_forward(const float* fa, const float* fb, const float* lin, int N, int Nr, int C, int hw, float* d,
+                             size_t d_row_stride, void* stream);
+int acfm_lpips_layer_backward(const float* fa, const float* fb, const float* lin, const float* grad_d,
+                              size_t grad_d_row_stride, int N, int Nr, int C, int hw, float* grad_fa, void* stream);
+int acfm_lpips_mask_weights(const float* mask, int Nr, int H, int W, const int32_t* layer_hw, int n_layers, float* M,
+                            void* stream);
+int acfm_lpips_masked_mean_forward(const float* d, const float* M, int N, int Nr, int P, float* loss, void* stream);
+int acfm_lpips_masked_mean_backward(const float* grad_loss, const float* M, int N, int Nr, int P, float* grad_d,
+                                    void* stream);
+
 /* ---- on-device input preparation ----------------------------------------
  * replaces the per-batch CPU work of ShapeTrainer.set_input (multiframe/main.py:365-377) and
  * its device->host->device round trip of the masks.
