@@ -9,7 +9,7 @@
 // fp64 throughout (v_mfma_f64_16x16x4_f64), in three launches:
 //
 //   k_solve_softmax   A = softmax over vertices of each handle's logits (fp64), one WG per handle; the workgroups
-//                     beyond the 32 handles fill the sentinels of the tiles the factorisation publishes
+//                     beyond the 32 nrhs handle rows fill the sentinels of the tiles the factorisation publishes
 //                     (solve_prepare_block) and reset the status word and the job ticket
 //   k_solve_gram_rows W = L^T L + A^T A, one WG per row; only the non-zeros of L's column are
 //                     visited (the cotangent Laplacian has ~7 per column), fixed summation order
@@ -28,9 +28,12 @@
 // (The round-1 schedule -- one launch per tile column, then k_apply_R for P -- did the same operations in the same
 // order, bit-identical results; DESIGN.md section 4 has its numbers.)
 //
-// Storage: (2 nblk + 1) x nblk tiles, row-major, ld = n_pad = 32 nblk; tile rows [0, nblk) the
-// matrix, tile row nblk the right-hand sides (row h = handle h), tile rows (nblk, 2 nblk] the
-// identity / R.  Indices in [n, n_pad) are padded with the identity.
+// Storage: (2 nblk + nrhs) x nblk tiles, row-major, ld = n_pad = 32 nblk, nrhs = ceil(K_h / 32) <= 4; tile rows
+// [0, nblk) the matrix, tile rows [nblk, nblk + nrhs) the right-hand sides (row n_pad + h = handle h: panel h / 32,
+// rows >= K_h zero), tile rows [nblk + nrhs, 2 nblk + nrhs) the identity / R.  Indices in [n, n_pad) are padded with
+// the identity.  The per-handle buffers X, Z, Q are panel-major, [nrhs][n_pad][32], and A64 is [32 nrhs][n_pad], so
+// panel 0 is the whole buffer of a solve with up to 32 handles and every kernel indexes inside a panel as it did
+// with one.  The status word and the ticket sit in front of everything whose size depends on K_h.
 #include "acfm_common.h"
 
 #include <atomic>
@@ -43,38 +46,43 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NB = 32;        // tile edge
 constexpr int LDT = NB + 2;   // padded LDS row stride (doubles); even: rows stay 16-byte aligned
-constexpr int KHP = 32;       // max handles = one tile row
+constexpr int KHP = 32;       // handles per panel = one tile row of right-hand sides
+constexpr int MAX_RHS = 4;    // panels: at most 128 handles
 
 struct SolveWs {
-  double* W;     // [(2 nblk+1)*32, n_pad] working matrix (trailing updates in place)
-  double* Lf;    // same shape: the factor L; tile row nblk = Y^T = A L^-T; tile rows above = R = L^-T
+  double* W;     // [(2 nblk+nrhs)*32, n_pad] working matrix (trailing updates in place)
+  double* Lf;    // same shape: the factor L; tile rows [nblk, nblk+nrhs) = Y^T = A L^-T; tile rows above = R = L^-T
   double* Linv;  // [nblk, 32, 32] inverses of the diagonal factor tiles
-  double* A64;   // [32, n_pad] handle weights
-  double* X;     // [n_pad, 32] P in fp64
-  double* Z;     // [n_pad, 32] backward: R^T dP
-  double* Q;     // [n_pad, 32] backward: M^-1 dP
+  double* A64;   // [32 nrhs, n_pad] handle weights
+  double* X;     // [nrhs, n_pad, 32] P in fp64
+  double* Z;     // [nrhs, n_pad, 32] backward: R^T dP
+  double* Q;     // [nrhs, n_pad, 32] backward: M^-1 dP
   int* info;     // 0, or 1 + index of the first non-positive pivot
   int n, n_pad, nblk, ld;
+  int nrhs;      // right-hand-side tile rows = handle panels, ceil(Kh / 32)
   size_t bytes;
 };
 
-static inline SolveWs carve_solve(void* base, int V) {
+// Linv and the status words come first: their place depends on V alone (acfm_deform_solve_info takes no Kh)
+static inline SolveWs carve_solve(void* base, int V, int Kh) {
   SolveWs s;
   s.n = V;
   s.nblk = (V + NB - 1) / NB;
   s.n_pad = s.nblk * NB;
   s.ld = s.n_pad;
+  s.nrhs = (Kh + KHP - 1) / KHP;
   char* p = (char*)base;
   size_t o = 0;
-  const size_t mat = sizeof(double) * (size_t)(2 * s.n_pad + NB) * s.ld;
+  const size_t mat = sizeof(double) * (size_t)(2 * s.n_pad + NB * s.nrhs) * s.ld;
+  const size_t pan = sizeof(double) * (size_t)s.nrhs * KHP * s.n_pad;
+  s.Linv = (double*)(p + o); o += align256(sizeof(double) * (size_t)s.nblk * NB * NB);
+  s.info = (int*)(p + o);    o += 256;
   s.W = (double*)(p + o);    o += align256(mat);
   s.Lf = (double*)(p + o);   o += align256(mat);
-  s.Linv = (double*)(p + o); o += align256(sizeof(double) * (size_t)s.nblk * NB * NB);
-  s.A64 = (double*)(p + o);  o += align256(sizeof(double) * (size_t)KHP * s.n_pad);
-  s.X = (double*)(p + o);    o += align256(sizeof(double) * (size_t)s.n_pad * KHP);
-  s.Z = (double*)(p + o);    o += align256(sizeof(double) * (size_t)s.n_pad * KHP);
-  s.Q = (double*)(p + o);    o += align256(sizeof(double) * (size_t)s.n_pad * KHP);
-  s.info = (int*)(p + o);    o += 256;
+  s.A64 = (double*)(p + o);  o += align256(pan);
+  s.X = (double*)(p + o);    o += align256(pan);
+  s.Z = (double*)(p + o);    o += align256(pan);
+  s.Q = (double*)(p + o);    o += align256(pan);
   s.bytes = o;
   return s;
 }
@@ -204,14 +212,14 @@ __device__ __forceinline__ void potrf32_wg(const double* sC, double* sU, int* sC
   POTRF_STAMP(3);
 }
 
-// ---- A = softmax(lbs[:, h]) over the vertices, fp64; grid = 32 (rows >= Kh are zero) ----------
-// grid = 32 + solve_prepare_blocks: the workgroups beyond the 32 handles fill the sentinels of the tile launch
+// ---- A = softmax(lbs[:, h]) over the vertices, fp64; grid = 32 nrhs (rows >= Kh are zero) ----------
+// grid = 32 nrhs + solve_prepare_blocks: the workgroups beyond the handle rows fill the sentinels of the tile launch
 // (neither half depends on the other, both precede the rows of W: one launch instead of two)
 __device__ __forceinline__ void solve_prepare_block(const SolveWs& s, int b_in);
 __global__ __launch_bounds__(256) void k_solve_softmax(const float* __restrict__ lbs, SolveWs s, int Kh) {
   __shared__ double scratch[256];
-  if (blockIdx.x >= KHP) {
-    solve_prepare_block(s, (int)blockIdx.x - KHP);
+  if ((int)blockIdx.x >= KHP * s.nrhs) {
+    solve_prepare_block(s, (int)blockIdx.x - KHP * s.nrhs);
     return;
   }
   const int h = blockIdx.x, t = threadIdx.x;
@@ -336,13 +344,18 @@ __global__ __launch_bounds__(256) void k_solve_gram_rows(const float* __restrict
 }
 
 // ---- the factorisation as ONE launch: tiles as dataflow ------------------------------------------
-// Every tile (i, j) of the factor (matrix rows, the right-hand-side row, the identity rows that become
+// Every tile (i, j) of the factor (matrix rows, the nrhs right-hand-side rows, the identity rows that become
 // R = L^-T) is one job:   acc = W_ij - sum_{k<j} L_ik L_jk^T   (k ascending, the order of the trailing
 // updates of a right-looking sweep),  then  L_ij = acc L_jj^-T  (diagonal: factorise + invert).
-// Jobs are handed out by a ticket in column-major order (column j: diagonal, matrix rows below it,
-// right-hand sides, identity rows 0..j), so a job depends only on jobs with a lower ticket: whichever
-// workgroup holds the lowest unfinished ticket can always finish, with any number of resident
-// workgroups and any dispatch order.
+// Jobs are handed out by a ticket in column-major order; column j holds nblk + 1 + nrhs jobs whatever j is:
+//   the diagonal, the nblk - 1 - j matrix rows below it, the nrhs right-hand-side rows, the identity rows 0..j
+// (ticket = j (nblk + 1 + nrhs) + place in that list; with nrhs = 1 this is the enumeration of the solve that
+// stopped at 32 handles).  A job waits only for tiles of lower tickets: its own row i and row j in the columns
+// k < j, which are jobs of the earlier column k (a column holds every matrix row from its diagonal down, every
+// right-hand-side row and every identity row that has begun; identity row r starts its sum at k = r), and Linv_j,
+// whose job is the first of column j.  So whichever workgroup holds the lowest unfinished ticket can always finish,
+// with any number of resident workgroups and any dispatch order.  The last nblk nrhs tickets are the jobs of
+// P = R Y (apply_job); they read tiles of R and Y^T only, all of lower tickets.
 //
 // Hand-off without flags or fences: Lf and Linv are pre-filled with a sentinel (all-ones, a NaN no
 // arithmetic produces); producers write every word of a finished tile with one agent-scope (sc1,
@@ -392,8 +405,10 @@ __device__ __forceinline__ bool gate(const double* word, int& budget) {
 }
 
 __device__ __forceinline__ void solve_prepare_block(const SolveWs& s, int b_in) {
-  // sentinel into every tile k_chol_tiles publishes (and the diagonal inverses); grid = (2 nblk + 1) nblk + nblk
-  const int nb = s.nblk, tiles = (2 * nb + 1) * nb, b = b_in, t = threadIdx.x;
+  // sentinel into every tile k_chol_tiles publishes (and the diagonal inverses); grid = (2 nblk + nrhs) nblk + nblk.
+  // Every right-hand-side tile row is published, so every one is poisoned: one left out would hand the previous
+  // call's valid words to this call's consumers.
+  const int nb = s.nblk, nr = s.nrhs, tiles = (2 * nb + nr) * nb, b = b_in, t = threadIdx.x;
   ulonglong2 ones = {CHOL_SENTINEL, CHOL_SENTINEL};
   if (b >= tiles) {
     ulonglong2* d = reinterpret_cast<ulonglong2*>(s.Linv + (size_t)(b - tiles) * NB * NB);
@@ -401,7 +416,7 @@ __device__ __forceinline__ void solve_prepare_block(const SolveWs& s, int b_in) 
     return;
   }
   const int ti = b / nb, tj = b % nb;
-  const bool used = ti < nb ? tj <= ti : (ti == nb || tj >= ti - nb - 1);
+  const bool used = ti < nb ? tj <= ti : (ti < nb + nr || tj >= ti - nb - nr);
   if (!used) return;
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
@@ -416,16 +431,20 @@ __device__ __forceinline__ void solve_prepare_block(const SolveWs& s, int b_in) 
 #define CHOL_STAMP(slot) do {} while (0)
 #endif
 
-// P = R Y as the last jobs of the same launch: job c = the 32 vertices of tile row c for all handles,
+// P = R Y as the last jobs of the same launch: job (c, pn) = the 32 vertices of tile row c for the 32 handles of
+// panel pn (h = 32 pn + the h below; Kh = what the panel holds),
 //   P[v][h] = sum_{p >= c} sum_q R[32c + v][32p + q] Y^T[h][32p + q],
 // operands read (and awaited) word by word like every other hand-off; the two wave pairs take alternate p and
 // meet in LDS.  Writes X (fp64, the backward's copy) and the fp32 result.
-__device__ __forceinline__ void apply_job(const SolveWs& s, int c, int Kh, float* __restrict__ P, double* sRed /*[2][2][4][64]*/,
-                                          int t, int& budget, bool& expired) {
+__device__ __forceinline__ void apply_job(const SolveWs& s, int c, int pn, int Kh_all, float* __restrict__ P_all,
+                                          double* sRed /*[2][2][4][64]*/, int t, int& budget, bool& expired) {
   const int lane = t & 63, w = t >> 6, qj = w & 1, par = w >> 1, x = lane & 15, y = lane >> 4;
-  const int nqi = Kh > 16 ? 2 : 1, nb = s.nblk, ld = s.ld;
-  const double* rowR = s.Lf + (size_t)(NB * (nb + 1 + c) + 16 * qj + x) * ld + y;
-  const double* rowY0 = s.Lf + (size_t)(NB * nb + x) * ld + y;
+  const int Kh = Kh_all - KHP * pn;  // > 0; beyond 32: the later panels' share
+  const int nqi = Kh > 16 ? 2 : 1, nb = s.nblk, ld = s.ld, ry = nb + pn, rr = nb + s.nrhs + c;
+  float* P = P_all + KHP * pn;
+  double* X = s.X + (size_t)pn * s.n_pad * KHP;
+  const double* rowR = s.Lf + (size_t)(NB * rr + 16 * qj + x) * ld + y;
+  const double* rowY0 = s.Lf + (size_t)(NB * ry + x) * ld + y;
   const double* rowY1 = rowY0 + (size_t)16 * ld;
   f64x4 acc[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
   for (int p = c + par; p < nb; p += 2) {
@@ -434,8 +453,8 @@ __device__ __forceinline__ void apply_job(const SolveWs& s, int c, int Kh, float
       bool bad = ld_operand(rowR + NB * p, bb) | ld_operand(rowY0 + NB * p, a0);
       if (nqi > 1) bad |= ld_operand(rowY1 + NB * p, a1);
       if (!__any(bad) || expired) break;
-      const bool ok = gate(s.Lf + (size_t)(NB * (nb + 1 + c)) * ld + NB * p, budget) &&
-                      gate(s.Lf + (size_t)(NB * nb) * ld + NB * p, budget);
+      const bool ok = gate(s.Lf + (size_t)(NB * rr) * ld + NB * p, budget) &&
+                      gate(s.Lf + (size_t)(NB * ry) * ld + NB * p, budget);
       if (!ok) expired = true;
     }
 #pragma unroll
@@ -459,8 +478,8 @@ __device__ __forceinline__ void apply_job(const SolveWs& s, int c, int Kh, float
         if (qi >= nqi) continue;
         const int h = 16 * qi + acc_row(lane, e), v = NB * c + 16 * qj + x;
         const double r = acc[qi][e] + sRed[((qi * 2 + qj) * 4 + e) * 64 + lane];
-        s.X[(size_t)v * KHP + h] = r;
-        if (v < s.n && h < Kh) P[(size_t)v * Kh + h] = (float)r;
+        X[(size_t)v * KHP + h] = r;
+        if (v < s.n && h < Kh) P[(size_t)v * Kh_all + h] = (float)r;
       }
   }
 }
@@ -470,7 +489,7 @@ __global__ __launch_bounds__(256) void k_chol_tiles(SolveWs s, int Kh, float* __
   __shared__ int s_ticket, sCount;
   double(*sP)[LDT] = sPQ[0];
   double(*sQ)[LDT] = sPQ[1];
-  const int nb = s.nblk, ntiles = nb * (nb + 2), ld = s.ld;
+  const int nb = s.nblk, nr = s.nrhs, percol = nb + 1 + nr, ntiles = nb * percol, ld = s.ld;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int qi = w >> 1, qj = w & 1, x = lane & 15, y = lane >> 4;
   const int col = 16 * qj + x;
@@ -482,23 +501,25 @@ __global__ __launch_bounds__(256) void k_chol_tiles(SolveWs s, int Kh, float* __
     __syncthreads();
     const int b = s_ticket;
     __syncthreads();
-    if (b >= ntiles + nb) break;
-    if (b >= ntiles) {
-      apply_job(s, b - ntiles, Kh, P, &sPQ[0][0][0], t, budget, expired);
+    if (b >= ntiles + nb * nr) break;
+    if (b >= ntiles) {  // vertex tile by vertex tile (the longest sums first), its panels side by side
+      apply_job(s, (b - ntiles) / nr, (b - ntiles) % nr, Kh, P, &sPQ[0][0][0], t, budget, expired);
       if (expired && lane == 0) atomicOr(s.info, CHOL_E_HANDOFF);
       continue;
     }
-    const int j = b / (nb + 2), yy = b % (nb + 2);
-    const int i = yy < nb - j ? j + yy : (yy == nb - j ? nb : nb + 1 + (yy - (nb - j) - 1));
+    // place yy in column j: [0, nb - j) matrix rows j.., then nr right-hand-side rows, then identity rows 0..j;
+    // in tile rows: matrix i < nb, right-hand sides nb <= i < nb + nr, identity row r at i = nb + nr + r
+    const int j = b / percol, yy = b % percol;
+    const int i = yy < nb - j ? j + yy : nb + (yy - (nb - j));
     const bool diag = i == j;
-    const int k0 = i > nb ? i - nb - 1 : 0;  // identity row r: zero left of column r
+    const int k0 = i >= nb + nr ? i - nb - nr : 0;  // identity row r: zero left of column r
     CHOL_STAMP(0);
     // ---- start value
     f64x4 acc, acc2 = zero;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int row = 16 * qi + acc_row(lane, e);
-      if (i <= nb) {
+      if (i < nb + nr) {
         acc[e] = s.W[(size_t)(NB * i + row) * ld + NB * j + col];
         if (diag && j > 0) acc2[e] = s.W[(size_t)(NB * i + row) * ld + NB * (j - 1) + col];
       } else {
@@ -597,22 +618,29 @@ __global__ __launch_bounds__(256) void k_chol_tiles(SolveWs s, int Kh, float* __
   }
 }
 
-// ---- out = R rhs (TRANS: R^T rhs), R = L^-T upper block-triangular; grid = nblk ------------------
-// WG c produces the 32 vertices of tile row c for all handles.  Right-hand sides and results are
-// [n_pad][32] (vertex-major); RHS 1: an [n_pad][32] fp64 buffer, 2: an fp32 [V][Kh] tensor (the incoming gradient).
+// ---- out = R rhs (TRANS: R^T rhs), R = L^-T upper block-triangular; grid = (nblk, nrhs) ----------
+// WG (c, pn) produces the 32 vertices of tile row c for the handles of panel pn (h below counts inside the panel).
+// Right-hand sides and results are [nrhs][n_pad][32] (panel, then vertex-major); RHS 1: such an fp64 buffer,
+// 2: an fp32 [V][Kh] tensor (the incoming gradient).
 constexpr int APPLY_PAR = 8;  // waves sharing the tile sum of one (vertex tile, handle half)
 template <bool TRANS, int RHS>
-__global__ __launch_bounds__(64 * 2 * APPLY_PAR) void k_apply_R(SolveWs s, const double* __restrict__ rhs64,
-                                                 const float* __restrict__ rhs32, int Kh,
-                                                 double* __restrict__ out, float* __restrict__ out32) {
+__global__ __launch_bounds__(64 * 2 * APPLY_PAR) void k_apply_R(SolveWs s, const double* __restrict__ rhs64_all,
+                                                 const float* __restrict__ rhs32_all, int Kh_all,
+                                                 double* __restrict__ out_all, float* __restrict__ out32_all) {
   __shared__ double sRed[APPLY_PAR - 1][2][2][4][64];
-  const int c = blockIdx.x;
+  const int c = blockIdx.x, pn = blockIdx.y;
+  const int Kh = Kh_all - KHP * pn;  // > 0; beyond 32: the later panels' share
+  const size_t panel = (size_t)pn * s.n_pad * KHP;
+  const double* rhs64 = RHS == 1 ? rhs64_all + panel : nullptr;
+  const float* rhs32 = RHS == 2 ? rhs32_all + KHP * pn : nullptr;
+  double* out = out_all + panel;
+  float* out32 = out32_all ? out32_all + KHP * pn : nullptr;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int qj = w & 1, par = w >> 1;
   const int nqi = Kh > 16 ? 2 : 1;
   const int x = lane & 15, y = lane >> 4;
   const int n = s.n, ld = s.ld, nblk = s.nblk;
-  const double* R = s.Lf + (size_t)(s.n_pad + NB) * ld;
+  const double* R = s.Lf + (size_t)(s.n_pad + NB * s.nrhs) * ld;
   f64x4 acc[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
   const int pb = (TRANS ? 0 : c) + par, pe = TRANS ? c + 1 : nblk;
   for (int p = pb; p < pe; p += APPLY_PAR) {
@@ -627,7 +655,7 @@ __global__ __launch_bounds__(64 * 2 * APPLY_PAR) void k_apply_R(SolveWs s, const
         if (qi >= nqi) continue;
         const int h = 16 * qi + x, v = NB * p + q;
         if (RHS == 1) a[qi][ks] = rhs64[(size_t)v * KHP + h];
-        else a[qi][ks] = (v < n && h < Kh) ? (double)rhs32[(size_t)v * Kh + h] : 0.0;
+        else a[qi][ks] = (v < n && h < Kh) ? (double)rhs32[(size_t)v * Kh_all + h] : 0.0;
       }
     }
 #pragma unroll
@@ -655,7 +683,7 @@ __global__ __launch_bounds__(64 * 2 * APPLY_PAR) void k_apply_R(SolveWs s, const
 #pragma unroll
         for (int pp = 0; pp < APPLY_PAR - 1; ++pp) r += sRed[pp][qi][qj][e][lane];  // fixed order
         out[(size_t)v * KHP + h] = r;
-        if (out32 && v < n && h < Kh) out32[(size_t)v * Kh + h] = (float)r;
+        if (out32 && v < n && h < Kh) out32[(size_t)v * Kh_all + h] = (float)r;
       }
   }
 }
@@ -666,18 +694,22 @@ __global__ __launch_bounds__(64 * 2 * APPLY_PAR) void k_apply_R(SolveWs s, const
 constexpr int BWD_T = 1024;
 __global__ __launch_bounds__(BWD_T) void k_solve_bwd_lbs(SolveWs s, int Kh, float* __restrict__ grad_lbs) {
   __shared__ double scratch[BWD_T], scratch2[BWD_T];
-  __shared__ double sAQ[KHP], sAP[KHP];
+  __shared__ double sAQ[KHP * MAX_RHS], sAP[KHP * MAX_RHS];
   const int h = blockIdx.x, t = threadIdx.x;
   const double* a_row = s.A64 + (size_t)h * s.n_pad;
-  {  // (A Q)[h][h'], (A P)[h][h']: 32 partial sums per output, two independent chains each
+  const size_t panel = (size_t)s.n_pad * KHP;  // doubles of one handle panel of Q / X
+  // (A Q)[h][h'], (A P)[h][h'], panel by panel: 32 partial sums per output, two independent chains each
+  for (int pn = 0; pn < s.nrhs; ++pn) {
+    const double* Qp = s.Q + pn * panel;
+    const double* Xp = s.X + pn * panel;
     const int hp = t & 31, part = t >> 5;
     double aq0 = 0.0, aq1 = 0.0, ap0 = 0.0, ap1 = 0.0;
     for (int v = part; v < s.n; v += 64) {
       const int v1 = v + 32;
       const double a0 = a_row[v], a1 = v1 < s.n ? a_row[v1] : 0.0;
       const size_t o0 = (size_t)v * KHP + hp, o1 = (size_t)(v1 < s.n ? v1 : v) * KHP + hp;
-      aq0 += a0 * s.Q[o0]; ap0 += a0 * s.X[o0];
-      aq1 += a1 * s.Q[o1]; ap1 += a1 * s.X[o1];
+      aq0 += a0 * Qp[o0]; ap0 += a0 * Xp[o0];
+      aq1 += a1 * Qp[o1]; ap1 += a1 * Xp[o1];
     }
     scratch[t] = aq0 + aq1;
     scratch2[t] = ap0 + ap1;
@@ -686,17 +718,22 @@ __global__ __launch_bounds__(BWD_T) void k_solve_bwd_lbs(SolveWs s, int Kh, floa
       const double* src = t < 32 ? scratch : scratch2;
       double z = 0.0;
       for (int q = 0; q < 32; ++q) z += src[(t & 31) + 32 * q];
-      (t < 32 ? sAQ : sAP)[t & 31] = z;
+      (t < 32 ? sAQ : sAP)[KHP * pn + (t & 31)] = z;
     }
     __syncthreads();
   }
-  double* gA = s.W + (size_t)(s.n_pad + h) * s.ld;  // the right-hand-side row of W is free by now
+  double* gA = s.W + (size_t)(s.n_pad + h) * s.ld;  // the right-hand-side rows of W are free by now
   double dot = 0.0;
   for (int v = t; v < s.n; v += BWD_T) {
     const double* q = s.Q + (size_t)v * KHP;
     const double* p = s.X + (size_t)v * KHP;
-    double g = q[h];
-    for (int hp = 0; hp < Kh; ++hp) g -= sAQ[hp] * p[hp] + sAP[hp] * q[hp];
+    double g = q[(h >> 5) * panel + (h & 31)];
+    for (int pn = 0; pn < s.nrhs; ++pn) {  // hp = 32 pn + hl ascending, over all handles
+      const int kl = Kh - KHP * pn < KHP ? Kh - KHP * pn : KHP;
+      const double *qp = q + pn * panel, *pp = p + pn * panel, *aq = sAQ + KHP * pn, *ap = sAP + KHP * pn;
+#pragma unroll 8  // eight handles' loads in flight, as the single loop over Kh <= 32 handles had
+      for (int hl = 0; hl < kl; ++hl) g -= aq[hl] * pp[hl] + ap[hl] * qp[hl];
+    }
     gA[v] = g;
     dot += a_row[v] * g;
   }
@@ -736,21 +773,22 @@ static int chol_resident_workgroups() {
 extern "C" {
 
 size_t acfm_deform_solve_workspace_bytes(int V, int Kh) {
-  if (V <= 0 || Kh <= 0 || Kh > KHP) return 0;
-  return carve_solve(nullptr, V).bytes;
+  if (V <= 0 || Kh <= 0 || Kh > KHP * MAX_RHS) return 0;
+  return carve_solve(nullptr, V, Kh).bytes;
 }
 
 int acfm_deform_solve(const float* L, const float* lbs, int V, int Kh, float* P, void* ws, size_t ws_bytes,
                       void* stream) {
-  if (!L || !lbs || !P || !ws || V <= 0 || Kh <= 0 || Kh > KHP || V > 16384) return ACFM_E_BADARG;
-  SolveWs s = carve_solve(ws, V);
+  if (!L || !lbs || !P || !ws || V <= 0 || Kh <= 0 || Kh > KHP * MAX_RHS || V > 16384) return ACFM_E_BADARG;
+  SolveWs s = carve_solve(ws, V, Kh);
   if (ws_bytes < s.bytes) return ACFM_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(ACFM_PROF_SOLVE, st);
-  hipLaunchKernelGGL(k_solve_softmax, dim3(KHP + (2 * s.nblk + 2) * s.nblk), dim3(256), 0, st, lbs, s, Kh);
+  // handle rows, then one block per tile of Lf and per diagonal inverse (solve_prepare_block)
+  hipLaunchKernelGGL(k_solve_softmax, dim3(KHP * s.nrhs + (2 * s.nblk + s.nrhs + 1) * s.nblk), dim3(256), 0, st, lbs, s, Kh);
   hipLaunchKernelGGL(k_solve_gram_rows, dim3(s.n_pad), dim3(256), 0, st, L, s, Kh);
   {  // factorisation, R = L^-T, Y^T and P = R Y in one launch
-    const int jobs = s.nblk * (s.nblk + 3), cap = chol_resident_workgroups();
+    const int jobs = s.nblk * (s.nblk + 1 + 2 * s.nrhs), cap = chol_resident_workgroups();
     hipLaunchKernelGGL(k_chol_tiles, dim3(jobs < cap ? jobs : cap), dim3(256), 0, st, s, Kh, P);
   }
   ACFM_CHECK_LAUNCH();
@@ -759,14 +797,15 @@ int acfm_deform_solve(const float* L, const float* lbs, int V, int Kh, float* P,
 
 int acfm_deform_solve_backward(const float* grad_P, int V, int Kh, void* ws, size_t ws_bytes, float* grad_lbs,
                                void* stream) {
-  if (!grad_P || !grad_lbs || !ws || V <= 0 || Kh <= 0 || Kh > KHP || V > 16384) return ACFM_E_BADARG;
-  SolveWs s = carve_solve(ws, V);
+  if (!grad_P || !grad_lbs || !ws || V <= 0 || Kh <= 0 || Kh > KHP * MAX_RHS || V > 16384) return ACFM_E_BADARG;
+  SolveWs s = carve_solve(ws, V, Kh);
   if (ws_bytes < s.bytes) return ACFM_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(ACFM_PROF_SOLVE_BWD, st);
-  hipLaunchKernelGGL((k_apply_R<true, 2>), dim3(s.nblk), dim3(64 * 2 * APPLY_PAR), 0, st, s, (const double*)nullptr, grad_P, Kh,
+  const dim3 tiles(s.nblk, s.nrhs);
+  hipLaunchKernelGGL((k_apply_R<true, 2>), tiles, dim3(64 * 2 * APPLY_PAR), 0, st, s, (const double*)nullptr, grad_P, Kh,
                      s.Z, (float*)nullptr);
-  hipLaunchKernelGGL((k_apply_R<false, 1>), dim3(s.nblk), dim3(64 * 2 * APPLY_PAR), 0, st, s, (const double*)s.Z,
+  hipLaunchKernelGGL((k_apply_R<false, 1>), tiles, dim3(64 * 2 * APPLY_PAR), 0, st, s, (const double*)s.Z,
                      (const float*)nullptr, Kh, s.Q, (float*)nullptr);
   hipLaunchKernelGGL(k_solve_bwd_lbs, dim3(Kh), dim3(BWD_T), 0, st, s, Kh, grad_lbs);
   ACFM_CHECK_LAUNCH();
@@ -777,9 +816,10 @@ int acfm_deform_solve_backward(const float* grad_P, int V, int Kh, void* ws, siz
 int acfm_debug_potrf_stamps(long long* out_host) {
   return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(acfm::g_potrf_stamps), sizeof(long long) * 16) == hipSuccess ? ACFM_OK : ACFM_E_LAUNCH;
 }
-// diagnostic build only: the 8 clock stamps (10 ns units) of each diagonal job of k_chol_tiles
+// diagnostic build only: the 8 clock stamps (10 ns units) of each diagonal job of k_chol_tiles, of a solve with up
+// to 32 handles (where Z lies depends on the number of panels)
 int acfm_debug_solve_stamps(const void* ws, int V, long long* out_host, int n) {
-  SolveWs s = carve_solve(const_cast<void*>(ws), V);
+  SolveWs s = carve_solve(const_cast<void*>(ws), V, 1);
   if (n > 8 * s.nblk) n = 8 * s.nblk;
   return hipMemcpy(out_host, s.Z, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess ? ACFM_OK : ACFM_E_LAUNCH;
 }
@@ -787,14 +827,14 @@ int acfm_debug_solve_stamps(const void* ws, int V, long long* out_host, int n) {
 
 size_t acfm_deform_solve_info_offset(int V) {
   if (V <= 0) return 0;
-  SolveWs s = carve_solve(nullptr, V);
+  SolveWs s = carve_solve(nullptr, V, 1);  // the same for every Kh
   return (size_t)((char*)s.info - (char*)nullptr);
 }
 
 int acfm_deform_solve_info(const void* ws, size_t ws_bytes, int V, int* info_host, void* stream) {
   if (!ws || !info_host || V <= 0) return ACFM_E_BADARG;
-  SolveWs s = carve_solve(const_cast<void*>(ws), V);
-  if (ws_bytes < s.bytes) return ACFM_E_WORKSPACE;
+  SolveWs s = carve_solve(const_cast<void*>(ws), V, 1);  // the status word lies where it lies for every Kh
+  if (ws_bytes < s.bytes) return ACFM_E_WORKSPACE;       // the smallest workspace of this V
   hipStream_t st = (hipStream_t)stream;
   if (hipMemcpyAsync(info_host, s.info, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return ACFM_E_LAUNCH;
   if (hipStreamSynchronize(st) != hipSuccess) return ACFM_E_LAUNCH;

@@ -440,8 +440,8 @@ class _DeformSolve(torch.autograd.Function):
         V, Kh = b.shape
         if l.shape != (V, V):
             raise ValueError("L must be [V,V] = [%d,%d], got %s" % (V, V, tuple(l.shape)))
-        if Kh > 32:
-            raise ValueError("at most 32 handles (got %d)" % Kh)
+        if Kh > 128:
+            raise ValueError("at most 128 handles (got %d)" % Kh)
         capturing = torch.cuda.is_current_stream_capturing()
         if not capturing:
             solve_status()
@@ -484,7 +484,9 @@ class _DeformSolve(torch.autograd.Function):
 def deform_solve(L, lbs_logits, check=False):
     """P [V,K_h] = (L^T L + A^T A)^-1 A^T with A = softmax(lbs_logits, dim 0)^T: the reference's
     per-frame Cholesky solve (multiframe/main.py:586-609) collapsed to one fp64 factorisation per
-    step.  L [V,V] dense Laplacian (no gradient), lbs_logits [V,K_h] (gradient supported).
+    step.  L [V,V] dense Laplacian (no gradient), lbs_logits [V,K_h] (gradient supported), K_h <= 128 (the
+    reference's 64-handle bird model and its 128-handle default; ValueError beyond) and V <= 16384.  Up to 32
+    handles are one panel of right-hand sides; every further 32 add a panel of tile jobs to the same launch.
     check=True synchronises and raises if the matrix is not positive definite or a hand-off of the single-launch
     factorisation timed out (decode_solve_info); check=False (the per-step path) copies the status word to the host
     without blocking and the NEXT deform_solve / solve_status() call raises for it."""

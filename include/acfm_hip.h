@@ -217,14 +217,17 @@ int acfm_camera_normalize_backward(const float* cam_raw, const float* grad_cams,
  * [K_h,V] (mesh_net.py:597-599) and the dense cotangent Laplacian L [V,V] of the mean shape,
  *   P = (L^T L + A^T A)^-1 A^T   [V,K_h]
  * by a blocked fp64 Cholesky on the matrix cores; once per optimiser step for all frames
- * (pred_v_n = mean_v + P delta_n, acfm_deform_apply).  K_h <= 32.
+ * (pred_v_n = mean_v + P delta_n, acfm_deform_apply).  K_h <= 128 and V <= 16384 (ACFM_E_BADARG beyond; the
+ * workspace query returns 0): the handles are right-hand sides in panels of 32, ceil(K_h / 32) tile rows of the same
+ * single launch, and up to 32 handles compute what one panel always did, bit for bit.
  * The workspace keeps the factor: acfm_deform_solve_backward turns grad_P [V,K_h] into
  * grad_lbs [V,K_h] (L carries no gradient, geom_utils.py:245).  acfm_deform_solve_info copies
  * the factorisation status to the host and synchronises the stream: 0 = ok; bit ACFM_SOLVE_INFO_HANDOFF set = a
  * hand-off wait of the single-launch factorisation expired (a starved wave: P holds NaNs; re-run the solve);
  * otherwise the low bits are 1 + first row of the 32-row tile with a non-positive pivot (the reference's
  * torch.cholesky raises there).  acfm_deform_solve_info_offset: byte offset of that int32 status word inside the
- * workspace, for callers that copy it without blocking (ops.py polls it that way between steps). */
+ * workspace, for callers that copy it without blocking (ops.py polls it that way between steps).  The offset depends
+ * on V alone, and acfm_deform_solve_info accepts any workspace of at least acfm_deform_solve_workspace_bytes(V, 1). */
 #define ACFM_SOLVE_INFO_HANDOFF 0x40000000
 size_t acfm_deform_solve_workspace_bytes(int V, int Kh);
 int acfm_deform_solve(const float* L, const float* lbs, int V, int Kh, float* P, void* ws, size_t ws_bytes,
