@@ -249,6 +249,18 @@ class Meshes:
             return torch.searchsorted(key, (torch.minimum(a, b) * V + torch.maximum(a, b)).reshape(-1)).reshape(-1, 3)
         return self._topo("faces_packed_to_edges_packed", make)
 
+    def geodesic_tables_packed(self):
+        """-> (faces [F,3], edges [E,2], face_edges [F,3]) int32, contiguous: faces_packed(), edges_packed() and
+        faces_packed_to_edges_packed() as acfm_geodesic_distances reads them.  Topology only: built once per faces
+        tensor (the edges are a sort + unique with one host read), outside any graph capture."""
+        def make():
+            return tuple(t.to(torch.int32).contiguous() for t in
+                         (self.faces_packed(), self.edges_packed(), self.faces_packed_to_edges_packed()))
+        return self._topo("geodesic_tables_packed", make)
+
+    def has_geodesic_tables(self):
+        return "geodesic_tables_packed" in self._topology()
+
     def normal_pairs_packed(self):
         """-> (quads [Q,4] int64 = (a, b, c, d), weights [Q] float32) for mesh_normal_consistency: for every edge
         (a, b), a < b, that lies in m >= 2 faces, every unordered pair of those faces, c and d being the faces' third

@@ -736,6 +736,33 @@ int acfm_uv_atlas_backward(const float* grad_atlas, const float* atlas, const fl
                            const int32_t* pix_taps, int n_entries, int B, int Hu, int Wu, int Fp, int T, int nsym,
                            float* grad_uvimage, void* stream);
 
+/* ---- geodesic handles: the distances of the lbs initialisation (multiframe/nnutils/mesh_net.py:69-85, 523-544) ----
+ * replaces gdist.local_gdist_matrix(verts, faces) there -- by shortest paths on the edge-Steiner graph of the mesh, a
+ * certified UPPER BOUND of the exact polyhedral geodesic that gdist computes, not its values (DESIGN.md "Geodesic
+ * handles" has the definition and the measured error; nothing could be checked against the gdist package).
+ *   verts [N,V,3] f32: N sets of positions on ONE topology.  faces [F,3], edges [E,2] = (lo, hi), lo < hi, in
+ *   Meshes.edges_packed() order, face_edges [F,3] = the rows of `edges` of each face's edges: int32 tables the caller
+ *   builds once per faces tensor (mesh_net.py:523-544 runs once per model).
+ *   Nodes: the V vertices, then m = 0..ACFM_GEODESIC_MAX_STEINER points per edge, node V + e m + (j - 1), j = 1..m, at
+ *   a + (j / (m + 1)) (b - a), a = verts[lo], b = verts[hi].  Arcs: inside every face all pairs of the 3 + 3 m nodes on
+ *   its boundary (one wave's lanes), length sqrt((dx dx + dy dy) + dz dz), every operation rounded.
+ *   out [N,S,V]: out[n,s,v] = the shortest path from vertex sources[s] (i32 [S] on the device; NULL = all V in order,
+ *   then S must be V) to vertex v in f32, every hop rounded; 0 at the source, +inf where there is no path.  Every
+ *   element is written.  The result is the least fixed point of d_v = min(d_v, fl(d_u + w_uv)), which does not depend
+ *   on the order of the relaxations: the same bits on every run.
+ * One launch, one workgroup per (source, mesh): all node distances in dynamic LDS, acfm_geodesic_lds_bytes(V, E, m) =
+ *   16 + 4 (V + m E) bytes (0 for arguments out of range), at most ACFM_GEODESIC_LDS_MAX; a graph that does not fit is
+ *   ACFM_E_BADARG -- there is no global-memory variant.  No global atomics, nothing shared between workgroups.
+ * status: one i32 on the device, ZERO before the call.  It stays 0 unless a workgroup gave up: 1 = not converged after
+ *   V + m E sweeps (the Bellman-Ford bound: cannot happen with arcs >= 0), 2 = a source outside [0, V); that
+ *   workgroup's row is NaN.  A face with a table entry out of range is left out of the graph, never dereferenced. */
+#define ACFM_GEODESIC_MAX_STEINER 20
+#define ACFM_GEODESIC_LDS_MAX 153600
+size_t acfm_geodesic_lds_bytes(int V, int E, int m);
+int acfm_geodesic_distances(const float* verts, const int32_t* faces, const int32_t* edges, const int32_t* face_edges,
+                            int N, int V, int F, int E, int m, const int32_t* sources, int S, float* out,
+                            int32_t* status, void* stream);
+
 /* ---- perceptual texture loss: the tail of LPIPS (multiframe/nnutils/loss_utils.py:359-383) --------
  * replaces everything lpips.LPIPS(net='alex', lpips=False, spatial=True) and its caller do around AlexNet's five
  * convolutions (which stay with the framework).  float32, contiguous NCHW.  The definition is restated in DESIGN.md

@@ -1,0 +1,58 @@
+"""Timing of the geodesic handle distances (mesh_net.py:69-85, 523-544) at the reference's size: all pairs of a
+642-vertex template at steiner = 15 (29,442 nodes, 1.18 M arcs, 117,784 bytes of LDS per workgroup, 642 workgroups).
+ops.geodesic_distances (csrc/acfm_geodesic.hip, float32) against the host path of handles.py -- scipy's Dijkstra on the
+same graph in float64 --, which is timed on a subset of the sources (its cost is per source) and scaled.  Events around
+every iteration, warm-up, median.
+usage: python tools/geodesic_bench.py [--mesh horse] [--steiner 15] [--reps 20] [--host-sources 16] [--dump D.npy]
+(--dump keeps the GPU's matrix, to compare two builds of the library bit for bit: ACFM_LIB selects the build)"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
+from acfm_video_3d_reconstruction_amd import handles, ops
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--mesh", default="horse")
+ap.add_argument("--steiner", type=int, default=15)
+ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--host-sources", type=int, default=16, help="sources timed on the host path (0 = all)")
+ap.add_argument("--dump", default=None, help="save the GPU's [V,V] matrix here (.npy)")
+a = ap.parse_args()
+d = torch.device("cuda:0")
+m = np.load(os.path.join(ROOT, "tests", "golden", "meshes.npz"))
+v, f = m[a.mesh + "_v"].astype(np.float32), m[a.mesh + "_f"]
+V = v.shape[0]
+tv, tf = torch.tensor(v, device=d), torch.tensor(f, device=d)
+
+D = ops.geodesic_distances(tv, tf, a.steiner)          # builds the tables
+if a.dump:
+    np.save(a.dump, D.cpu().numpy())
+for _ in range(a.warmup):
+    ops.geodesic_distances(tv, tf, a.steiner)
+ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+for e0, e1 in ev:
+    e0.record(); ops.geodesic_distances(tv, tf, a.steiner); e1.record()
+torch.cuda.synchronize()
+ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+gpu_ms = ms[a.reps // 2]
+
+k = V if a.host_sources <= 0 else min(a.host_sources, V)
+src = np.linspace(0, V - 1, k).astype(np.int64)
+t0 = time.perf_counter()
+pos, r, c, w = handles.steiner_graph(v.astype(np.float64), f, a.steiner)
+t_graph = time.perf_counter() - t0
+t0 = time.perf_counter()
+Dh = handles.geodesic_distance_matrix(v.astype(np.float64), f, a.steiner, src)
+t_host = time.perf_counter() - t0 - t_graph            # (the call builds the graph once more)
+err = float(np.abs(D[torch.as_tensor(src, device=d)].cpu().numpy() - Dh).max())
+print("%s: V = %d, steiner = %d: %d nodes, %d arcs" % (a.mesh, V, a.steiner, pos.shape[0], r.shape[0]))
+print("max |gpu - host| over %d sources: %.3e = %.3e of max D = %.4f" % (k, err, err / Dh.max(), Dh.max()))
+print("GPU, all %d sources: median %.2f ms (min %.2f, max %.2f) of %d" % (V, gpu_ms, ms[0], ms[-1], a.reps))
+print("host: graph %.2f s; Dijkstra %.3f s per source over %d sources -> %.1f s for all %d (%.0f x the GPU)"
+      % (t_graph, max(t_host, 0.0) / k, k, max(t_host, 0.0) / k * V, V, max(t_host, 0.0) / k * V / (gpu_ms * 1e-3)))
