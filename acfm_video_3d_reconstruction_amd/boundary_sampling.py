@@ -1,0 +1,127 @@
+"""The random subset of boundary points of loss_utils.bds_loss (multiframe/nnutils/loss_utils.py:211,
+`torch.randperm(P)[:n_samples]`), drawn on the GPU.
+
+    sampler = BoundarySampler(n_samples=1000, seed=0)
+    loss = loss_utils.bds_loss(verts, bds, faces, pix_to_face, sampler=sampler)
+
+The reference draws on the host at every call; here the draw is a kernel (ops.boundary_subset on acfm_sample.hip)
+whose only state is an int64 pair (seed, draw) in device memory, advanced in stream order.  A step that contains the
+boundary loss can therefore be captured into a hipGraph with more than n_samples boundary points per frame, and every
+replay draws a fresh subset.
+
+The draws follow the reference's DISTRIBUTION -- a uniform subset of min(n_samples, P) slots without replacement --
+not its random stream (torch's host Mersenne Twister cannot be continued on the device); the same holds for
+pytorch3d_shim.ops.sample_points_from_meshes.  The order inside a subset is ascending instead of random, which the loss,
+a sum over the points, does not see.
+
+Two forms:
+  shared (per_mesh=False, the reference's): ONE subset for the batch, over the padded length P -- or over
+      min(P, max(counts)) when the true list lengths are given;
+  per mesh (per_mesh=True): every frame draws from its OWN counts[b] points, so each frame gets n_samples real points
+      instead of spending draws on its padding (whose valid flag is 0).
+
+subset_host is the definition in numpy; the kernel equals it index for index (tests/test_gpu_boundary_sampler.py)."""
+import numpy as np
+import torch
+
+from . import ops
+
+# Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11)
+_M0, _M1 = 0xD2511F53, 0xCD9E8D57
+_W0, _W1 = 0x9E3779B9, 0xBB67AE85
+_MASK32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """counter: four uint32 arrays (or scalars) of one shape, key: two -> the four output words as uint64 arrays
+    holding 32-bit values."""
+    c = [np.asarray(x, dtype=np.uint64) & np.uint64(_MASK32) for x in counter]
+    c = list(np.broadcast_arrays(*c))
+    k0, k1 = int(key[0]) & _MASK32, int(key[1]) & _MASK32
+    m32, s32 = np.uint64(_MASK32), np.uint64(32)
+    for _ in range(10):
+        p0 = np.uint64(_M0) * c[0]       # 32 x 32 -> 64 bits: no overflow in uint64
+        p1 = np.uint64(_M1) * c[2]
+        c = [(p1 >> s32) ^ c[1] ^ np.uint64(k0), p1 & m32, (p0 >> s32) ^ c[3] ^ np.uint64(k1), p0 & m32]
+        k0, k1 = (k0 + _W0) & _MASK32, (k1 + _W1) & _MASK32
+    return c
+
+
+def slot_keys(seed, draw, row, P_r):
+    """The 64-bit keys of slots 0 .. P_r - 1 of row `row` in draw `draw`: Philox4x32-10 with key (seed's low word,
+    seed's high word) and counter (slot, row, draw's low word, draw's high word); key = x0 << 32 | x1."""
+    seed, draw = int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF
+    i = np.arange(int(P_r), dtype=np.uint64)
+    x = philox4x32_10((i, int(row) & _MASK32, draw & _MASK32, draw >> 32), (seed & _MASK32, seed >> 32))
+    return (x[0] << np.uint64(32)) | x[1]
+
+
+def subset_host(seed, draw, row, P_r, n_samples):
+    """The definition of the draw: int32 [n_samples] = the min(n_samples, P_r) slots of [0, P_r) with the smallest
+    (key, slot) pairs, in ascending slot order, then -1."""
+    P_r, n = max(int(P_r), 0), int(n_samples)
+    out = np.full((n,), -1, dtype=np.int32)
+    k = min(n, P_r)
+    if k:
+        keys = slot_keys(seed, draw, row, P_r)
+        order = np.lexsort((np.arange(P_r), keys))      # by key, ties by slot
+        out[:k] = np.sort(order[:k]).astype(np.int32)
+    return out
+
+
+def draw_host(seed, draw, P, n_samples, counts=None, per_mesh=False):
+    """What BoundarySampler.draw / ops.boundary_subset return for that (seed, draw): int32 [rows, n_samples]."""
+    if per_mesh:
+        return np.stack([subset_host(seed, draw, r, min(int(P), max(int(c), 0)), n_samples)
+                         for r, c in enumerate(counts)])
+    P0 = int(P) if counts is None else min(int(P), max(0, max(int(c) for c in counts)))
+    return subset_host(seed, draw, 0, P0, n_samples)[None]
+
+
+class BoundarySampler:
+    """Holds the device state (seed, draw) of the boundary-point draw, one int64 [2] tensor per device, created on
+    first use there (create it before capturing a graph: call draw() or state_on(device) once eagerly)."""
+
+    def __init__(self, n_samples=1000, seed=0, per_mesh=False):
+        if int(n_samples) <= 0:
+            raise ValueError("BoundarySampler: n_samples must be positive")
+        self.n_samples, self.seed, self.per_mesh = int(n_samples), int(seed), bool(per_mesh)
+        self._states = {}
+
+    def state_on(self, device):
+        """The int64 [2] = (seed, draw) tensor of `device`."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("acfm_video_3d_reconstruction_amd ops run on the GPU only "
+                               "(got a %s tensor); there is no CPU fallback" % device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        st = self._states.get(device)
+        if st is None:
+            st = self._states[device] = torch.tensor([self.seed, 0], dtype=torch.int64, device=device)
+        return st
+
+    @property
+    def state(self):
+        """The state on the current GPU."""
+        return self.state_on(torch.device("cuda", torch.cuda.current_device()))
+
+    def reseed(self, seed, draw=0):
+        """Restart every device's sequence at (seed, draw).  In stream order on the existing state tensors, so graphs
+        captured with them keep working."""
+        self.seed = int(seed)
+        for st in self._states.values():
+            st.copy_(torch.tensor([self.seed, int(draw)], dtype=torch.int64))
+        return self
+
+    def draw(self, P, counts=None, device=None):
+        """-> sel int32 [1, n_samples] (shared) or [RB, n_samples] (per mesh); advances the draw counter."""
+        if device is None:
+            device = counts.device if counts is not None else torch.device("cuda", torch.cuda.current_device())
+        if counts is not None and not counts.is_cuda:
+            raise RuntimeError("acfm_video_3d_reconstruction_amd ops run on the GPU only "
+                               "(got a %s tensor); there is no CPU fallback" % counts.device)
+        if self.per_mesh and counts is None:
+            raise ValueError("BoundarySampler(per_mesh=True) needs the true counts (compute_boundaries(..., "
+                             "return_counts=True))")
+        return ops.boundary_subset(self.state_on(device), P, self.n_samples, counts=counts, per_mesh=self.per_mesh)

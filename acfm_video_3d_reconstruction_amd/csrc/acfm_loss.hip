@@ -2,6 +2,7 @@
 //   fused silhouette losses  <- loss_utils.l1_loss / iou / edt_loss   (loss_utils.py:18-32, 72-77, 245-253)
 //   visible-vertex bitmap    <- loss_utils.bds_loss :214-224 / optical_flow_loss :432-443
 //   boundary loss            <- loss_utils.bds_loss :204-237
+//   boundary loss on a subset named by slot lists (acfm_sample.hip draws them) <- :211-213 + :226-237
 #include "acfm_common.h"
 #include "acfm_row_finish.h"
 
@@ -351,6 +352,93 @@ __global__ __launch_bounds__(LTPB) void k_bds_loss(const float* __restrict__ ver
   else if (lane == 0) atomicAdd(&loss[n], contrib);
 }
 
+// k_bds_loss with the lane's point read through a slot list, sel [rows][S] (acfm_boundary_subset): lane p < S takes
+// slot s = sel[((n % RB) % rows) S + p] of its reference's P points; s < 0 is an empty entry (adds 0, argmin -1).
+// argmin is [N][S], and no gathered copy of the points exists.  Everything after the point's load is k_bds_loss line
+// for line -- written out a second time, not shared through a template: with the body in a common function the
+// compiler allocated k_bds_loss's registers differently, and that kernel's machine code is pinned
+// (tools/isa_diff.py against the parent).
+__global__ __launch_bounds__(LTPB) void k_bds_loss_sel(const float* __restrict__ verts_xy,
+                                                       const float* __restrict__ bds,
+                                                       const uint8_t* __restrict__ vis, int V, int P, int RB,
+                                                       float* __restrict__ loss, int32_t* __restrict__ argmin,
+                                                       RowScratch sc, const int32_t* __restrict__ sel, int rows,
+                                                       int S) {
+  extern __shared__ float s_xy[];  // [V][2]: per quarter, its visible vertices packed to the front; then int s_idx[V]
+  __shared__ float s_best[4][64];
+  __shared__ int s_bi[4][64];
+  const int n = blockIdx.y, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  // the lane's boundary point first: its load is in flight while the vertices are staged
+  const int p = blockIdx.x * 64 + lane;
+  float bx = 0.f, by = 0.f, bm = 0.f;
+  int s = -1;
+  if (p < S) s = sel[(size_t)((n % RB) % rows) * S + p];
+  const bool empty = s < 0 || s >= P;
+  if (!empty) {
+    const float* b = bds + ((size_t)(n % RB) * P + s) * 3;
+    bx = b[0]; by = b[1]; bm = b[2];
+  }
+  const int chunk = (V + 3) / 4, v0 = wv * chunk, v1 = min(V, v0 + chunk);
+  int* s_idx = reinterpret_cast<int*>(s_xy + 2 * (size_t)V);
+  int nvis = 0;
+  {
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    // (unconditional loads, four rounds in flight: with the loads behind the visibility test the staging was a
+    // chain of memory latencies)
+    for (int base = v0; base < v1; base += 4 * 64) {
+      uint8_t vz[4];
+      float2 xy[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int v = min(base + u * 64 + lane, v1 - 1);
+        vz[u] = vis[(size_t)n * V + v];
+        xy[u] = *reinterpret_cast<const float2*>(verts_xy + ((size_t)n * V + v) * 2);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int v = base + u * 64 + lane;
+        const bool keep = (v < v1) && vz[u] != 0;
+        const unsigned long long m = __ballot(keep);
+        if (keep) {
+          const int pos = v0 + nvis + __popcll(m & lt);
+          *reinterpret_cast<float2*>(s_xy + 2 * pos) = xy[u];
+          s_idx[pos] = v;
+        }
+        nvis += __popcll(m);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  float best = 1000.0f;  // loss_utils.py:228: invisible vertices sit at distance 1000
+  int bi = -1;
+#pragma unroll 8
+  for (int v = v0; v < v0 + nvis; ++v) {
+    const float2 q = *reinterpret_cast<const float2*>(s_xy + 2 * v);
+    const float dx = bx - q.x, dy = by - q.y;
+    const float d = dx * dx + dy * dy;
+    if (d < best) { best = d; bi = v; }
+  }
+  if (bi >= 0) bi = s_idx[bi];
+  s_best[wv][lane] = best; s_bi[wv][lane] = bi;
+  __syncthreads();
+  if (wv != 0) return;
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const float d = s_best[w][lane];
+    if (d < best) { best = d; bi = s_bi[w][lane]; }
+  }
+  float contrib = 0.f;
+  if (p < S) {
+    contrib = empty ? 0.f : best * bm;
+    argmin[(size_t)n * S + p] = empty ? -1 : bi;
+  }
+  contrib = wave_sum(contrib);
+  if (sc.tickets) row_finish<1>(sc, n, (int)gridDim.x, (int)blockIdx.x, contrib, loss + n);
+  else if (lane == 0) atomicAdd(&loss[n], contrib);
+}
+
 // One workgroup per mesh: the points' contributions are summed per vertex in LDS (P <= ~1000 points
 // onto V vertices) and the whole [V,2] gradient row is stored, zeros included -- no global atomics
 // (64 k scattered memory-side atomics took 13 us) and no zero fill of the output.
@@ -372,6 +460,45 @@ __global__ __launch_bounds__(256) void k_bds_loss_bwd(const float* __restrict__ 
       const int p = min(p0 + u * 256, P - 1);
       v[u] = (p0 + u * 256 < P) ? argmin[(size_t)n * P + p] : -1;
       const float* b = bds + ((size_t)(n % RB) * P + p) * 3;
+      bx[u] = b[0]; by[u] = b[1]; bm[u] = b[2];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float g = go * bm[u];
+      if (v[u] < 0 || g == 0.f) continue;
+      const float* x = verts_xy + ((size_t)n * V + v[u]) * 2;
+      atomicAdd(&s_g[2 * v[u]], 2.0f * (x[0] - bx[u]) * g);
+      atomicAdd(&s_g[2 * v[u] + 1], 2.0f * (x[1] - by[u]) * g);
+    }
+  }
+  __syncthreads();
+  float* o = gv + (size_t)n * V * 2;
+  for (int i = tid; i < 2 * V; i += 256) o[i] = s_g[i];
+}
+
+// k_bds_loss_bwd over the entries of argmin [N][S]: entry p belongs to slot sel[((n % RB) % rows) S + p] (see
+// k_bds_loss_sel, also for why this is a second kernel and not a template).
+__global__ __launch_bounds__(256) void k_bds_loss_sel_bwd(const float* __restrict__ verts_xy,
+                                                          const float* __restrict__ bds,
+                                                          const int32_t* __restrict__ argmin,
+                                                          const float* __restrict__ gl, int V, int P, int RB,
+                                                          float* __restrict__ gv, const int32_t* __restrict__ sel,
+                                                          int rows, int S) {
+  extern __shared__ float s_g[];  // [V][2]
+  const int n = blockIdx.x, tid = threadIdx.x;
+  for (int i = tid; i < 2 * V; i += 256) s_g[i] = 0.f;
+  __syncthreads();
+  const float go = gl[n];
+  for (int p0 = tid; p0 < S; p0 += 4 * 256) {      // four points per thread in flight
+    int v[4];
+    float bx[4], by[4], bm[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int p = min(p0 + u * 256, S - 1);
+      v[u] = (p0 + u * 256 < S) ? argmin[(size_t)n * S + p] : -1;
+      int s = sel[(size_t)((n % RB) % rows) * S + p];
+      if (s < 0 || s >= P) { s = 0; v[u] = -1; }   // an empty entry (its argmin is -1 already)
+      const float* b = bds + ((size_t)(n % RB) * P + s) * 3;
       bx[u] = b[0]; by[u] = b[1]; bm[u] = b[2];
     }
 #pragma unroll
@@ -920,6 +1047,41 @@ int acfm_bds_loss_backward(const float* verts_xy, const float* bds, const int32_
   ProfScope ps(ACFM_PROF_BDS_BWD, st);
   hipLaunchKernelGGL(k_bds_loss_bwd, dim3(N), dim3(256), lds, st, verts_xy, bds, argmin,
                      grad_loss, V, P, ref_batch, grad_verts_xy);
+  ACFM_CHECK_LAUNCH();
+  return ACFM_OK;
+}
+
+int acfm_bds_loss_sel_ws(const float* verts_xy, const float* bds, const uint8_t* vis, const int32_t* sel, int N, int V,
+                         int P, int ref_batch, int rows, int S, float* loss, int32_t* argmin, uint32_t* tickets,
+                         float* partials, size_t partial_floats, void* stream) {
+  if (!verts_xy || !bds || !vis || !sel || !loss || !argmin || N <= 0 || N > 65535 || V <= 0 || P <= 0 || S <= 0 ||
+      ref_batch <= 0 || N % ref_batch != 0 || (rows != 1 && rows != ref_batch))
+    return ACFM_E_BADARG;
+  const size_t lds = sizeof(float) * 3 * (size_t)V;
+  if (lds > 150 * 1024) return ACFM_E_BADARG;
+  RowScratch sc;
+  if (const int rc = row_scratch(ACFM_LOSS_BDS, N, S, tickets, partials, partial_floats, sc)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (!sc.tickets && zero_async(loss, sizeof(float) * (size_t)N, st) != ACFM_OK) return ACFM_E_LAUNCH;
+  ProfScope ps(ACFM_PROF_BDS, st);
+  hipLaunchKernelGGL(k_bds_loss_sel, dim3((S + 63) / 64, N), dim3(LTPB), lds, st, verts_xy, bds, vis,
+                     V, P, ref_batch, loss, argmin, sc, sel, rows, S);
+  ACFM_CHECK_LAUNCH();
+  return ACFM_OK;
+}
+
+int acfm_bds_loss_sel_backward(const float* verts_xy, const float* bds, const int32_t* sel, const int32_t* argmin,
+                               const float* grad_loss, int N, int V, int P, int ref_batch, int rows, int S,
+                               float* grad_verts_xy, void* stream) {
+  if (!verts_xy || !bds || !sel || !argmin || !grad_loss || !grad_verts_xy || N <= 0 || N > 65535 || V <= 0 ||
+      P <= 0 || S <= 0 || ref_batch <= 0 || N % ref_batch != 0 || (rows != 1 && rows != ref_batch))
+    return ACFM_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = sizeof(float) * 2 * (size_t)V;
+  if (lds > 150 * 1024) return ACFM_E_BADARG;
+  ProfScope ps(ACFM_PROF_BDS_BWD, st);
+  hipLaunchKernelGGL(k_bds_loss_sel_bwd, dim3(N), dim3(256), lds, st, verts_xy, bds, argmin, grad_loss, V, P,
+                     ref_batch, grad_verts_xy, sel, rows, S);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
 }

@@ -36,16 +36,25 @@ def compute_dt_barrier(mask, k=50):
     return out[0] if mask.dim() == 2 else out
 
 
-def compute_boundaries(masks):
+def compute_boundaries(masks, cap=None, return_counts=False):
     """image.py:122-146: masks [N,H,W] -> float32 [N, max_count, 3] = (x, y, valid) of the
     boundary pixels (find_boundaries, mode='thick'), padded to the longest list of the batch.
-    One small device->host read (the counts) sizes the result, like the reference's max()."""
+    One small device->host read (the counts) sizes the result, like the reference's max().
+
+    cap: the fixed-shape form, [N, cap, 3] -- the first `cap` points of every list in row-major order, padded with
+    (-1, -1, 0); no host read (so the call can be captured into a hipGraph) and no scratch beyond the result.
+    return_counts: also the TRUE counts, int32 [N] on the device (a count above cap tells of the overflow)."""
     _lib.require_gpu(masks)
     m = _masks3(masks)
     N, H, W = m.shape
-    cap = H * W
+    fixed = cap is not None
+    cap = int(cap) if fixed else H * W
+    if cap <= 0:
+        raise ValueError("compute_boundaries: cap must be positive")
     out = torch.empty((N, cap, 3), dtype=torch.float32, device=m.device)
     counts = torch.empty((N,), dtype=torch.int32, device=m.device)
     _lib.call("acfm_boundaries", m.device, _lib.ptr(m), N, H, W, cap, _lib.ptr(out), _lib.ptr(counts))
-    max_bd = int(counts.max().item())
-    return out[:, :max_bd].contiguous()
+    if not fixed:
+        max_bd = int(counts.max().item())
+        out = out[:, :max_bd].contiguous()
+    return (out, counts) if return_counts else out

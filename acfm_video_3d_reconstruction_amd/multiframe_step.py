@@ -52,8 +52,12 @@ def _y_rotation_quats(num_guesses):
 
 class MultiframeStep(nn.Module):
     def __init__(self, mean_v, faces, lbs_logits, num_training_frames, img_size=256, vert2kp=None, prior_stream=False,
-                 **opts):
+                 boundary_sampler=None, **opts):
         super().__init__()
+        # boundary_sampling.BoundarySampler: the boundary loss draws its <= n_samples points on the device (main.py:
+        # 715-716 draws on the host), so the step can be captured with batch["boundaries"] of any length; the lists'
+        # true lengths are read from batch.get("boundary_counts") (int32 [B*T] on the device)
+        self.boundary_sampler = boundary_sampler
         o = dict(DEFAULTS)
         o.update(opts)
         self.opts = SimpleNamespace(**o)
@@ -131,7 +135,9 @@ class MultiframeStep(nn.Module):
         # reference's masks / edts / boundaries .repeat(G, ...) copies, main.py:472-479, are not made)
         l1, _, edt = loss_utils.fused_silhouette_losses(mask_pred, batch["masks"], batch["edts_barrier"])
         pred_proj = self.renderer.project_points(pred_v, cam)
-        bdt = loss_utils.bds_loss(pred_proj, batch["boundaries"], faces, pix_to_face, reduce=False)
+        bkw = {} if self.boundary_sampler is None else dict(sampler=self.boundary_sampler,
+                                                            counts=batch.get("boundary_counts"))
+        bdt = loss_utils.bds_loss(pred_proj, batch["boundaries"], faces, pix_to_face, reduce=False, **bkw)
         if parts:
             return mask_pred, l1, edt, bdt
         sil_cons = o.edt_reg_wt * edt + o.bdt_reg_wt * bdt

@@ -170,12 +170,23 @@ def masked_texture_mse(texture_pred, imgs, masks):
     return ops.tex_mse(texture_pred, imgs, masks)
 
 
-def bds_loss(verts, bds, faces, pix_to_face, reduce=True, n_samples=1000, k=1):
+def bds_loss(verts, bds, faces, pix_to_face, reduce=True, n_samples=1000, k=1, sampler=None, counts=None):
     """loss_utils.py:204-237.  verts [B,V,2] projected vertices, bds [B,P,3] = (x, y, valid),
-    pix_to_face [B,H,W,K] (slot 0 = nearest face)."""
+    pix_to_face [B,H,W,K] (slot 0 = nearest face).
+
+    sampler (boundary_sampling.BoundarySampler): the draw of :211 happens on the device and the loss reads the
+    drawn points in place -- no host randperm, no index upload, no gathered copy, so the call can be captured into a
+    hipGraph, and every replay draws afresh.  The subset has the reference's distribution, not its random stream.
+    The sampler's n_samples is used.  counts (int32 [RB] on the device, image_utils.compute_boundaries(...,
+    return_counts=True)): the true list lengths, so that no draw is spent on padding."""
     if k != 1:
         raise NotImplementedError("bds_loss: only k=1 (what the reference uses) is built")
     bt, nv, _ = verts.shape
+    if sampler is not None:
+        vis = ops.visible_vertices(pix_to_face, faces, nv)
+        sel = sampler.draw(bds.shape[1], counts=counts, device=bds.device)
+        loss = ops.bds_loss_per_mesh(verts, bds, vis, sel=sel)
+        return loss.mean() if reduce else loss
     indices = torch.randperm(bds.shape[1])[:n_samples]  # CPU generator, like the reference (:211)
     if bds.shape[1] > n_samples:
         bds = bds[..., indices.to(bds.device), :]
@@ -187,8 +198,9 @@ def bds_loss(verts, bds, faces, pix_to_face, reduce=True, n_samples=1000, k=1):
 
 
 class Boundaries_Loss(nn.Module):
-    def forward(self, verts, bds, faces, pix_to_face, reduce=True, n_samples=1000):
-        return bds_loss(verts, bds, faces, pix_to_face, reduce=reduce, n_samples=n_samples)
+    def forward(self, verts, bds, faces, pix_to_face, reduce=True, n_samples=1000, sampler=None, counts=None):
+        return bds_loss(verts, bds, faces, pix_to_face, reduce=reduce, n_samples=n_samples, sampler=sampler,
+                        counts=counts)
 
 
 def hinge_loss(loss, margin):

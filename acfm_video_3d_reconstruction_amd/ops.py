@@ -1847,9 +1847,78 @@ class _BdsLoss(torch.autograd.Function):
         return gv, None, None
 
 
-def bds_loss_per_mesh(verts_xy, bds, vis):
-    """[N,V,2] x [N,P,3] x uint8 [N,V] -> [N] (sum over boundary points)."""
-    return _BdsLoss.apply(verts_xy, bds, vis)
+class _BdsLossSel(torch.autograd.Function):
+    """_BdsLoss with every point read through a slot list (acfm_bds_loss_sel_ws): no gathered copy of the points."""
+
+    @staticmethod
+    def forward(ctx, verts_xy, bds, vis, sel):
+        _lib.require_gpu(verts_xy, bds, vis, sel)
+        v, b = _f32c(verts_xy), _f32c(bds)
+        N, V, _ = v.shape
+        P = b.shape[1]
+        RB = _ref_batch(N, b, "bds_loss")
+        if sel.dtype != torch.int32 or sel.dim() != 2 or sel.shape[0] not in (1, RB):
+            raise ValueError("bds_loss: sel must be int32 [1, S] or [%d, S], got %s %s"
+                             % (RB, sel.dtype, tuple(sel.shape)))
+        s = sel.contiguous()
+        rows, S = s.shape
+        loss = torch.empty((N,), dtype=torch.float32, device=v.device)
+        arg = torch.empty((N, S), dtype=torch.int32, device=v.device)
+        with torch.cuda.device(v.device):
+            tk, part, nf = _loss_scratch(v.device, _LOSS_BDS, N, S)
+        _lib.call("acfm_bds_loss_sel_ws", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vis.contiguous()), _lib.ptr(s),
+                  N, V, P, RB, rows, S, _lib.ptr(loss), _lib.ptr(arg), _lib.ptr(tk), _lib.ptr(part), nf)
+        ctx.save_for_backward(v, b, s, arg)
+        ctx.rb = RB
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        v, b, s, arg = ctx.saved_tensors
+        N, V, _ = v.shape
+        P = b.shape[1]
+        rows, S = s.shape
+        g = _f32c(gl)
+        gv = torch.empty_like(v)
+        _lib.call("acfm_bds_loss_sel_backward", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(s), _lib.ptr(arg),
+                  _lib.ptr(g), N, V, P, ctx.rb, rows, S, _lib.ptr(gv))
+        return gv, None, None, None
+
+
+def bds_loss_per_mesh(verts_xy, bds, vis, sel=None):
+    """[N,V,2] x [N,P,3] x uint8 [N,V] -> [N] (sum over boundary points).
+    sel (int32 [1,S] or [RB,S], from boundary_subset): only the points whose slots it names are summed, -1 entries
+    are skipped; the points are read in place."""
+    if sel is None:
+        return _BdsLoss.apply(verts_xy, bds, vis)
+    return _BdsLossSel.apply(verts_xy, bds, vis, sel)
+
+
+def boundary_subset(state, P, n_samples, counts=None, per_mesh=False):
+    """The draw of loss_utils.bds_loss (:211, torch.randperm(P)[:n_samples]) on the device -> sel int32
+    [rows, n_samples]: per row a uniform random subset of min(n_samples, P_r) of the slots [0, P_r) in ascending
+    order, then -1.  state: int64 [2] = (seed, draw) on the GPU; the call uses draw = state[1] and advances it by one
+    in stream order (no host synchronisation: a captured call draws afresh at every replay).  counts: int32 [RB] true
+    list lengths, or None.  per_mesh=False: one row for the batch, P_0 = min(P, max(counts)) (the reference's one
+    subset over the padded length when counts is None); per_mesh=True: rows = RB, P_r = min(P, counts[r]).
+    The draws have the reference's distribution, not its random stream; boundary_sampling.subset_host is the
+    definition, index for index."""
+    _lib.require_gpu(state, counts)
+    if state.dtype != torch.int64 or tuple(state.shape) != (2,) or not state.is_contiguous():
+        raise ValueError("boundary_subset: state must be a contiguous int64 [2] tensor (seed, draw)")
+    if per_mesh and counts is None:
+        raise ValueError("boundary_subset: per_mesh=True needs counts")
+    nc = 0
+    if counts is not None:
+        if counts.dtype != torch.int32 or counts.dim() != 1 or counts.device != state.device:
+            raise ValueError("boundary_subset: counts must be int32 [RB] on the state's device")
+        counts = counts.contiguous()
+        nc = counts.shape[0]
+    rows = nc if per_mesh else 1
+    sel = torch.empty((rows, int(n_samples)), dtype=torch.int32, device=state.device)
+    _lib.call("acfm_boundary_subset", state.device, _lib.ptr(state), _lib.ptr(counts), nc, rows, int(P),
+              int(n_samples), _lib.ptr(sel))
+    return sel
 
 
 # ------------------------------------------------------------------------------ mesh priors

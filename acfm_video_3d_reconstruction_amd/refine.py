@@ -14,9 +14,13 @@ from .nnutils import loss_utils
 
 def refine_total(renderer, solver, delta, cam, faces, masks, edts_barrier, boundaries, mask_loss_wt=1.0,
                  boundaries_reg_wt=1.0, edt_reg_wt=0.1, bdt_reg_wt=0.1, of_loss_wt=0.0, optical_flows=None,
-                 of_renderer=None, num_frames=2):
+                 of_renderer=None, num_frames=2, boundary_sampler=None, boundary_counts=None):
     """The loss of one refinement iteration (predictor.py:310-345) for handle offsets `delta` [N,K_h,3] and
-    cameras `cam` [N,7]: -> (total, pred_v).  refine_clip() differentiates exactly this."""
+    cameras `cam` [N,7]: -> (total, pred_v).  refine_clip() differentiates exactly this.
+    boundary_sampler (boundary_sampling.BoundarySampler): the boundary loss draws its points on the device, afresh
+    at every iteration as the reference does (:321) -- needed to capture the iteration when boundaries holds more
+    than n_samples points; boundary_counts: the lists' true lengths (int32 [N] on the device) for it."""
+    bkw = {} if boundary_sampler is None else dict(sampler=boundary_sampler, counts=boundary_counts)
     pred_v = solver(delta)                                                    # predictor.py:310-315
     mask_pred, pix_to_face = renderer(pred_v, faces, cam)                     # :317
     pred_proj = renderer.project_points(pred_v, cam)                          # :319
@@ -27,12 +31,12 @@ def refine_total(renderer, solver, delta, cam, faces, masks, edts_barrier, bound
     # reduction launches on N-element vectors.
     if mask_pred.is_cuda:
         raw = loss_utils.fused_silhouette_losses(mask_pred, masks, edts_barrier, raw=True)   # (l1, ., ., edt) per frame
-        bdt = loss_utils.bds_loss(pred_proj, boundaries, faces, pix_to_face, reduce=False)   # :321
+        bdt = loss_utils.bds_loss(pred_proj, boundaries, faces, pix_to_face, reduce=False, **bkw)   # :321
         total = loss_utils.combine_losses([raw, bdt], [mask_loss_wt, 0.0, 0.0, boundaries_reg_wt * bdt_reg_wt,
                                                        boundaries_reg_wt * edt_reg_wt])
     else:
         l1, _, edt = loss_utils.fused_silhouette_losses(mask_pred, masks, edts_barrier)
-        bdt_loss = loss_utils.bds_loss(pred_proj, boundaries, faces, pix_to_face)  # :321
+        bdt_loss = loss_utils.bds_loss(pred_proj, boundaries, faces, pix_to_face, **bkw)  # :321
         per_frame = mask_loss_wt * l1 + (boundaries_reg_wt * bdt_reg_wt) * edt
         total = per_frame.mean() + (boundaries_reg_wt * edt_reg_wt) * bdt_loss
     if of_loss_wt > 0 and optical_flows is not None:
@@ -56,9 +60,12 @@ class ClipRefiner:
     def __init__(self, renderer, solver, delta_v_res, cam_pred, faces, masks, edts_barrier, boundaries,
                  optimize_camera=False, mask_loss_wt=1.0, boundaries_reg_wt=1.0, edt_reg_wt=0.1, bdt_reg_wt=0.1,
                  of_loss_wt=0.0, optical_flows=None, of_renderer=None, num_frames=2, lr=5e-3, capturable=False,
-                 log_len=1):
+                 log_len=1, boundary_sampler=None, boundary_counts=None):
         self.args = (renderer, solver, faces, masks, edts_barrier, boundaries)
-        self.kw = (mask_loss_wt, boundaries_reg_wt, edt_reg_wt, bdt_reg_wt, of_loss_wt, optical_flows, of_renderer, num_frames)
+        self.kw = (mask_loss_wt, boundaries_reg_wt, edt_reg_wt, bdt_reg_wt, of_loss_wt, optical_flows, of_renderer, num_frames,
+                   boundary_sampler, boundary_counts)
+        if boundary_sampler is not None and delta_v_res.is_cuda:
+            boundary_sampler.state_on(delta_v_res.device)   # the state exists before any capture
         self.delta = delta_v_res.clone().detach().requires_grad_(True)
         params = [self.delta]
         self.optimize_camera = optimize_camera
@@ -130,19 +137,22 @@ class ClipRefiner:
 def refine_clip(renderer, solver, delta_v_res, cam_pred, faces, masks, edts_barrier, boundaries,
                 num_optim_iter=20, optimize_camera=False, mask_loss_wt=1.0, boundaries_reg_wt=1.0,
                 edt_reg_wt=0.1, bdt_reg_wt=0.1, of_loss_wt=0.0, optical_flows=None, of_renderer=None,
-                num_frames=2, lr=5e-3, use_graph=False):
+                num_frames=2, lr=5e-3, use_graph=False, boundary_sampler=None, boundary_counts=None):
     """delta_v_res [N,K_h,3] predicted handle offsets, cam_pred [N,7], masks [N,H,W],
     edts_barrier [N,1,H,W], boundaries [N,P,3]; optional optical_flows [b,T,H,W,2].
     use_graph=True captures one whole iteration (render, losses, backward, Adam update) into a
     hipGraph after three eager iterations and replays it for the rest: the loop is launch-bound
     (~30 short kernels per iteration) and every entry point is stream-ordered, so the replayed
     iterations perform exactly the eager sequence of updates without returning to Python.
+    boundary_sampler / boundary_counts: see refine_total (with more than n_samples boundary points per frame the
+    iteration can only be captured with a sampler: the host draw is an upload).
     Returns (pred_v, cam, delta, history of total losses)."""
     graphable = use_graph and delta_v_res.is_cuda
     r = ClipRefiner(renderer, solver, delta_v_res, cam_pred, faces, masks, edts_barrier, boundaries,
                     optimize_camera=optimize_camera, mask_loss_wt=mask_loss_wt, boundaries_reg_wt=boundaries_reg_wt,
                     edt_reg_wt=edt_reg_wt, bdt_reg_wt=bdt_reg_wt, of_loss_wt=of_loss_wt, optical_flows=optical_flows,
-                    of_renderer=of_renderer, num_frames=num_frames, lr=lr, capturable=graphable, log_len=num_optim_iter)
+                    of_renderer=of_renderer, num_frames=num_frames, lr=lr, capturable=graphable, log_len=num_optim_iter,
+                    boundary_sampler=boundary_sampler, boundary_counts=boundary_counts)
     done = 0
     if graphable and num_optim_iter > 3:
         done = r.capture(3)

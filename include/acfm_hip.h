@@ -80,6 +80,7 @@ int acfm_stream_capture_id(void* stream, unsigned long long* id_host);
 #define ACFM_PROF_SOLVE_BWD 18
 #define ACFM_PROF_FRAG_FWD 19
 #define ACFM_PROF_FRAG_BWD 20
+#define ACFM_PROF_BDS_SUBSET 21
 #define ACFM_PROF_NKERNELS 24
 #define ACFM_PROF_RING 8192
 int acfm_prof_enable(int on);
@@ -631,6 +632,38 @@ int acfm_bds_loss_ws(const float* verts_xy, const float* bds, const uint8_t* vis
 int acfm_bds_loss_backward(const float* verts_xy, const float* bds, const int32_t* argmin,
                            const float* grad_loss, int N, int V, int P, int ref_batch, float* grad_verts_xy,
                            void* stream);
+/* The boundary loss over a SUBSET of each reference's points, named by slot lists (acfm_boundary_subset below)
+ * instead of a gathered copy -- replaces `indices = torch.randperm(P)[:n_samples]; bds = bds[..., indices, :]` of
+ * loss_utils.bds_loss (:211-213) together with the distance search that follows it (:226-237).
+ *   sel [rows,S] i32, rows = 1 (one list for every reference) or rows = ref_batch (reference b reads row b): entry p
+ *   names slot sel[((n % ref_batch) % rows) S + p] of bds [ref_batch,P,3]; an entry < 0 (or >= P) is empty: it adds 0
+ *   and its argmin is -1.  loss [N], argmin [N,S] i32.  Scratch as for acfm_bds_loss_ws with n = S
+ *   (acfm_loss_partial_floats(ACFM_LOSS_BDS, N, S)); LDS limits as for acfm_bds_loss. */
+int acfm_bds_loss_sel_ws(const float* verts_xy, const float* bds, const uint8_t* vis, const int32_t* sel, int N, int V,
+                         int P, int ref_batch, int rows, int S, float* loss, int32_t* argmin, uint32_t* tickets,
+                         float* partials, size_t partial_floats, void* stream);
+int acfm_bds_loss_sel_backward(const float* verts_xy, const float* bds, const int32_t* sel, const int32_t* argmin,
+                               const float* grad_loss, int N, int V, int P, int ref_batch, int rows, int S,
+                               float* grad_verts_xy, void* stream);
+/* acfm_boundary_subset: the draw itself, `torch.randperm(P)[:n_samples]` of loss_utils.bds_loss (:211), on the device:
+ * a uniform random subset of min(n_samples, P_r) of the slots [0, P_r) of every row r, without replacement, written
+ * in ascending slot order and followed by -1.  sel [rows,n_samples] i32.
+ *   state  int64[2] on the device = (seed, draw).  The call uses draw = state[1] and leaves state[1] one higher (a
+ *          launch of its own behind the draw, in stream order: no host synchronisation, and a captured call draws
+ *          a fresh subset at every replay, as the reference redraws at every call).
+ *   counts i32 [n_counts] true list lengths (acfm_boundaries), or NULL with n_counts = 0.
+ *   rows = 1        one subset for the whole batch, as in the reference: P_0 = min(P, max(counts)), or P without counts;
+ *   rows = n_counts one subset per reference over ITS OWN points: P_r = min(P, counts[r]) -- every frame gets n_samples
+ *                   real points instead of spending draws on the padding.
+ *   A row with P_r = 0 is all -1.
+ * Definition: slot i of row r in draw t has the 64-bit key x0 << 32 | x1 of Philox4x32-10 (Salmon et al., SC'11) with
+ * key (seed's low word, seed's high word) and counter (i, r, t's low word, t's high word); the subset is the slots
+ * with the min(n_samples, P_r) smallest (key, i).  boundary_sampling.subset_host restates this in numpy and is the
+ * specification: the kernel equals it index for index.  The draws follow the reference's DISTRIBUTION, not its
+ * random stream (as pytorch3d_shim's sample_points_from_meshes).  P <= 2^30; one workgroup per row, no storage
+ * sized by P. */
+int acfm_boundary_subset(int64_t* state, const int32_t* counts, int n_counts, int rows, int P, int n_samples,
+                         int32_t* sel, void* stream);
 
 /* ---- mesh priors -------------------------------------------------------------------------
  * Packed meshes: verts [P,3] f32, faces [F,3] / edges [E,2] i64 with packed vertex ids.
