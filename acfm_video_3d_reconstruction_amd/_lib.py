@@ -131,6 +131,8 @@ SIGNATURES = {
     "acfm_uv_atlas_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "acfm_geodesic_lds_bytes": (_sz, [_i, _i, _i]),
     "acfm_geodesic_distances": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "acfm_geodesic_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "acfm_geodesic_distances_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "acfm_lpips_input_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "acfm_lpips_input_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "acfm_lpips_layer_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),

@@ -82,15 +82,28 @@ def _host_distances(verts, faces, m, sources):
     return dijkstra(g, directed=False, indices=src)[:, :V]
 
 
-def geodesic_distance_matrix(verts, faces, steiner=15, sources=None):
+MEMORY = ("lds", "device", "auto")   # ops.GEODESIC_MEMORY (this module imports without the library)
+
+
+def _memory(memory):
+    if memory not in MEMORY:
+        raise ValueError('memory must be one of "lds", "device", "auto", got %r' % (memory,))
+    return memory
+
+
+def geodesic_distance_matrix(verts, faces, steiner=15, sources=None, memory="auto"):
     """D [S,V]: D[s,v] = the edge-Steiner distance from vertex sources[s] (None = all V) to vertex v, +inf between
     components.  GPU tensors -> ops.geodesic_distances (float32 tensor on the device; verts may be [N,V,3]); arrays or
-    host tensors -> float64 through scipy (an array for arrays, a tensor for tensors)."""
+    host tensors -> float64 through scipy (an array for arrays, a tensor for tensors).
+    memory: where the GPU kernel keeps the node distances -- "lds" (refused when the graph does not fit a workgroup's
+    LDS), "device" (a workspace, any graph) or "auto" (LDS where it fits: the same bits either way).  The host path
+    only validates it."""
     m = _steiner(steiner)
+    _memory(memory)
     if torch.is_tensor(verts) and verts.is_cuda:
         from . import ops
         f = faces if torch.is_tensor(faces) else torch.as_tensor(np.asarray(faces), device=verts.device)
-        return ops.geodesic_distances(verts, f, m, sources)
+        return ops.geodesic_distances(verts, f, m, sources, memory=memory)
     as_tensor = torch.is_tensor(verts)
     v = verts.detach().cpu().numpy() if torch.is_tensor(verts) else verts
     f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else faces
@@ -133,18 +146,19 @@ def lbs_logits_from_distances(D, idx_pts, pp=16):
     return torch.log(torch.clamp(w, min=1e-10))
 
 
-def geodesic_lbs_logits(verts, faces, num_lbs, pp=16, steiner=15):
+def geodesic_lbs_logits(verts, faces, num_lbs, pp=16, steiner=15, memory="auto"):
     """mesh_net.py:523-544: idx_pts = sorted(farthest_point_sampling(D, num_lbs - 1)), D the distance matrix of the
     template; logits = log(clamp(1 / D[:, idx_pts] ** pp, 1e-10)) with each handle's own row at its column maximum.
     -> (logits [V,num_lbs] float32 -- a tensor on verts' device for tensors, an array for arrays --, idx_pts int64 array).
     The logits are what deform.DeformSolver / MultiframeStep take as lbs_logits.  ValueError on a mesh that is not
-    connected."""
+    connected.  memory: as geodesic_distance_matrix (with "auto" the 2562-vertex template runs at the default steiner)."""
+    _memory(memory)
     num_lbs = int(num_lbs)
     if num_lbs < 1:
         raise ValueError("num_lbs must be at least 1, got %d" % num_lbs)
     if (verts.dim() if torch.is_tensor(verts) else np.asarray(verts).ndim) != 2:
         raise ValueError("geodesic_lbs_logits: one template, verts [V,3], expected")
-    D = geodesic_distance_matrix(verts, faces, steiner)
+    D = geodesic_distance_matrix(verts, faces, steiner, memory=memory)
     idx_pts = np.sort(farthest_point_sampling(D, num_lbs - 1))
     logits = lbs_logits_from_distances(D, idx_pts, pp)
     return (logits if torch.is_tensor(verts) else logits.numpy()), idx_pts

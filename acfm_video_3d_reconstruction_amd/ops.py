@@ -2135,7 +2135,24 @@ def geodesic_max_steiner(V, E):
     return max(fits) if fits else -1
 
 
-def geodesic_distances(verts, faces, steiner=15, sources=None):
+GEODESIC_MEMORY = ("lds", "device", "auto")
+
+
+def geodesic_memory(memory):
+    """`memory` of geodesic_distances, validated: one of "lds", "device", "auto"."""
+    if memory not in GEODESIC_MEMORY:
+        raise ValueError('memory must be one of "lds", "device", "auto", got %r' % (memory,))
+    return memory
+
+
+def geodesic_device_workgroups(items, max_workgroups=None):
+    """The grid of the device-memory kernel for `items` = S N (source, mesh) pairs: min(items, max_workgroups),
+    max_workgroups None = two per CU of the current device."""
+    one = int(_lib.lib().acfm_geodesic_workspace_bytes(1, 1, 0, 0, 1, 1))
+    return int(_lib.lib().acfm_geodesic_workspace_bytes(1, 1, 0, 0, int(items), int(max_workgroups or 0))) // one
+
+
+def geodesic_distances(verts, faces, steiner=15, sources=None, memory="lds", max_workgroups=None):
     """Surface distances between the vertices of a mesh, for the handle weights of mesh_net.py:69-85, 523-544 (there
     gdist.local_gdist_matrix): shortest paths on the edge-Steiner graph -- `steiner` = m points on every edge, inside
     every face all pairs of its 3 + 3 m boundary nodes joined by their Euclidean distance.  An upper bound of the exact
@@ -2143,8 +2160,12 @@ def geodesic_distances(verts, faces, steiner=15, sources=None):
     diagonal; the same bits on every run.
     verts [V,3] or [N,V,3] float32 on the GPU, faces [F,3] (one topology for all N), sources: None (all V vertices) or
     S vertex ids (a sequence or an integer tensor; any order, repeats allowed) -> [S,V] or [N,S,V] float32, detached (the
-    reference computes these in numpy).  One launch, one workgroup per (source, mesh), the graph in LDS: a graph of
-    more than 153,584 / 4 nodes is refused with the largest steiner count that fits.
+    reference computes these in numpy).
+    memory = "lds": one launch, one workgroup per (source, mesh), the graph in LDS: a graph of more than 153,584 / 4
+    nodes is refused with the largest steiner count that fits.  "device": the same relaxation with the distances in a
+    per-call workspace (one row of V + m E floats per resident workgroup), any graph, the same bits; a persistent grid
+    of min(S N, max_workgroups) workgroups, max_workgroups None = two per CU.  "auto": "lds" where the graph fits,
+    else "device".
     The int32 edge tables are built once per faces tensor (Meshes.geodesic_tables_packed) and `sources` is uploaded per
     call: inside a graph capture the op runs only when the tables exist and `sources` is None or an int32 tensor on the
     device, and it raises otherwise."""
@@ -2165,6 +2186,9 @@ def geodesic_distances(verts, faces, steiner=15, sources=None):
     if m != steiner or not 0 <= m <= GEODESIC_MAX_STEINER:
         raise ValueError("steiner must be an integer in [0, %d] (3 steiner + 3 nodes per face, one wave), got %r"
                          % (GEODESIC_MAX_STEINER, steiner))
+    geodesic_memory(memory)
+    if max_workgroups is not None and (int(max_workgroups) != max_workgroups or int(max_workgroups) < 1):
+        raise ValueError("max_workgroups must be None or a positive integer, got %r" % (max_workgroups,))
     dev = verts.device
     v = verts.detach().contiguous()
     batched = v.dim() == 3
@@ -2183,7 +2207,8 @@ def geodesic_distances(verts, faces, steiner=15, sources=None):
     F_, E = f32.shape[0], e32.shape[0]
     with torch.cuda.device(dev):
         need = int(_lib.lib().acfm_geodesic_lds_bytes(V, E, m))
-    if need == 0 or need > GEODESIC_LDS_MAX:
+    fits = 0 < need <= GEODESIC_LDS_MAX
+    if memory == "lds" and not fits:
         raise ValueError("geodesic_distances: %d vertices + %d x %d edge points need %d bytes of LDS, a workgroup has %d; "
                          "the largest steiner that fits this mesh is %d" % (V, m, E, 16 + 4 * (V + m * E),
                                                                            GEODESIC_LDS_MAX, geodesic_max_steiner(V, E)))
@@ -2205,8 +2230,19 @@ def geodesic_distances(verts, faces, steiner=15, sources=None):
     S = V if src is None else src.shape[0]
     out = torch.empty((N, S, V), dtype=torch.float32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.call("acfm_geodesic_distances", dev, _lib.ptr(v3), _lib.ptr(f32), _lib.ptr(e32), _lib.ptr(fe32), N, V, F_, E, m,
-              _lib.ptr(src), S, _lib.ptr(out), _lib.ptr(status))
+    if memory == "lds" or (memory == "auto" and fits):
+        _lib.call("acfm_geodesic_distances", dev, _lib.ptr(v3), _lib.ptr(f32), _lib.ptr(e32), _lib.ptr(fe32), N, V, F_, E,
+                  m, _lib.ptr(src), S, _lib.ptr(out), _lib.ptr(status))
+    else:
+        cap = int(max_workgroups or 0)
+        with torch.cuda.device(dev):
+            ws_bytes = int(_lib.lib().acfm_geodesic_workspace_bytes(N, V, E, m, S, cap))
+        if ws_bytes == 0:
+            raise ValueError("geodesic_distances: no workspace size for N = %d, V = %d, E = %d, steiner = %d, S = %d"
+                             % (N, V, E, m, S))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.call("acfm_geodesic_distances_dev", dev, _lib.ptr(v3), _lib.ptr(f32), _lib.ptr(e32), _lib.ptr(fe32), N, V,
+                  F_, E, m, _lib.ptr(src), S, _lib.ptr(out), _lib.ptr(status), cap, _lib.ptr(ws), ws_bytes)
     if not capturing:       # (a captured call cannot read it: a workgroup that gave up leaves a row of NaN)
         st = int(status.item())
         if st:

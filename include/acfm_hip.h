@@ -785,7 +785,8 @@ int acfm_uv_atlas_backward(const float* grad_atlas, const float* atlas, const fl
  *   on the order of the relaxations: the same bits on every run.
  * One launch, one workgroup per (source, mesh): all node distances in dynamic LDS, acfm_geodesic_lds_bytes(V, E, m) =
  *   16 + 4 (V + m E) bytes (0 for arguments out of range), at most ACFM_GEODESIC_LDS_MAX; a graph that does not fit is
- *   ACFM_E_BADARG -- there is no global-memory variant.  No global atomics, nothing shared between workgroups.
+ *   ACFM_E_BADARG here -- acfm_geodesic_distances_dev below takes it.  No global atomics, nothing shared between
+ *   workgroups.
  * status: one i32 on the device, ZERO before the call.  It stays 0 unless a workgroup gave up: 1 = not converged after
  *   V + m E sweeps (the Bellman-Ford bound: cannot happen with arcs >= 0), 2 = a source outside [0, V); that
  *   workgroup's row is NaN.  A face with a table entry out of range is left out of the graph, never dereferenced. */
@@ -795,6 +796,20 @@ size_t acfm_geodesic_lds_bytes(int V, int E, int m);
 int acfm_geodesic_distances(const float* verts, const int32_t* faces, const int32_t* edges, const int32_t* face_edges,
                             int N, int V, int F, int E, int m, const int32_t* sources, int S, float* out,
                             int32_t* status, void* stream);
+/* The same distances, bit for bit (the least fixed point of the same operator with the same arc arithmetic), for a graph
+ * of any size: the node distances of a workgroup's current (source, mesh) item live in its own row of `ws`, LDS holds
+ * only the sweep flags and the clean-face signatures.  One launch of G = min(S N, max_workgroups) persistent
+ * workgroups (max_workgroups = 0: two per CU of the current device); workgroup g takes items g, g + G, ... in order and
+ * refills its row with +inf for each.  Rows are private, there are no tickets; distances are read, filled and lowered
+ * with agent-scope atomics only (the loads bypass the CU's L1: DESIGN.md "Geodesic handles").
+ * acfm_geodesic_workspace_bytes: G rows of 4 (V + m E) bytes, each rounded up to 128; 0 for arguments out of range.
+ *   ws: that many bytes on the device, 128-byte aligned, any contents; fewer is ACFM_E_WORKSPACE.
+ * Arguments, out, status: as acfm_geodesic_distances. */
+size_t acfm_geodesic_workspace_bytes(int N, int V, int E, int m, int S, int max_workgroups);
+int acfm_geodesic_distances_dev(const float* verts, const int32_t* faces, const int32_t* edges,
+                                const int32_t* face_edges, int N, int V, int F, int E, int m, const int32_t* sources,
+                                int S, float* out, int32_t* status, int max_workgroups, void* ws, size_t ws_bytes,
+                                void* stream);
 
 /* ---- perceptual texture loss: the tail of LPIPS (multiframe/nnutils/loss_utils.py:359-383) --------
  * replaces everything lpips.LPIPS(net='alex', lpips=False, spatial=True) and its caller do around AlexNet's five
