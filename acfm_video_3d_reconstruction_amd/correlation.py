@@ -1,11 +1,25 @@
 """Drop-in for multiframe/data/optical_flow/model/correlation_package/correlation.py (the one
 native extension of the reference tree): `Correlation(pad_size, kernel_size, max_displacement,
 stride1, stride2, corr_multiply)` with the configuration MaskFlownet uses (MaskFlownet.py:116, 416:
-pad_size = max_displacement, kernel_size = 1, strides 1).  Forward only: ACFM never trains the flow
-network, the reference's backward kernels are never executed."""
+pad_size = max_displacement, kernel_size = 1, strides 1).  Forward only (ACFM never trains the flow network) unless
+`flow_ops.trainable()` is on: then GPU calls that need gradients run the backward kernel, as the reference's
+CorrelationFunction.backward does (correlation.py:38-52)."""
+import torch
+import torch.nn.functional as F
 from torch import nn
 
 from . import ops
+
+
+def correlation_torch(f1, f2, md):
+    """The operator's definition in torch ops, on any device and in any float dtype: zero-pad f2 by md, take the
+    (2md+1)^2 shifted products and the mean over C; channel (tj+md)(2md+1) + (ti+md) pairs f1[y,x] with f2[y+tj,x+ti].
+    Differentiable like any torch expression: the tests' float64 reference and the benchmark's baseline."""
+    md = int(md)
+    H, W = f1.shape[-2:]
+    p2 = F.pad(f2, (md, md, md, md))
+    return torch.stack([(f1 * p2[..., tj:tj + H, ti:ti + W]).mean(1)
+                        for tj in range(2 * md + 1) for ti in range(2 * md + 1)], 1)
 
 
 class Correlation(nn.Module):

@@ -1,11 +1,18 @@
 """Drop-in for the one thing MaskFlownet takes from torchvision (`from torchvision import ops`, MaskFlownet.py:6):
 `ops.DeformConv2d` and `ops.deform_conv2d`, in the configuration the network uses (MaskFlownet.py:36-37, 488-492:
 kernel 3x3, stride 1, padding 1, dilation 1, groups 1, one offset group, no modulation mask).  GPU tensors take the
-HIP kernel (ops.deform_conv2d, forward only: ACFM never trains the flow network); host tensors take the same
+HIP kernel (ops.deform_conv2d; forward only, as ACFM never trains the flow network, unless `trainable()` below is on:
+then calls that need gradients run the backward kernels); host tensors take the same
 definition written with torch ops (nine grid_sample calls and an einsum), differentiable like any torch expression,
 so the module can be built and checked without a GPU.  An offset with 2 channels is the shared form: every tap reads
 the same (row, column) offset, which is what MaskFlownet's `repeat_interleave(flow.unsqueeze(1), 9, 1).view(..)`
-(= `flow.repeat(1, 9, 1, 1)`) expresses."""
+(= `flow.repeat(1, 9, 1, 1)`) expresses.
+
+Fine-tuning the flow network: `flow_ops.set_trainable(True)` (or `with flow_ops.trainable():`) switches the GPU path
+of DeformConv2d, deform_conv2d, warp_correlate and correlation.Correlation from refusing autograd to the backward
+kernels.  The switch is process-wide, read at every call, and not thread-local (nn.DataParallel's replica threads see
+it); the default is off, so a frozen network never pays for saved tensors."""
+import contextlib
 import math
 
 import torch
@@ -16,6 +23,26 @@ from . import ops
 
 _BUILT = ("only MaskFlownet's configuration is built (kernel_size=3, stride=1, padding=1, dilation=1, groups=1, "
           "one offset group: an offset of 18 channels, or of 2 shared by the nine taps; no mask)")
+
+
+def set_trainable(flag):
+    """Turn the backward kernels of the flow operators on or off for the whole process -> the previous value."""
+    previous, ops._FLOW_TRAINABLE = ops._FLOW_TRAINABLE, bool(flag)
+    return previous
+
+
+def is_trainable():
+    return ops._FLOW_TRAINABLE
+
+
+@contextlib.contextmanager
+def trainable(flag=True):
+    """with flow_ops.trainable(): ...   -- set_trainable(flag) for the block, the previous value afterwards."""
+    previous = set_trainable(flag)
+    try:
+        yield
+    finally:
+        set_trainable(previous)
 
 
 def _pair(v):
@@ -115,6 +142,7 @@ class DeformConv2d(nn.Module):
 def warp_correlate(c1, c2, flow, deform, md):
     """One pyramid level's warp and cost volume (MaskFlownet.py:558-564 and the four blocks after it):
     warp = leaky_relu(deform(c2, flow)), with flow [B,2,H,W] (the reference's `flow * self.scale / stride`) handed over
-    as the shared offset instead of its ninefold copy, then leaky_relu(correlation(c1, warp, md)); both slopes 0.1."""
+    as the shared offset instead of its ninefold copy, then leaky_relu(correlation(c1, warp, md)); both slopes 0.1.
+    Under `trainable()` gradients reach c1, c2, flow and the layer's parameters."""
     warp = F.leaky_relu(deform(c2, flow), 0.1)
     return F.leaky_relu(ops.correlation(c1, warp, md), 0.1)

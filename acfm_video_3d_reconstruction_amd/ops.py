@@ -674,35 +674,74 @@ def of_loss(proj, flows, vis, B, T, masks=None, flip_t=False):
     return _OFLoss.apply(proj, flows, vis, int(B), int(T), masks, bool(flip_t))
 
 
+# ------------------------------------------------------------------------------ flow operators: the switch
+# Process-wide and read at call time (flow_ops.set_trainable / flow_ops.trainable are its public face).  Deliberately not
+# thread-local: nn.DataParallel's replica threads must see what the main thread set.
+_FLOW_TRAINABLE = False
+
+_FORWARD_ONLY = ("%s: forward only (frozen flow network); wrap the call in torch.no_grad(), or opt in to the backward "
+                 "kernels with flow_ops.set_trainable(True) / `with flow_ops.trainable():`")
+
+
+def _once(fn):
+    return torch.autograd.function.once_differentiable(fn)
+
+
 # ------------------------------------------------------------------------------ correlation
-def correlation(f1, f2, max_displacement):
-    """Cost volume of MaskFlownet's Correlation layer (pad = max_displacement = md, kernel 1, strides 1):
-    f1, f2 [N,C,H,W] -> [N,(2md+1)^2,H,W].  Forward only (the flow network is frozen in ACFM)."""
+def _correlation_args(f1, f2, max_displacement):
     _lib.require_gpu(f1, f2)
-    if f1.requires_grad or f2.requires_grad:
-        if torch.is_grad_enabled():
-            raise RuntimeError("correlation: forward only (frozen flow network); wrap the call in torch.no_grad()")
     a, b = _f32c(f1), _f32c(f2)
     if a.dim() != 4 or a.shape != b.shape:
         raise ValueError("correlation: two [N,C,H,W] tensors of equal shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    return a, b, int(max_displacement)
+
+
+def _correlation_forward(a, b, md):
     N, C, H, W = a.shape
-    md = int(max_displacement)
     out = torch.empty((N, (2 * md + 1) ** 2, H, W), dtype=torch.float32, device=a.device)
     _lib.call("acfm_correlation_forward", a.device, _lib.ptr(a), _lib.ptr(b), N, C, H, W, md, _lib.ptr(out))
     return out
 
 
+class _Correlation(torch.autograd.Function):
+    """Saves f1 and f2 only; the backward computes the side(s) asked for, each with its own launch."""
+
+    @staticmethod
+    def forward(ctx, f1, f2, md):
+        a, b, md = _correlation_args(f1, f2, md)
+        ctx.save_for_backward(a, b)
+        ctx.md, ctx.dtypes = md, (f1.dtype, f2.dtype)
+        return _correlation_forward(a, b, md)
+
+    @staticmethod
+    @_once
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        N, C, H, W = a.shape
+        go = _f32c(g)
+        g1 = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        g2 = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        _lib.call("acfm_correlation_backward", a.device, _lib.ptr(go), _lib.ptr(a), _lib.ptr(b), N, C, H, W, ctx.md,
+                  _lib.ptr(g1), _lib.ptr(g2))
+        return (None if g1 is None else g1.to(ctx.dtypes[0]), None if g2 is None else g2.to(ctx.dtypes[1]), None)
+
+
+def correlation(f1, f2, max_displacement):
+    """Cost volume of MaskFlownet's Correlation layer (pad = max_displacement = md, kernel 1, strides 1):
+    f1, f2 [N,C,H,W] -> [N,(2md+1)^2,H,W].  Forward only (the flow network is frozen in ACFM) unless
+    `flow_ops.trainable()` is on: then a call that needs gradients goes through the backward kernel
+    (acfm_correlation_backward: both sides are fixed-order gathers, bit-reproducible), with the same forward bits."""
+    if torch.is_grad_enabled() and (f1.requires_grad or f2.requires_grad):
+        _lib.require_gpu(f1, f2)
+        if not _FLOW_TRAINABLE:
+            raise RuntimeError(_FORWARD_ONLY % "correlation")
+        return _Correlation.apply(f1, f2, int(max_displacement))
+    return _correlation_forward(*_correlation_args(f1, f2, max_displacement))
+
+
 # ------------------------------------------------------------------------------ deformable convolution
-def deform_conv2d(input, offset, weight, bias=None, shared_offset=False):
-    """torchvision's deform_conv2d in MaskFlownet's configuration (3x3, stride 1, padding 1, dilation 1, one group,
-    one offset group, no mask): input [N,Cin,H,W], offset [N,18,H,W] (channel 2t the row offset, 2t+1 the column
-    offset of tap t = 3 ky + kx), weight [Cout,Cin,3,3], bias [Cout] or None -> [N,Cout,H,W].  shared_offset: offset
-    is [N,2,H,W] and every tap reads it -- offset.repeat(1, 9, 1, 1), which is what MaskFlownet's unsqueeze(1) /
-    repeat_interleave(.., 9, 1) / view builds, without the copy and with the same bits.  Forward only (the flow
-    network is frozen in ACFM)."""
+def _dconv_args(input, offset, weight, bias, shared_offset):
     _lib.require_gpu(input, offset, weight, bias)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, offset, weight, bias)):
-        raise RuntimeError("deform_conv2d: forward only (frozen flow network); wrap the call in torch.no_grad()")
     x, o, w = _f32c(input), _f32c(offset), _f32c(weight)
     b = None if bias is None else _f32c(bias)
     if x.dim() != 4:
@@ -719,10 +758,64 @@ def deform_conv2d(input, offset, weight, bias=None, shared_offset=False):
         raise ValueError("deform_conv2d: bias must be [%d], got %s" % (Cout, tuple(b.shape)))
     if min(N, Cin, H, W, Cout) < 1:
         raise ValueError("deform_conv2d: empty input %s or weight %s" % (tuple(x.shape), tuple(w.shape)))
+    return x, o, w, b
+
+
+def _dconv_forward(x, o, w, b, shared_offset):
+    (N, Cin, H, W), Cout = x.shape, w.shape[0]
     out = torch.empty((N, Cout, H, W), dtype=torch.float32, device=x.device)
     _lib.call("acfm_deform_conv2d_forward", x.device, _lib.ptr(x), _lib.ptr(o), _lib.ptr(w), _lib.ptr(b), N, Cin, H, W,
               Cout, 1 if shared_offset else 0, _lib.ptr(out))
     return out
+
+
+class _DeformConv2d(torch.autograd.Function):
+    """Saves input, offset and weight only (no columns, no tap tables: the backward recomputes the sampling)."""
+
+    @staticmethod
+    def forward(ctx, input, offset, weight, bias, shared_offset):
+        x, o, w, b = _dconv_args(input, offset, weight, bias, shared_offset)
+        ctx.save_for_backward(x, o, w)
+        ctx.shared = bool(shared_offset)
+        ctx.dtypes = tuple(None if t is None else t.dtype for t in (input, offset, weight, bias))
+        return _dconv_forward(x, o, w, b, shared_offset)
+
+    @staticmethod
+    @_once
+    def backward(ctx, g):
+        x, o, w = ctx.saved_tensors
+        (N, Cin, H, W), Cout = x.shape, w.shape[0]
+        need = ctx.needs_input_grad
+        go = _f32c(g)                                      # (the stride-0 gradient of out.sum() becomes a real tensor)
+        new = lambda t, on: torch.empty_like(t) if on else None
+        gx, goff, gw = new(x, need[0]), new(o, need[1]), new(w, need[2])
+        gb = torch.empty((Cout,), dtype=torch.float32, device=x.device) if need[3] else None
+        ws, nbytes = None, 0
+        if gw is not None:
+            nbytes = int(_lib.lib().acfm_deform_conv2d_backward_workspace_bytes(N, Cin, H, W, Cout))
+            ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device)
+        _lib.call("acfm_deform_conv2d_backward", x.device, _lib.ptr(go), _lib.ptr(x), _lib.ptr(o), _lib.ptr(w), N, Cin, H,
+                  W, Cout, 1 if ctx.shared else 0, _lib.ptr(gx), _lib.ptr(goff), _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(ws),
+                  nbytes)
+        return tuple(None if t is None else t.to(dt) for t, dt in zip((gx, goff, gw, gb), ctx.dtypes)) + (None,)
+
+
+def deform_conv2d(input, offset, weight, bias=None, shared_offset=False):
+    """torchvision's deform_conv2d in MaskFlownet's configuration (3x3, stride 1, padding 1, dilation 1, one group,
+    one offset group, no mask): input [N,Cin,H,W], offset [N,18,H,W] (channel 2t the row offset, 2t+1 the column
+    offset of tap t = 3 ky + kx), weight [Cout,Cin,3,3], bias [Cout] or None -> [N,Cout,H,W].  shared_offset: offset
+    is [N,2,H,W] and every tap reads it -- offset.repeat(1, 9, 1, 1), which is what MaskFlownet's unsqueeze(1) /
+    repeat_interleave(.., 9, 1) / view builds, without the copy and with the same bits.  Forward only (the flow
+    network is frozen in ACFM) unless `flow_ops.trainable()` is on: then a call that needs gradients goes through
+    acfm_deform_conv2d_backward with the same forward bits (the shared form gets the gradient of the [N,2,H,W] offset
+    itself; grad_input is added atomically and does not repeat its bits, the other gradients do; at an integer sample
+    coordinate the offset gradient is the floor cell's, torchvision's convention)."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, offset, weight, bias)):
+        _lib.require_gpu(input, offset, weight, bias)
+        if not _FLOW_TRAINABLE:
+            raise RuntimeError(_FORWARD_ONLY % "deform_conv2d")
+        return _DeformConv2d.apply(input, offset, weight, bias, bool(shared_offset))
+    return _dconv_forward(*_dconv_args(input, offset, weight, bias, shared_offset), shared_offset)
 
 
 # ------------------------------------------------------------------------------ lazy pix_to_face

@@ -125,17 +125,26 @@ int acfm_deform_apply_backward(const float* P, const float* delta, const float* 
 int acfm_deform_presolve_sums_f64(const float* delta, const float* grad_verts, int N, int V, int Kh, double* G64,
                                   double* mean64, float* grad_P, void* stream);
 
-/* ---- correlation cost volume (forward only) ----------------------------------------------
+/* ---- correlation cost volume -------------------------------------------------------------
  * replaces correlation_cuda.forward as MaskFlownet calls it (multiframe/data/optical_flow/model/
  * correlation_package/correlation_cuda_kernel.cu:73-147, correlation.py:20-37; MaskFlownet.py:116,
  * 416: pad_size = max_displacement = md, kernel_size = 1, stride1 = stride2 = 1, corr_multiply = 1):
  *   f1, f2 [N,C,H,W] f32 -> out [N,(2md+1)^2,H,W],
  *   out[n,(tj+md)(2md+1)+(ti+md),y,x] = mean_c f1[n,c,y,x] f2[n,c,y+tj,x+ti]  (zero outside), md in 1..4.
- * The flow network is frozen in ACFM (flows are precomputed by the optical_flow scripts): no backward. */
+ * The flow network is frozen in ACFM (flows are precomputed by the optical_flow scripts); the backward below is for
+ * fine-tuning it (the reference's CorrelationFunction.backward, correlation.py:38-52). */
 int acfm_correlation_forward(const float* f1, const float* f2, int N, int C, int H, int W, int md, float* out,
                              void* stream);
+/* grad_out [N,(2md+1)^2,H,W] -> grad_f1, grad_f2 [N,C,H,W]; either may be NULL (that side is not computed, and its
+ * partner map -- f2 for grad_f1, f1 for grad_f2 -- need not be given).  With d = (tj+md)(2md+1)+(ti+md):
+ *   grad_f1[n,c,y,x] = 1/C sum_d grad_out[n,d,y,x]       f2[n,c,y+tj,x+ti]   (0 outside)
+ *   grad_f2[n,c,y,x] = 1/C sum_d grad_out[n,d,y-tj,x-ti] f1[n,c,y-tj,x-ti]   (0 where the shifted pixel is outside)
+ * Gathers in a fixed order, no atomics, no zero fill: bit-reproducible, and a side computed alone has the bits of the
+ * same side computed with the other.  Same argument ranges as the forward. */
+int acfm_correlation_backward(const float* grad_out, const float* f1, const float* f2, int N, int C, int H, int W,
+                              int md, float* grad_f1, float* grad_f2, void* stream);
 
-/* ---- deformable convolution (forward only) ----------------------------------------------
+/* ---- deformable convolution --------------------------------------------------------------
  * replaces torchvision.ops.deform_conv2d as MaskFlownet calls it (MaskFlownet.py:36-37, 488-492, 558-640: kernel 3x3,
  * stride 1, padding 1, dilation 1, groups 1, one offset group, no mask), fp32:
  *   input [N,Cin,H,W], offset [N,18,H,W], weight [Cout,Cin,3,3] (torchvision's layout, read as it is), bias [Cout] or
@@ -147,9 +156,24 @@ int acfm_correlation_forward(const float* f1, const float* f2, int N, int C, int
  * offset.repeat(1, 9, 1, 1) (MaskFlownet's unsqueeze(1), repeat_interleave(.., 9, 1), view) handed to the 18-channel
  * form, bit for bit, without that copy.
  * Cin, Cout >= 1 arbitrary.  The columns are never written to device memory and nothing is added atomically: results
- * are bit-reproducible.  The flow network is frozen in ACFM: no backward. */
+ * are bit-reproducible.  The flow network is frozen in ACFM; the backward below is for fine-tuning it. */
 int acfm_deform_conv2d_forward(const float* input, const float* offset, const float* weight, const float* bias, int N,
                                int Cin, int H, int W, int Cout, int shared_offset, float* out, void* stream);
+/* Backward: grad_out [N,Cout,H,W] -> grad_input [N,Cin,H,W], grad_offset [N,18,H,W] (shared_offset: [N,2,H,W], the sum
+ * over the nine taps), grad_weight [Cout,Cin,3,3], grad_bias [Cout]; every one of the four may be NULL and is then not
+ * computed (no weight-gradient kernel for a frozen weight).  Nothing of the forward is saved: the sampling is recomputed
+ * from input and offset.  At an integer sample coordinate the offset gradient is that of the floor cell (the forward
+ * difference towards the +1 neighbour, torchvision's convention); it is 0 for a position outside (-1,H) x (-1,W).
+ *   grad_input is a data-dependent scatter: float atomics into a buffer the call zero-fills -- NOT bit-reproducible;
+ *   grad_offset, grad_weight and grad_bias are reduced in a fixed order: bit-reproducible.
+ * ws: acfm_deform_conv2d_backward_workspace_bytes(N, Cin, H, W, Cout) bytes on the device, any contents (the partial
+ * weight gradients of the pixel ranges); needed only with grad_weight (NULL: ACFM_E_BADARG, too small:
+ * ACFM_E_WORKSPACE).  The query returns 0 for arguments out of range.  Same argument ranges as the forward. */
+size_t acfm_deform_conv2d_backward_workspace_bytes(int N, int Cin, int H, int W, int Cout);
+int acfm_deform_conv2d_backward(const float* grad_out, const float* input, const float* offset, const float* weight,
+                                int N, int Cin, int H, int W, int Cout, int shared_offset, float* grad_input,
+                                float* grad_offset, float* grad_weight, float* grad_bias, void* ws, size_t ws_bytes,
+                                void* stream);
 
 /* ---- optical-flow loss -----------------------------------------------------------------
  * replaces the tail of loss_utils.optical_flow_loss (multiframe/nnutils/loss_utils.py:445-474):
