@@ -103,6 +103,8 @@ SIGNATURES = {
     "acfm_mask_losses_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "acfm_tex_mse_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "acfm_bds_loss_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "acfm_step_losses_ws": (_sz, [_i, _i, _i, _i, _vp]),
+    "acfm_step_losses_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "acfm_mask_losses_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "acfm_tex_mse": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "acfm_tex_mse_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -210,6 +212,24 @@ def require_gpu(*tensors):
         if t is not None and not t.is_cuda:
             raise RuntimeError("acfm_video_3d_reconstruction_amd ops run on the GPU only "
                                "(got a %s tensor); there is no CPU fallback" % t.device)
+
+
+class StepMaskJob(ctypes.Structure):
+    """acfm_step_mask_job of include/acfm_hip.h (and below: the other jobs of acfm_step_losses_forward)."""
+    _fields_ = [("mask", _vp), ("gt", _vp), ("edt", _vp), ("out", _vp), ("HW", _i), ("ref_batch", _i)]
+
+
+class StepTexJob(ctypes.Structure):
+    _fields_ = [("tex", _vp), ("img", _vp), ("mask", _vp), ("out", _vp), ("HW", _i), ("ref_batch", _i)]
+
+
+class StepBdsJob(ctypes.Structure):
+    _fields_ = [("verts_xy", _vp), ("bds", _vp), ("vis", _vp), ("sel", _vp), ("loss", _vp), ("argmin", _vp),
+                ("V", _i), ("P", _i), ("ref_batch", _i), ("rows", _i), ("S", _i)]
+
+
+class StepTotalJob(ctypes.Structure):
+    _fields_ = [("terms", _vp), ("cols", _vp), ("weights", _vp), ("nterms", _i), ("total", _vp)]
 
 
 class RasterTuning(ctypes.Structure):

@@ -37,6 +37,76 @@ __device__ __forceinline__ float4 load16_in_range(__amdgpu_buffer_rsrc_t r, int 
 // out[n] = (sum|m-gt|/HW, sum m*gt, sum(m+gt-m*gt), sum edt*m/HW); one pass over the mask.
 // (prediction n is compared with reference n % RB: the G camera hypotheses of a frame share the
 // frame's ground truth, so the trainer's gt.repeat(G, ...) copies are never made)
+// k_mask_losses's body for workgroup `blk` of mesh n as functions, for k_step_tail: mask_losses_block leaves the four
+// waves' sums in s_red behind a barrier, mask_losses_value is what wave 0 hands to the finish in lane c < 4.  The
+// kernel below is the same text written out, not a caller of these: called from it they changed its register
+// allocation and schedule, and its machine code is pinned (tools/isa_diff.py against the parent; as k_bds_loss_sel
+// found before).  Same expressions in the same order under -ffp-contract=off: the same bits
+// (tests/test_gpu_step_tail.py compares them).  A change to one is a change to both.
+template <int PIX_FWD>
+__device__ __forceinline__ void mask_losses_block(const float* __restrict__ mask, const float* __restrict__ gt,
+                                                  const float* __restrict__ edt, int HW, int RB, int n, int blk,
+                                                  float (&s_red)[4][4]) {
+  const int tid = threadIdx.x;
+  const size_t base = (size_t)n * HW, rbase = (size_t)(n % RB) * HW;
+  const int start = blk * PIX_FWD;
+  const int end = min(start + PIX_FWD, HW);
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  const bool vec = ((HW & 3) == 0);
+  if (vec) {
+    // the block's two 16-byte pieces per thread and array are loaded before any of them is used
+    constexpr int U = PIX_FWD / (LTPB * 4);
+    static_assert(PIX_FWD % (LTPB * 4) == 0, "whole rounds of one 16-byte piece per thread");
+    float4 m[U], g[U], e[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = start + (u * LTPB + tid) * 4;
+      const bool in = i < end;
+      m[u] = in ? *reinterpret_cast<const float4*>(mask + base + i) : make_float4(0, 0, 0, 0);
+      g[u] = (in && gt) ? *reinterpret_cast<const float4*>(gt + rbase + i) : make_float4(0, 0, 0, 0);
+    }
+    // edt m is +0 wherever the rendered mask is 0 (most of a frame): edt is fetched only for the pieces whose four mask
+    // values are not all zero -- the other lanes present an offset outside the workgroup's range and get zeros back
+    // without a memory access (load16_in_range), and a3 + (+0) == a3
+    if (edt) {
+      const __amdgpu_buffer_rsrc_t re = pixel_range(edt + rbase + start, (unsigned)(end - start) * 4u);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const bool want = m[u].x != 0.f || m[u].y != 0.f || m[u].z != 0.f || m[u].w != 0.f;
+        e[u] = load16_in_range(re, want ? (u * LTPB + tid) * 16 : OUT_OF_RANGE);
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) e[u] = make_float4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      a0 += fabsf(m[u].x - g[u].x) + fabsf(m[u].y - g[u].y) + fabsf(m[u].z - g[u].z) + fabsf(m[u].w - g[u].w);
+      a1 += m[u].x * g[u].x + m[u].y * g[u].y + m[u].z * g[u].z + m[u].w * g[u].w;
+      a2 += (m[u].x + g[u].x - m[u].x * g[u].x) + (m[u].y + g[u].y - m[u].y * g[u].y) +
+            (m[u].z + g[u].z - m[u].z * g[u].z) + (m[u].w + g[u].w - m[u].w * g[u].w);
+      a3 += e[u].x * m[u].x + e[u].y * m[u].y + e[u].z * m[u].z + e[u].w * m[u].w;
+    }
+  } else {
+    for (int i = start + tid; i < end; i += LTPB) {
+      const float m = mask[base + i], g = gt ? gt[rbase + i] : 0.f, e = edt ? edt[rbase + i] : 0.f;
+      a0 += fabsf(m - g); a1 += m * g; a2 += m + g - m * g; a3 += e * m;
+    }
+  }
+  a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3);
+  const int w = tid >> 6;
+  if ((tid & 63) == 0) { s_red[w][0] = a0; s_red[w][1] = a1; s_red[w][2] = a2; s_red[w][3] = a3; }
+  __syncthreads();
+}
+__device__ __forceinline__ float mask_losses_value(const float (&s_red)[4][4], int HW) {
+  const int tid = threadIdx.x;
+  float v = 0.f;
+  if (tid < 4) {
+    v = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
+    if (tid == 0 || tid == 3) v = v / (float)HW;
+  }
+  return v;
+}
 template <int PIX_FWD>
 __global__ __launch_bounds__(LTPB) void k_mask_losses(const float* __restrict__ mask,
                                                       const float* __restrict__ gt,
@@ -139,6 +209,77 @@ __global__ __launch_bounds__(LTPB) void k_mask_losses_bwd(const float* __restric
 
 // masked texture MSE (multiframe/main.py:655-662): per mesh mean over (3,H,W) of
 // (tex*m - img*m)^2; the workgroups' sums are added by row_finish (or, without scratch, one atomic per workgroup).
+// (tex_mse_block: k_tex_mse's body for workgroup `blk` of mesh n up to the four waves' sums in s_red, for k_step_tail;
+// a second copy of the kernel's text for the reason given at mask_losses_block)
+template <int PIX_FWD>
+__device__ __forceinline__ void tex_mse_block(const float* __restrict__ tex, const float* __restrict__ img,
+                                              const float* __restrict__ m, int HW, int RB, int n, int blk,
+                                              float (&s_red)[4]) {
+  const int tid = threadIdx.x;
+  const size_t b3 = (size_t)n * 3 * HW, r3 = (size_t)(n % RB) * 3 * HW, b1 = (size_t)(n % RB) * HW;
+  const int start = blk * PIX_FWD;
+  const int end = min(start + PIX_FWD, HW);
+  float acc = 0.f;
+  if ((HW & 3) == 0) {   // 16-byte loads
+    // The mask first: where a piece's four mask values are all zero, (t m - g m)^2 is +0 for finite t and g and
+    // acc + (+0) == acc, so the piece's six colour loads fetch nothing (the reference mask covers about a sixth of
+    // a frame).  No branch does that: the colours come through buffer loads over the workgroup's pixel range, and a
+    // lane whose piece is not wanted (or lies past the end) presents an offset outside the range, for which the
+    // hardware returns zeros without a memory access.  Every piece then goes through the same expression in the
+    // same order as before; an unread piece contributes (0 * 0 - 0 * 0)^2 = +0.
+    constexpr int U = PIX_FWD / (LTPB * 4);
+    constexpr int UB = U < 4 ? U : 4;   // pieces whose colour loads are in flight together (24 VGPRs each)
+    static_assert(PIX_FWD % (LTPB * 4) == 0 && U % UB == 0, "a workgroup's pixels are whole rounds of one 16-byte piece per thread");
+    const unsigned range_bytes = (unsigned)(end - start) * 4u;   // <= PIX_FWD * 4
+    const __amdgpu_buffer_rsrc_t rm = pixel_range(m + b1 + start, range_bytes);
+    float4 mk[U];   // (the same way: a piece past the end reads as zeros, and no branch splits the loads up)
+#pragma unroll
+    for (int u = 0; u < U; ++u) mk[u] = load16_in_range(rm, (u * LTPB + tid) * 16);
+    __amdgpu_buffer_rsrc_t rt[3], rg[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      rt[c] = pixel_range(tex + b3 + (size_t)c * HW + start, range_bytes);
+      rg[c] = pixel_range(img + r3 + (size_t)c * HW + start, range_bytes);
+    }
+#pragma unroll
+    for (int u0 = 0; u0 < U; u0 += UB) {
+      float4 t[UB][3], g[UB][3];
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        const float4 k = mk[u0 + u];
+        const bool want = k.x != 0.f || k.y != 0.f || k.z != 0.f || k.w != 0.f;
+        const int off = want ? ((u0 + u) * LTPB + tid) * 16 : OUT_OF_RANGE;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          t[u][c] = load16_in_range(rt[c], off);
+          g[u][c] = load16_in_range(rg[c], off);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        const float4 k = mk[u0 + u];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float d0 = t[u][c].x * k.x - g[u][c].x * k.x, d1 = t[u][c].y * k.y - g[u][c].y * k.y;
+          const float d2 = t[u][c].z * k.z - g[u][c].z * k.z, d3 = t[u][c].w * k.w - g[u][c].w * k.w;
+          acc += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+        }
+      }
+    }
+  } else
+  for (int i = start + tid; i < end; i += LTPB) {
+    const float mk = m[b1 + i];
+    if (mk == 0.f) continue;   // adds +0 for finite colours: not read
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float d = tex[b3 + (size_t)c * HW + i] * mk - img[r3 + (size_t)c * HW + i] * mk;
+      acc += d * d;
+    }
+  }
+  acc = wave_sum(acc);
+  if ((tid & 63) == 0) s_red[tid >> 6] = acc;
+  __syncthreads();
+}
 template <int PIX_FWD>
 __global__ __launch_bounds__(LTPB) void k_tex_mse(const float* __restrict__ tex,
                                                   const float* __restrict__ img,
@@ -275,6 +416,103 @@ __global__ void k_visible(const int64_t* __restrict__ p2f, const int64_t* __rest
 // straight from memory into LDS, 64 vertices a round, keeping the visible ones packed in ascending order
 // (ballot + prefix count) next to the index each came from.  A wave reads no other wave's quarter, so no
 // workgroup barrier stands between the staging and the search.
+// (bds_block: the body of k_bds_loss / k_bds_loss_sel below for workgroup `blk` of mesh n, for k_step_tail -- a copy of
+// their text for the reason given at mask_losses_block; true in wave 0, which then carries the workgroup's sum in
+// `contrib`.)
+// SEL: the lane's point is read through a slot list, sel [rows][S] (acfm_boundary_subset): lane p < S takes slot
+// s = sel[((n % RB) % rows) S + p] of its reference's P points; s < 0 is an empty entry (adds 0, argmin -1).  argmin
+// is then [N][S], and no gathered copy of the points exists.
+template <bool SEL>
+__device__ __forceinline__ bool bds_block(const float* __restrict__ verts_xy, const float* __restrict__ bds,
+                                          const uint8_t* __restrict__ vis, int V, int P, int RB, int n, int blk,
+                                          int32_t* __restrict__ argmin, const int32_t* __restrict__ sel, int rows, int S,
+                                          float (&s_best)[4][64], int (&s_bi)[4][64], float& contrib) {
+  extern __shared__ float s_xy[];  // [V][2]: per quarter, its visible vertices packed to the front; then int s_idx[V]
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  // the lane's boundary point first: its load is in flight while the vertices are staged
+  const int p = blk * 64 + lane;
+  float bx = 0.f, by = 0.f, bm = 0.f;
+  bool empty = false;
+  if constexpr (SEL) {
+    int s = -1;
+    if (p < S) s = sel[(size_t)((n % RB) % rows) * S + p];
+    empty = s < 0 || s >= P;
+    if (!empty) {
+      const float* b = bds + ((size_t)(n % RB) * P + s) * 3;
+      bx = b[0]; by = b[1]; bm = b[2];
+    }
+  } else {
+    if (p < P) {
+      const float* b = bds + ((size_t)(n % RB) * P + p) * 3;
+      bx = b[0]; by = b[1]; bm = b[2];
+    }
+  }
+  const int chunk = (V + 3) / 4, v0 = wv * chunk, v1 = min(V, v0 + chunk);
+  int* s_idx = reinterpret_cast<int*>(s_xy + 2 * (size_t)V);
+  int nvis = 0;
+  {
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    // (unconditional loads, four rounds in flight: with the loads behind the visibility test the staging was a
+    // chain of memory latencies)
+    for (int base = v0; base < v1; base += 4 * 64) {
+      uint8_t vz[4];
+      float2 xy[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int v = min(base + u * 64 + lane, v1 - 1);
+        vz[u] = vis[(size_t)n * V + v];
+        xy[u] = *reinterpret_cast<const float2*>(verts_xy + ((size_t)n * V + v) * 2);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int v = base + u * 64 + lane;
+        const bool keep = (v < v1) && vz[u] != 0;
+        const unsigned long long m = __ballot(keep);
+        if (keep) {
+          const int pos = v0 + nvis + __popcll(m & lt);
+          *reinterpret_cast<float2*>(s_xy + 2 * pos) = xy[u];
+          s_idx[pos] = v;
+        }
+        nvis += __popcll(m);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  float best = 1000.0f;  // loss_utils.py:228: invisible vertices sit at distance 1000
+  int bi = -1;
+#pragma unroll 8
+  for (int v = v0; v < v0 + nvis; ++v) {
+    const float2 q = *reinterpret_cast<const float2*>(s_xy + 2 * v);
+    const float dx = bx - q.x, dy = by - q.y;
+    const float d = dx * dx + dy * dy;
+    if (d < best) { best = d; bi = v; }
+  }
+  if (bi >= 0) bi = s_idx[bi];
+  s_best[wv][lane] = best; s_bi[wv][lane] = bi;
+  __syncthreads();
+  if (wv != 0) return false;
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const float d = s_best[w][lane];
+    if (d < best) { best = d; bi = s_bi[w][lane]; }
+  }
+  contrib = 0.f;
+  if constexpr (SEL) {
+    if (p < S) {
+      contrib = empty ? 0.f : best * bm;
+      argmin[(size_t)n * S + p] = empty ? -1 : bi;
+    }
+  } else {
+    if (p < P) {
+      contrib = best * bm;
+      argmin[(size_t)n * P + p] = bi;
+    }
+  }
+  contrib = wave_sum(contrib);
+  return true;
+}
 __global__ __launch_bounds__(LTPB) void k_bds_loss(const float* __restrict__ verts_xy,
                                                    const float* __restrict__ bds,
                                                    const uint8_t* __restrict__ vis, int V, int P, int RB,
@@ -627,6 +865,98 @@ __global__ __launch_bounds__(256) void k_combine_bwd(CombArgs a, int N, const fl
       for (int c = 0; c < a.cols[t]; ++c) a.g[t][(size_t)n * a.cols[t] + c] = a.w[t][c] * g;
 }
 
+// ---- the step's tail in one launch: boundary loss, silhouette losses, texture MSE and their weighted total ----------
+// k_step_tail's grid is the workgroups of k_bds_loss[_sel], k_mask_losses and k_tex_mse one after the other (the
+// boundary loss first: it is the chain of latencies, so it starts first); every workgroup runs the body of the kernel
+// it stands for (bds_block, mask_losses_block, tex_mse_block) on the same pixel partition and finishes its row through
+// the same tickets in the same order, so each term has the bits the separate launch gives.  A role with nb == 0 is
+// absent.  The three launches were short for what they are, not for their bytes (ramp, a few dependent loads, ticket,
+// drain): as roles of one grid those chains overlap.
+// The total: a row that is finished is published (row_finish_published) and counted in one more ticket word,
+// `done`, which wraps at rows = N x (roles present); the wave that counts the last row evaluates k_combine's
+// expression on the finished rows -- the 256 threads of k_combine as four passes of its 64 lanes, added in
+// k_combine's order -- reading every term with device-scope loads.  Terms that no role of this launch writes are
+// read the same way (an earlier launch finished them).
+struct TailBds {
+  const float* verts_xy; const float* bds; const uint8_t* vis; const int32_t* sel;
+  float* loss; int32_t* argmin; RowScratch sc;
+  int V, P, RB, rows, S, nb;
+};
+struct TailMask {
+  const float* mask; const float* gt; const float* edt;
+  float* out; RowScratch sc;
+  int HW, RB, nb, wide;
+};
+struct TailTex {
+  const float* tex; const float* img; const float* mask;
+  float* out; RowScratch sc;
+  int HW, RB, nb, wide;
+};
+struct TailTotal {
+  CombArgs a;
+  float* total;        // nullptr: no total
+  unsigned* done;      // one word, zero between launches
+  unsigned rows;
+};
+__device__ __forceinline__ void tail_row_done(const TailTotal& t, int N) {
+  const int lane = threadIdx.x & 63;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  unsigned ticket = 0u;
+  if (lane == 0) ticket = atomicInc(t.done, t.rows - 1u);
+  ticket = __shfl(ticket, 0, 64);
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  if (ticket != t.rows - 1u) return;
+  float s[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    float acc = 0.f;
+    for (int n = w * 64 + lane; n < N; n += 256)
+      for (int k = 0; k < t.a.nterms; ++k)
+        for (int c = 0; c < t.a.cols[k]; ++c)
+          if (t.a.w[k][c] != 0.f)
+            acc += t.a.w[k][c] * __uint_as_float(__hip_atomic_load(
+                                     reinterpret_cast<const unsigned*>(t.a.t[k]) + (size_t)n * t.a.cols[k] + c,
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    s[w] = wave_sum(acc);
+  }
+  if (lane == 0) t.total[0] = (s[0] + s[1] + s[2] + s[3]) / (float)N;
+}
+__global__ __launch_bounds__(LTPB) __attribute__((amdgpu_waves_per_eu(4))) void k_step_tail(TailBds B, TailMask M, TailTex T, TailTotal tot, int N) {
+  __shared__ float s_best[4][64];
+  __shared__ int s_bi[4][64];
+  __shared__ float s_red4[4][4];
+  __shared__ float s_red[4];
+  const int tid = threadIdx.x;
+  int b = blockIdx.x;
+  bool finished;
+  if (b < B.nb * N) {
+    const int n = b / B.nb, blk = b - n * B.nb;
+    float contrib;
+    const bool wave0 = B.sel ? bds_block<true>(B.verts_xy, B.bds, B.vis, B.V, B.P, B.RB, n, blk, B.argmin, B.sel, B.rows,
+                                               B.S, s_best, s_bi, contrib)
+                             : bds_block<false>(B.verts_xy, B.bds, B.vis, B.V, B.P, B.RB, n, blk, B.argmin, nullptr, 0, 0,
+                                                s_best, s_bi, contrib);
+    if (!wave0) return;
+    finished = row_finish_published<1>(B.sc, n, B.nb, blk, contrib, B.loss + n);
+  } else if ((b -= B.nb * N) < M.nb * N) {
+    const int n = b / M.nb, blk = b - n * M.nb;
+    if (M.wide) mask_losses_block<PIX_PER_BLOCK_WIDE>(M.mask, M.gt, M.edt, M.HW, M.RB, n, blk, s_red4);
+    else mask_losses_block<PIX_PER_BLOCK>(M.mask, M.gt, M.edt, M.HW, M.RB, n, blk, s_red4);
+    if (tid >= 64) return;
+    const float v = mask_losses_value(s_red4, M.HW);
+    finished = row_finish_published<4>(M.sc, n, M.nb, blk, v, M.out + 4 * (size_t)n);
+  } else {
+    b -= M.nb * N;
+    const int n = b / T.nb, blk = b - n * T.nb;
+    if (T.wide) tex_mse_block<PIX_PER_BLOCK_WIDE>(T.tex, T.img, T.mask, T.HW, T.RB, n, blk, s_red);
+    else tex_mse_block<PIX_PER_BLOCK>(T.tex, T.img, T.mask, T.HW, T.RB, n, blk, s_red);
+    if (tid >= 64) return;
+    const float v = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) / (3.0f * (float)T.HW);
+    finished = row_finish_published<1>(T.sc, n, T.nb, blk, v, T.out + n);
+  }
+  if (finished && tot.total) tail_row_done(tot, N);
+}
+
 // ---- total per hypothesis, softmax weighting over the hypotheses, weighted mean: one launch each way ---------
 // multiframe/main.py:716-746.  One thread per frame n walks its G hypotheses; everything is summed in a fixed
 // order (one workgroup), so the result is reproducible.
@@ -903,6 +1233,66 @@ int acfm_combine_losses(const void* const* terms, const int* cols, const float* 
   if (!terms || !total || N <= 0 || fill_comb(a, terms, nullptr, cols, weights, nterms) != ACFM_OK)
     return ACFM_E_BADARG;
   hipLaunchKernelGGL(k_combine, dim3(1), dim3(256), 0, (hipStream_t)stream, a, N, total);
+  ACFM_CHECK_LAUNCH();
+  return ACFM_OK;
+}
+
+size_t acfm_step_losses_ws(int N, int HW_mask, int HW_tex, int S, size_t* ticket_words) {
+  if (N <= 0 || HW_mask < 0 || HW_tex < 0 || S < 0) return 0;
+  if (ticket_words) *ticket_words = 3 * (size_t)N + 1;
+  return (HW_mask ? loss_partial_floats(ACFM_LOSS_MASK, N, HW_mask) : 0) +
+         (HW_tex ? loss_partial_floats(ACFM_LOSS_TEX_MSE, N, HW_tex) : 0) + (S ? loss_partial_floats(ACFM_LOSS_BDS, N, S) : 0);
+}
+
+int acfm_step_losses_forward(const acfm_step_mask_job* mask, const acfm_step_tex_job* tex, const acfm_step_bds_job* bds,
+                             const acfm_step_total_job* total, int N, uint32_t* tickets, float* partials,
+                             size_t partial_floats, void* stream) {
+  if ((!mask && !tex && !bds) || N <= 0 || N > 65535 || !tickets || !partials) return ACFM_E_BADARG;
+  const int S = bds ? (bds->sel ? bds->S : bds->P) : 0;
+  if (mask && (!mask->mask || !mask->out || mask->HW <= 0 || mask->ref_batch <= 0 || N % mask->ref_batch != 0))
+    return ACFM_E_BADARG;
+  if (tex && (!tex->tex || !tex->img || !tex->mask || !tex->out || tex->HW <= 0 || tex->ref_batch <= 0 ||
+              N % tex->ref_batch != 0))
+    return ACFM_E_BADARG;
+  if (bds && (!bds->verts_xy || !bds->bds || !bds->vis || !bds->loss || !bds->argmin || bds->V <= 0 || bds->P <= 0 ||
+              S <= 0 || bds->ref_batch <= 0 || N % bds->ref_batch != 0 ||
+              (bds->sel && bds->rows != 1 && bds->rows != bds->ref_batch)))
+    return ACFM_E_BADARG;
+  const size_t lds = bds ? sizeof(float) * 3 * (size_t)bds->V : 0;   // as acfm_bds_loss_ws
+  if (lds > 150 * 1024) return ACFM_E_BADARG;
+  if (partial_floats < acfm_step_losses_ws(N, mask ? mask->HW : 0, tex ? tex->HW : 0, S, nullptr)) return ACFM_E_WORKSPACE;
+  TailBds B = {};
+  TailMask M = {};
+  TailTex T = {};
+  TailTotal tot = {};
+  float* part = partials;
+  if (mask) {
+    const int ppb = fwd_pix_per_block(N, mask->HW);
+    M = {mask->mask, mask->gt, mask->edt, mask->out, {tickets, part}, mask->HW, mask->ref_batch,
+         (mask->HW + ppb - 1) / ppb, ppb == PIX_PER_BLOCK_WIDE};
+    part += loss_partial_floats(ACFM_LOSS_MASK, N, mask->HW);
+  }
+  if (tex) {
+    const int ppb = fwd_pix_per_block(N, tex->HW);
+    T = {tex->tex, tex->img, tex->mask, tex->out, {tickets + N, part}, tex->HW, tex->ref_batch,
+         (tex->HW + ppb - 1) / ppb, ppb == PIX_PER_BLOCK_WIDE};
+    part += loss_partial_floats(ACFM_LOSS_TEX_MSE, N, tex->HW);
+  }
+  if (bds)
+    B = {bds->verts_xy, bds->bds, bds->vis, bds->sel, bds->loss, bds->argmin, {tickets + 2 * (size_t)N, part},
+         bds->V, bds->P, bds->ref_batch, bds->sel ? bds->rows : 0, bds->sel ? bds->S : 0, (S + 63) / 64};
+  if (total) {
+    if (!total->total || fill_comb(tot.a, total->terms, nullptr, total->cols, total->weights, total->nterms) != ACFM_OK)
+      return ACFM_E_BADARG;
+    tot.total = total->total;
+    tot.done = tickets + 3 * (size_t)N;
+    tot.rows = (unsigned)N * (unsigned)((mask != nullptr) + (tex != nullptr) + (bds != nullptr));
+  }
+  const size_t blocks = (size_t)N * ((size_t)B.nb + (size_t)M.nb + (size_t)T.nb);
+  if (blocks > 0x7fffffffull) return ACFM_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(ACFM_PROF_STEP_TAIL, st);
+  hipLaunchKernelGGL(k_step_tail, dim3((unsigned)blocks), dim3(LTPB), lds, st, B, M, T, tot, N);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
 }

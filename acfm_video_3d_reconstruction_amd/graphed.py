@@ -59,6 +59,7 @@ class GraphedStep:
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             self.loss, self.aux = self._one(zero=False)
             self.grads = {k: self.static[k].grad for k in self.grad_inputs}
+            ops.flush_pending_losses()        # a loss term fn returned without using it: its launch belongs in the graph
         with torch.no_grad():                 # undo the warm-up: same tensors, original values
             for p, s in zip(params, saved_params):
                 p.copy_(s)

@@ -72,7 +72,10 @@ def fused_silhouette_losses(mask_pred, mask_gt, edt, eps=1e-6, raw=False):
 def combine_losses(terms, weights):
     """Weighted total of per-mesh loss terms and its mean over the batch, (1/N) sum_n sum_t w_t * term_t[n]
     (the elementwise tail of multiframe/main.py:716-765), as one launch forward and one backward.
-    terms: up to 4 tensors [N] or [N,C<=4]; weights: one float per column, term by term."""
+    terms: up to 4 tensors [N] or [N,C<=4]; weights: one float per column, term by term.
+    Terms that come straight from fused_silhouette_losses(raw=True) / l1_loss / edt_loss, bds_loss(reduce=False) and
+    masked_texture_mse have not been launched yet (ops.PendingTerm): they leave here, with the total, as ONE launch.
+    Any other use of such a term launches it by itself first, so nothing changes for callers that add terms up by hand."""
     return ops.combine_losses(terms, weights)
 
 

@@ -2,10 +2,12 @@
 
 torch is used here for device memory, streams and autograd bookkeeping only; every op body
 is one or more stream-ordered calls into libacfm_hip.so."""
+import contextlib
 import ctypes
 import dataclasses
 import math
 import threading
+import weakref
 
 import torch
 
@@ -92,6 +94,7 @@ _LOCK = threading.RLock()
 def invalidate_setups():
     """Forget every cached face setup: call after writing to verts / cams / faces behind torch's back, and after a
     hipGraph replay whose outputs are then rendered eagerly (see above)."""
+    flush_pending_losses()    # (a replay rewrites the inputs a deferred loss term has yet to read)
     with _LOCK:
         _EPOCH[0] += 1
         _SETUP.clear()
@@ -1669,6 +1672,232 @@ def vertex_color_render(verts, faces, cams, verts_rgb, img_size, sigma=1e-4, gam
     return imgs, sil, p2f
 
 
+# ------------------------------------------------------------------------------ deferred loss terms
+# The three per-mesh loss sums of a step (mask_losses, tex_mse, bds_loss_per_mesh) are short launches, and the step
+# ends in combine_losses over them.  Like LazyPixToFace and LazyGrad, their forward is deferred: the operator allocates
+# its output, notes a job (arguments, inputs and the inputs' versions) and returns the output as a PendingTerm.
+# combine_losses launches the pending jobs among its terms and the total as ONE kernel (acfm_step_losses_forward).
+# Any other use of a PendingTerm first runs the launch the operator would have made (flush): torch functions on it
+# (arithmetic, indexing, .item(), .cpu(), printing, another operator saving it), its own backward,
+# invalidate_setups() / graph_replay(), flush_pending_losses().  What a flush refuses: an input written in place
+# since the call (RuntimeError naming it), and a term deferred inside a hipGraph capture that ended without using it
+# (the launch can no longer be recorded).  So that this does not happen, graphed.GraphedStep flushes before it ends
+# its capture, and inside ANY capture a term is deferred only if the last term of its kind on the device left in a
+# one-launch combine_losses -- which the eager warm-up calls that precede every capture have shown by then (the way
+# the cover flag above follows what the texture renders do); a term that a capture returns unread is launched where
+# it is called.  With a capture of your own that differs from its warm-up, call flush_pending_losses() before
+# leaving it.  Terms are not deferred on the worker threads nn.DataParallel runs its replicas on (their outputs are
+# gathered by code that does not look at the type).
+_DEFER = [True]
+_PENDING = weakref.WeakSet()
+_FUSED_LAST = {}         # (device index, kind) -> the last job of that kind was launched with others by combine_losses
+
+
+@contextlib.contextmanager
+def defer_losses(on=True):
+    """with ops.defer_losses(False): every loss term is launched where it is called (no PendingTerm)."""
+    flush_pending_losses()
+    with _LOCK:
+        old, _DEFER[0] = _DEFER[0], bool(on)
+    try:
+        yield
+    finally:
+        flush_pending_losses()
+        with _LOCK:
+            _DEFER[0] = old
+
+
+def _deferring(device=None, kind=None):
+    if not _DEFER[0] or threading.current_thread() is not threading.main_thread():
+        return False
+    if device is not None and torch.cuda.is_current_stream_capturing():
+        return _FUSED_LAST.get((device.index, kind), False)
+    return True
+
+
+def flush_pending_losses():
+    """Launch every loss term that is still deferred (each by its own kernel)."""
+    with _LOCK:
+        jobs = list(_PENDING)
+    for j in jobs:
+        j.flush()
+
+
+def launch_pending_together(terms):
+    """The pending terms among `terms` (at most one of each kind; same batch, stream and capture) as ONE launch
+    without a total -- what combine_losses does for its terms, for callers that add the terms up themselves."""
+    jobs = []
+    for t in terms:
+        j = t._job if type(t) is PendingTerm else None
+        if j is not None and not j.done and j not in jobs:
+            if any(k.kind == j.kind or k.N != j.N or k.device != j.device or k.stream != j.stream or k.cid != j.cid
+                   for k in jobs):
+                raise ValueError("launch_pending_together: one term of each kind, on the same batch, stream and capture")
+            jobs.append(j)
+    if jobs:
+        if jobs[0].stream != torch.cuda.current_stream(jobs[0].device):
+            raise ValueError("launch_pending_together: call it on the stream the terms were called on")
+        _launch_step_tail(jobs, None)
+
+
+class _PendingJob:
+    """A loss term whose launch has not been issued: kind 'mask' / 'tex' / 'bds', the output tensor(s), the inputs as
+    (name, tensor, version at the call), `launch` (the operator's own entry point) and `fill` (-> the job structure of
+    acfm_step_losses_forward)."""
+
+    def __init__(self, kind, what, out, N, inputs, launch, fill, sizes):
+        self.kind, self.what, self.out, self.N = kind, what, out, N
+        self.inputs = [(name, t, t._version) for name, t in inputs if t is not None]
+        self.launch, self.fill, self.sizes = launch, fill, sizes
+        self.device = out.device
+        self.stream = torch.cuda.current_stream(self.device)
+        self.cid = _capture_id(self.device)
+        self.done = False
+        with _LOCK:
+            _PENDING.add(self)
+
+    def check(self):
+        """Raises unless the job can still be launched on what its operator was called with."""
+        for name, t, version in self.inputs:
+            if t._version != version:
+                raise RuntimeError("%s: `%s` was written in place after the call and before its deferred launch "
+                                   "(combine_losses, or the first use of the result); the loss is not computed on "
+                                   "changed data -- use ops.defer_losses(False) or write after the result is used"
+                                   % (self.what, name))
+        with torch.cuda.stream(self.stream):
+            cid = _capture_id(self.device)
+        if cid != self.cid:
+            raise RuntimeError("%s: called inside a hipGraph capture that ended before its deferred launch was "
+                               "recorded; call ops.flush_pending_losses() before leaving the capture" % self.what
+                               if self.cid else
+                               "%s: called before a hipGraph capture and first used inside it; call "
+                               "ops.flush_pending_losses() before the capture begins" % self.what)
+
+    def __del__(self):
+        if not getattr(self, "done", True):   # dropped unread: nothing was launched for it, certainly not with others
+            _FUSED_LAST[(self.device.index, self.kind)] = False
+
+    def taken(self, fused=False):
+        _FUSED_LAST[(self.device.index, self.kind)] = fused
+        self.done = True
+        self.launch = self.fill = None
+        self.inputs = []
+        with _LOCK:
+            _PENDING.discard(self)
+
+    def flush(self):
+        if self.done:
+            return
+        self.check()             # (a job that cannot be launched stays pending: every use of its term raises)
+        self.done = True
+        try:
+            cur = torch.cuda.current_stream(self.device)
+            with torch.cuda.stream(self.stream):   # where the call was made: its inputs are ordered there
+                self.launch()
+            if cur != self.stream:
+                cur.wait_stream(self.stream)
+        finally:
+            self.taken()
+
+
+def _pending_terms(args):
+    found = []
+
+    def walk(x):
+        if type(x) is PendingTerm:
+            found.append(x)
+        elif isinstance(x, (list, tuple)):
+            for y in x:
+                walk(y)
+        elif isinstance(x, dict):
+            for y in x.values():
+                walk(y)
+    walk(args)
+    return found
+
+
+class PendingTerm(torch.Tensor):
+    """The output of a deferred loss operator (see above): a tensor on the operator's output storage, with the
+    operator's grad_fn, whose values exist once its job has been launched.  Reading it in any way launches the job."""
+
+    @staticmethod
+    def __new__(cls, out, job):
+        r = torch.Tensor._make_subclass(cls, out)
+        r._job = job
+        return r
+
+    @property
+    def is_pending(self):
+        return not self._job.done
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        if func not in _PENDING_META:
+            for t in _pending_terms((args, kwargs)):
+                t._job.flush()
+        with torch._C.DisableTorchFunctionSubclass():
+            return func(*args, **kwargs)
+
+
+# what can be asked of a PendingTerm without its values
+_PENDING_META = {getattr(torch.Tensor, n).__get__ for n in
+                 ("shape", "device", "dtype", "requires_grad", "grad_fn", "_version", "is_cuda", "is_leaf", "ndim",
+                  "layout", "names", "is_sparse", "is_quantized", "is_meta", "output_nr", "_base", "grad")}
+_PENDING_META |= {torch.Tensor.dim, torch.Tensor.size, torch.Tensor.numel, torch.Tensor.nelement, torch.Tensor.data_ptr,
+                  torch.Tensor.stride, torch.Tensor.is_contiguous, torch.Tensor.element_size, torch.Tensor.get_device,
+                  torch.Tensor.is_floating_point, torch.Tensor.storage_offset, torch.Tensor.ndimension,
+                  torch.Tensor.is_complex}
+
+
+def _raw(t):
+    """A PendingTerm's storage as a plain tensor, without launching its job."""
+    return t._job.out if type(t) is PendingTerm else t
+
+
+def _step_scratch(device, N, hw_mask, hw_tex, S):
+    words = ctypes.c_size_t(0)
+    need = int(_lib.lib().acfm_step_losses_ws(N, hw_mask, hw_tex, S, ctypes.byref(words)))
+    return _row_scratch(device, "step_tail", int(words.value), need)
+
+
+def _launch_step_tail(jobs, total):
+    """The pending `jobs` (at most one of each kind, same N, device, stream and capture) and, if total =
+    (term tensors [N,C], cols, weights, out) is given, the weighted total, as one acfm_step_losses_forward."""
+    dev, N = jobs[0].device, jobs[0].N
+    for j in jobs:
+        j.check()
+    by_kind = {j.kind: j for j in jobs}
+    keep = []
+    structs = {}
+    for kind in ("mask", "tex", "bds"):
+        j = by_kind.get(kind)
+        if j is not None:
+            structs[kind] = j.fill()
+            keep.append(structs[kind])
+    sz = {k: (by_kind[k].sizes if k in by_kind else 0) for k in ("mask", "tex", "bds")}
+    with torch.cuda.device(dev):
+        tk, part, nf = _step_scratch(dev, N, sz["mask"], sz["tex"], sz["bds"])
+    tot = None
+    if total is not None:
+        ts, cols, weights, out = total
+        ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        tot = _lib.StepTotalJob(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(cols, ctypes.c_void_p),
+                                ctypes.cast(weights, ctypes.c_void_p), len(ts), out.data_ptr())
+        keep.append(ptrs)
+
+    def ref(x):
+        return ctypes.cast(ctypes.pointer(x), ctypes.c_void_p) if x is not None else None
+    for j in jobs:
+        j.done = True
+    try:
+        _lib.call("acfm_step_losses_forward", dev, ref(structs.get("mask")), ref(structs.get("tex")),
+                  ref(structs.get("bds")), ref(tot), N, _lib.ptr(tk), _lib.ptr(part), nf)
+    finally:
+        for j in jobs:
+            j.taken(fused=True)
+
+
 # ------------------------------------------------------------------------------ mask losses
 def _ref_batch(N, ref, what):
     """References (ground-truth masks, images, boundary points) may be given once per frame for the G
@@ -1696,16 +1925,28 @@ class _MaskLosses(torch.autograd.Function):
         if g is not None and e is not None and g.shape[0] != e.shape[0]:
             raise ValueError("mask_losses: gt and edt must have the same batch")
         out = torch.empty((N, 4), dtype=torch.float32, device=m.device)
-        with torch.cuda.device(m.device):
-            tk, part, nf = _loss_scratch(m.device, _LOSS_MASK, N, HW)
-        _lib.call("acfm_mask_losses_ws", m.device, _lib.ptr(m), _lib.ptr(g), _lib.ptr(e), N, HW, RB, _lib.ptr(out),
-                  _lib.ptr(tk), _lib.ptr(part), nf)
+
+        def launch():
+            with torch.cuda.device(m.device):
+                tk, part, nf = _loss_scratch(m.device, _LOSS_MASK, N, HW)
+            _lib.call("acfm_mask_losses_ws", m.device, _lib.ptr(m), _lib.ptr(g), _lib.ptr(e), N, HW, RB, _lib.ptr(out),
+                      _lib.ptr(tk), _lib.ptr(part), nf)
         ctx.save_for_backward(m, g, e)
         ctx.rb = RB
-        return out
+        ctx.job = None
+        if not _deferring(m.device, "mask"):
+            launch()
+            return out
+        ctx.job = _PendingJob(
+            "mask", "mask_losses", out, N, (("mask", m), ("gt", g), ("edt", e)), launch,
+            lambda: _lib.StepMaskJob(m.data_ptr(), g.data_ptr() if g is not None else None,
+                                     e.data_ptr() if e is not None else None, out.data_ptr(), HW, RB), HW)
+        return PendingTerm(out, ctx.job)
 
     @staticmethod
     def backward(ctx, gout):
+        if ctx.job is not None:
+            ctx.job.flush()
         m, g, e = ctx.saved_tensors
         N = m.shape[0]
         HW = m[0].numel()
@@ -1739,16 +1980,27 @@ class _TexMSE(torch.autograd.Function):
         if t.shape[1:] != i.shape[1:] or t.shape[1] != 3 or t[0, 0].numel() != HW or m.shape[0] != RB:
             raise ValueError("tex [N,3,H,W], img [N or N/G,3,H,W] and mask [same batch as img,H,W]")
         out = torch.empty((N,), dtype=torch.float32, device=t.device)
-        with torch.cuda.device(t.device):
-            tk, part, nf = _loss_scratch(t.device, _LOSS_TEX_MSE, N, HW)
-        _lib.call("acfm_tex_mse_ws", t.device, _lib.ptr(t), _lib.ptr(i), _lib.ptr(m), N, HW, RB, _lib.ptr(out),
-                  _lib.ptr(tk), _lib.ptr(part), nf)
+
+        def launch():
+            with torch.cuda.device(t.device):
+                tk, part, nf = _loss_scratch(t.device, _LOSS_TEX_MSE, N, HW)
+            _lib.call("acfm_tex_mse_ws", t.device, _lib.ptr(t), _lib.ptr(i), _lib.ptr(m), N, HW, RB, _lib.ptr(out),
+                      _lib.ptr(tk), _lib.ptr(part), nf)
         ctx.save_for_backward(t, i, m)
         ctx.rb = RB
-        return out
+        ctx.job = None
+        if not _deferring(t.device, "tex"):
+            launch()
+            return out
+        ctx.job = _PendingJob("tex", "tex_mse", out, N, (("tex", t), ("img", i), ("mask", m)), launch,
+                              lambda: _lib.StepTexJob(t.data_ptr(), i.data_ptr(), m.data_ptr(), out.data_ptr(), HW, RB),
+                              HW)
+        return PendingTerm(out, ctx.job)
 
     @staticmethod
     def backward(ctx, go):
+        if ctx.job is not None:
+            ctx.job.flush()
         t, i, m = ctx.saved_tensors
         N = t.shape[0]
         HW = m[0].numel()
@@ -1775,7 +2027,23 @@ class _Combine(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weights, *terms):
         _lib.require_gpu(*terms)
-        ts = [_f32c(t if t.dim() == 2 else t.reshape(t.shape[0], -1)) for t in terms]
+        # the terms whose launch is still pending leave with the total, as one launch: at most one of each kind, all
+        # called on this stream and in this capture (any other pending term is launched by itself, here)
+        jobs = []
+        for t in terms:
+            j = t._job if type(t) is PendingTerm else None
+            if j is not None and not j.done and j not in jobs and all(k.kind != j.kind for k in jobs) and \
+                    j.N == terms[0].shape[0] and j.device == terms[0].device and \
+                    j.stream == torch.cuda.current_stream(j.device) and j.cid == _capture_id(j.device):
+                jobs.append(j)
+        fused = {id(j.out) for j in jobs}
+        ts = []
+        for t in terms:
+            r = _raw(t)
+            if id(r) in fused:
+                ts.append(r if r.dim() == 2 else r.view(r.shape[0], -1))
+            else:
+                ts.append(_f32c(t if t.dim() == 2 else t.reshape(t.shape[0], -1)))
         N = ts[0].shape[0]
         cols = [int(t.shape[1]) for t in ts]
         if not 1 <= len(ts) <= 4 or any(t.shape[0] != N for t in ts) or any(c < 1 or c > 4 for c in cols) \
@@ -1784,6 +2052,9 @@ class _Combine(torch.autograd.Function):
         total = torch.empty((), dtype=torch.float32, device=ts[0].device)
         ctx.args = ((ctypes.c_int * len(cols))(*cols), (ctypes.c_float * len(weights))(*[float(w) for w in weights]),
                     len(ts), N, [t.shape for t in terms])
+        if jobs:
+            _launch_step_tail(jobs, (ts, ctx.args[0], ctx.args[1], total))
+            return total
         ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         _lib.call("acfm_combine_losses", total.device, ptrs, ctx.args[0], ctx.args[1], len(ts), N, _lib.ptr(total))
         return total
@@ -1920,16 +2191,29 @@ class _BdsLoss(torch.autograd.Function):
         RB = _ref_batch(N, b, "bds_loss")
         loss = torch.empty((N,), dtype=torch.float32, device=v.device)
         arg = torch.empty((N, P), dtype=torch.int32, device=v.device)
-        with torch.cuda.device(v.device):
-            tk, part, nf = _loss_scratch(v.device, _LOSS_BDS, N, P)
-        _lib.call("acfm_bds_loss_ws", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vis.contiguous()), N, V, P, RB,
-                  _lib.ptr(loss), _lib.ptr(arg), _lib.ptr(tk), _lib.ptr(part), nf)
-        ctx.save_for_backward(v, b, arg)
+        vz = vis.contiguous()
+
+        def launch():
+            with torch.cuda.device(v.device):
+                tk, part, nf = _loss_scratch(v.device, _LOSS_BDS, N, P)
+            _lib.call("acfm_bds_loss_ws", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vz), N, V, P, RB,
+                      _lib.ptr(loss), _lib.ptr(arg), _lib.ptr(tk), _lib.ptr(part), nf)
         ctx.rb = RB
-        return loss
+        ctx.job = None
+        if not _deferring(v.device, "bds") or 12 * V > 150 * 1024:     # (a V the kernel refuses is refused here, by its own launch)
+            ctx.save_for_backward(v, b, arg)
+            launch()
+            return loss
+        ctx.job = _PendingJob("bds", "bds_loss", loss, N, (("verts", v), ("bds", b), ("vis", vz)), launch,
+                              lambda: _lib.StepBdsJob(v.data_ptr(), b.data_ptr(), vz.data_ptr(), None, loss.data_ptr(),
+                                                      arg.data_ptr(), V, P, RB, 0, 0), P)
+        ctx.save_for_backward(v, b, PendingTerm(arg, ctx.job))   # (whoever reads the saved argmin launches the job too)
+        return PendingTerm(loss, ctx.job)
 
     @staticmethod
     def backward(ctx, gl):
+        if ctx.job is not None:
+            ctx.job.flush()
         v, b, arg = ctx.saved_tensors
         N, V, _ = v.shape
         P = b.shape[1]
@@ -1957,16 +2241,29 @@ class _BdsLossSel(torch.autograd.Function):
         rows, S = s.shape
         loss = torch.empty((N,), dtype=torch.float32, device=v.device)
         arg = torch.empty((N, S), dtype=torch.int32, device=v.device)
-        with torch.cuda.device(v.device):
-            tk, part, nf = _loss_scratch(v.device, _LOSS_BDS, N, S)
-        _lib.call("acfm_bds_loss_sel_ws", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vis.contiguous()), _lib.ptr(s),
-                  N, V, P, RB, rows, S, _lib.ptr(loss), _lib.ptr(arg), _lib.ptr(tk), _lib.ptr(part), nf)
-        ctx.save_for_backward(v, b, s, arg)
+        vz = vis.contiguous()
+
+        def launch():
+            with torch.cuda.device(v.device):
+                tk, part, nf = _loss_scratch(v.device, _LOSS_BDS, N, S)
+            _lib.call("acfm_bds_loss_sel_ws", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vz), _lib.ptr(s),
+                      N, V, P, RB, rows, S, _lib.ptr(loss), _lib.ptr(arg), _lib.ptr(tk), _lib.ptr(part), nf)
         ctx.rb = RB
-        return loss
+        ctx.job = None
+        if not _deferring(v.device, "bds") or 12 * V > 150 * 1024:
+            ctx.save_for_backward(v, b, s, arg)
+            launch()
+            return loss
+        ctx.job = _PendingJob("bds", "bds_loss", loss, N, (("verts", v), ("bds", b), ("vis", vz), ("sel", s)), launch,
+                              lambda: _lib.StepBdsJob(v.data_ptr(), b.data_ptr(), vz.data_ptr(), s.data_ptr(),
+                                                      loss.data_ptr(), arg.data_ptr(), V, P, RB, rows, S), S)
+        ctx.save_for_backward(v, b, s, PendingTerm(arg, ctx.job))
+        return PendingTerm(loss, ctx.job)
 
     @staticmethod
     def backward(ctx, gl):
+        if ctx.job is not None:
+            ctx.job.flush()
         v, b, s, arg = ctx.saved_tensors
         N, V, _ = v.shape
         P = b.shape[1]

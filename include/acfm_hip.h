@@ -81,6 +81,7 @@ int acfm_stream_capture_id(void* stream, unsigned long long* id_host);
 #define ACFM_PROF_FRAG_FWD 19
 #define ACFM_PROF_FRAG_BWD 20
 #define ACFM_PROF_BDS_SUBSET 21
+#define ACFM_PROF_STEP_TAIL 22
 #define ACFM_PROF_NKERNELS 24
 #define ACFM_PROF_RING 8192
 int acfm_prof_enable(int on);
@@ -688,6 +689,45 @@ int acfm_bds_loss_sel_backward(const float* verts_xy, const float* bds, const in
  * sized by P. */
 int acfm_boundary_subset(int64_t* state, const int32_t* counts, int n_counts, int rows, int P, int n_samples,
                          int32_t* sel, void* stream);
+
+/* ---- the step's tail in one launch ------------------------------------------------------------------------------
+ * acfm_step_losses_forward: any of acfm_mask_losses_ws, acfm_tex_mse_ws and acfm_bds_loss_ws / acfm_bds_loss_sel_ws on
+ * the same N meshes, and optionally acfm_combine_losses over their outputs, as ONE kernel (k_step_tail): the three
+ * sums are short launches far below the memory and issue limits, and as roles of one grid their latencies overlap.
+ * Every job computes what its own entry point computes, bit for bit (same pixel partition, same order of sums); the
+ * fields of a job are that entry point's arguments.  mask / tex / bds: NULL = that term is not computed (at least
+ * one must be given).  bds->sel: NULL = acfm_bds_loss_ws (rows and S are ignored), else acfm_bds_loss_sel_ws.
+ * total: NULL, or the arguments of acfm_combine_losses; its terms are usually the outputs of the jobs of this call
+ * (the kernel evaluates the total once the last of them is finished), and any other term must have been finished by
+ * an earlier launch on the stream.  Same expression in the same order as acfm_combine_losses: the same bits.
+ * Scratch: tickets, acfm_step_losses_ws's *ticket_words words (3 N + 1), ALL ZERO before their first use and left at
+ * zero by every launch; partials, the returned number of floats, any contents (HW_mask / HW_tex / S = 0 for an absent
+ * job; S = P without a slot list).  Too small: ACFM_E_WORKSPACE.  Stream-ordered, no host synchronisation: capturable. */
+typedef struct {
+  const float* mask; const float* gt; const float* edt;   /* gt / edt may be NULL */
+  float* out;                                              /* [N,4] */
+  int HW, ref_batch;
+} acfm_step_mask_job;
+typedef struct {
+  const float* tex; const float* img; const float* mask;
+  float* out;                                              /* [N] */
+  int HW, ref_batch;
+} acfm_step_tex_job;
+typedef struct {
+  const float* verts_xy; const float* bds; const uint8_t* vis;
+  const int32_t* sel;                                      /* NULL, or [rows,S] */
+  float* loss; int32_t* argmin;                            /* [N], [N,P] (with sel: [N,S]) */
+  int V, P, ref_batch, rows, S;
+} acfm_step_bds_job;
+typedef struct {
+  const void* const* terms; const int* cols; const float* weights;
+  int nterms;
+  float* total;
+} acfm_step_total_job;
+size_t acfm_step_losses_ws(int N, int HW_mask, int HW_tex, int S, size_t* ticket_words);
+int acfm_step_losses_forward(const acfm_step_mask_job* mask, const acfm_step_tex_job* tex, const acfm_step_bds_job* bds,
+                             const acfm_step_total_job* total, int N, uint32_t* tickets, float* partials,
+                             size_t partial_floats, void* stream);
 
 /* ---- mesh priors -------------------------------------------------------------------------
  * Packed meshes: verts [P,3] f32, faces [F,3] / edges [E,2] i64 with packed vertex ids.
