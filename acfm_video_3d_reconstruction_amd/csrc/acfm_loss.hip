@@ -37,66 +37,18 @@ __device__ __forceinline__ float4 load16_in_range(__amdgpu_buffer_rsrc_t r, int 
 // out[n] = (sum|m-gt|/HW, sum m*gt, sum(m+gt-m*gt), sum edt*m/HW); one pass over the mask.
 // (prediction n is compared with reference n % RB: the G camera hypotheses of a frame share the
 // frame's ground truth, so the trainer's gt.repeat(G, ...) copies are never made)
-// k_mask_losses's body for workgroup `blk` of mesh n as functions, for k_step_tail: mask_losses_block leaves the four
-// waves' sums in s_red behind a barrier, mask_losses_value is what wave 0 hands to the finish in lane c < 4.  The
-// kernel below is the same text written out, not a caller of these: called from it they changed its register
-// allocation and schedule, and its machine code is pinned (tools/isa_diff.py against the parent; as k_bds_loss_sel
-// found before).  Same expressions in the same order under -ffp-contract=off: the same bits
-// (tests/test_gpu_step_tail.py compares them).  A change to one is a change to both.
+// k_mask_losses's body for workgroup `blk` of mesh n also runs as a role of k_step_tail: mask_losses_block leaves the
+// four waves' sums in s_red behind a barrier, mask_losses_value is what wave 0 hands to the finish in lane c < 4.
+// The body is ONE text, acfm_loss_body_mask.inc, #included in the kernel and in mask_losses_block -- not a function
+// that both call: called from the kernel, the function changed its register allocation and schedule, and its machine
+// code is pinned (tools/isa_diff.py against the parent; DESIGN.md, "The step's tail in one launch").  One text under
+// -ffp-contract=off: the same bits (tests/test_gpu_step_tail.py compares them).  (mask_losses_value the kernel does
+// call: that leaves its machine code as it is.)
 template <int PIX_FWD>
 __device__ __forceinline__ void mask_losses_block(const float* __restrict__ mask, const float* __restrict__ gt,
                                                   const float* __restrict__ edt, int HW, int RB, int n, int blk,
                                                   float (&s_red)[4][4]) {
-  const int tid = threadIdx.x;
-  const size_t base = (size_t)n * HW, rbase = (size_t)(n % RB) * HW;
-  const int start = blk * PIX_FWD;
-  const int end = min(start + PIX_FWD, HW);
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  const bool vec = ((HW & 3) == 0);
-  if (vec) {
-    // the block's two 16-byte pieces per thread and array are loaded before any of them is used
-    constexpr int U = PIX_FWD / (LTPB * 4);
-    static_assert(PIX_FWD % (LTPB * 4) == 0, "whole rounds of one 16-byte piece per thread");
-    float4 m[U], g[U], e[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = start + (u * LTPB + tid) * 4;
-      const bool in = i < end;
-      m[u] = in ? *reinterpret_cast<const float4*>(mask + base + i) : make_float4(0, 0, 0, 0);
-      g[u] = (in && gt) ? *reinterpret_cast<const float4*>(gt + rbase + i) : make_float4(0, 0, 0, 0);
-    }
-    // edt m is +0 wherever the rendered mask is 0 (most of a frame): edt is fetched only for the pieces whose four mask
-    // values are not all zero -- the other lanes present an offset outside the workgroup's range and get zeros back
-    // without a memory access (load16_in_range), and a3 + (+0) == a3
-    if (edt) {
-      const __amdgpu_buffer_rsrc_t re = pixel_range(edt + rbase + start, (unsigned)(end - start) * 4u);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const bool want = m[u].x != 0.f || m[u].y != 0.f || m[u].z != 0.f || m[u].w != 0.f;
-        e[u] = load16_in_range(re, want ? (u * LTPB + tid) * 16 : OUT_OF_RANGE);
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < U; ++u) e[u] = make_float4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      a0 += fabsf(m[u].x - g[u].x) + fabsf(m[u].y - g[u].y) + fabsf(m[u].z - g[u].z) + fabsf(m[u].w - g[u].w);
-      a1 += m[u].x * g[u].x + m[u].y * g[u].y + m[u].z * g[u].z + m[u].w * g[u].w;
-      a2 += (m[u].x + g[u].x - m[u].x * g[u].x) + (m[u].y + g[u].y - m[u].y * g[u].y) +
-            (m[u].z + g[u].z - m[u].z * g[u].z) + (m[u].w + g[u].w - m[u].w * g[u].w);
-      a3 += e[u].x * m[u].x + e[u].y * m[u].y + e[u].z * m[u].z + e[u].w * m[u].w;
-    }
-  } else {
-    for (int i = start + tid; i < end; i += LTPB) {
-      const float m = mask[base + i], g = gt ? gt[rbase + i] : 0.f, e = edt ? edt[rbase + i] : 0.f;
-      a0 += fabsf(m - g); a1 += m * g; a2 += m + g - m * g; a3 += e * m;
-    }
-  }
-  a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3);
-  const int w = tid >> 6;
-  if ((tid & 63) == 0) { s_red[w][0] = a0; s_red[w][1] = a1; s_red[w][2] = a2; s_red[w][3] = a3; }
-  __syncthreads();
+#include "acfm_loss_body_mask.inc"
 }
 __device__ __forceinline__ float mask_losses_value(const float (&s_red)[4][4], int HW) {
   const int tid = threadIdx.x;
@@ -113,62 +65,11 @@ __global__ __launch_bounds__(LTPB) void k_mask_losses(const float* __restrict__ 
                                                       const float* __restrict__ edt, int HW, int RB,
                                                       float* __restrict__ out, RowScratch sc) {
   __shared__ float s_red[4][4];
-  const int n = blockIdx.y, tid = threadIdx.x;
-  const size_t base = (size_t)n * HW, rbase = (size_t)(n % RB) * HW;
-  const int start = blockIdx.x * PIX_FWD;
-  const int end = min(start + PIX_FWD, HW);
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  const bool vec = ((HW & 3) == 0);
-  if (vec) {
-    // the block's two 16-byte pieces per thread and array are loaded before any of them is used
-    constexpr int U = PIX_FWD / (LTPB * 4);
-    static_assert(PIX_FWD % (LTPB * 4) == 0, "whole rounds of one 16-byte piece per thread");
-    float4 m[U], g[U], e[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = start + (u * LTPB + tid) * 4;
-      const bool in = i < end;
-      m[u] = in ? *reinterpret_cast<const float4*>(mask + base + i) : make_float4(0, 0, 0, 0);
-      g[u] = (in && gt) ? *reinterpret_cast<const float4*>(gt + rbase + i) : make_float4(0, 0, 0, 0);
-    }
-    // edt m is +0 wherever the rendered mask is 0 (most of a frame): edt is fetched only for the pieces whose four mask
-    // values are not all zero -- the other lanes present an offset outside the workgroup's range and get zeros back
-    // without a memory access (load16_in_range), and a3 + (+0) == a3
-    if (edt) {
-      const __amdgpu_buffer_rsrc_t re = pixel_range(edt + rbase + start, (unsigned)(end - start) * 4u);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const bool want = m[u].x != 0.f || m[u].y != 0.f || m[u].z != 0.f || m[u].w != 0.f;
-        e[u] = load16_in_range(re, want ? (u * LTPB + tid) * 16 : OUT_OF_RANGE);
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < U; ++u) e[u] = make_float4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      a0 += fabsf(m[u].x - g[u].x) + fabsf(m[u].y - g[u].y) + fabsf(m[u].z - g[u].z) + fabsf(m[u].w - g[u].w);
-      a1 += m[u].x * g[u].x + m[u].y * g[u].y + m[u].z * g[u].z + m[u].w * g[u].w;
-      a2 += (m[u].x + g[u].x - m[u].x * g[u].x) + (m[u].y + g[u].y - m[u].y * g[u].y) +
-            (m[u].z + g[u].z - m[u].z * g[u].z) + (m[u].w + g[u].w - m[u].w * g[u].w);
-      a3 += e[u].x * m[u].x + e[u].y * m[u].y + e[u].z * m[u].z + e[u].w * m[u].w;
-    }
-  } else {
-    for (int i = start + tid; i < end; i += LTPB) {
-      const float m = mask[base + i], g = gt ? gt[rbase + i] : 0.f, e = edt ? edt[rbase + i] : 0.f;
-      a0 += fabsf(m - g); a1 += m * g; a2 += m + g - m * g; a3 += e * m;
-    }
-  }
-  a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3);
-  const int w = tid >> 6;
-  if ((tid & 63) == 0) { s_red[w][0] = a0; s_red[w][1] = a1; s_red[w][2] = a2; s_red[w][3] = a3; }
-  __syncthreads();
+  const int n = blockIdx.y;
+  const unsigned blk = blockIdx.x;
+#include "acfm_loss_body_mask.inc"
   if (tid >= 64) return;
-  float v = 0.f;
-  if (tid < 4) {
-    v = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
-    if (tid == 0 || tid == 3) v = v / (float)HW;
-  }
+  const float v = mask_losses_value(s_red, HW);
   if (sc.tickets) row_finish<4>(sc, n, (int)gridDim.x, (int)blockIdx.x, v, out + 4 * (size_t)n);
   else if (tid < 4) atomicAdd(&out[4 * (size_t)n + tid], v);
 }
@@ -209,76 +110,13 @@ __global__ __launch_bounds__(LTPB) void k_mask_losses_bwd(const float* __restric
 
 // masked texture MSE (multiframe/main.py:655-662): per mesh mean over (3,H,W) of
 // (tex*m - img*m)^2; the workgroups' sums are added by row_finish (or, without scratch, one atomic per workgroup).
-// (tex_mse_block: k_tex_mse's body for workgroup `blk` of mesh n up to the four waves' sums in s_red, for k_step_tail;
-// a second copy of the kernel's text for the reason given at mask_losses_block)
+// (tex_mse_block: k_tex_mse's body for workgroup `blk` of mesh n up to the four waves' sums in s_red, for k_step_tail.
+// One text, acfm_loss_body_tex_mse.inc, included in both for the reason given at mask_losses_block.)
 template <int PIX_FWD>
 __device__ __forceinline__ void tex_mse_block(const float* __restrict__ tex, const float* __restrict__ img,
                                               const float* __restrict__ m, int HW, int RB, int n, int blk,
                                               float (&s_red)[4]) {
-  const int tid = threadIdx.x;
-  const size_t b3 = (size_t)n * 3 * HW, r3 = (size_t)(n % RB) * 3 * HW, b1 = (size_t)(n % RB) * HW;
-  const int start = blk * PIX_FWD;
-  const int end = min(start + PIX_FWD, HW);
-  float acc = 0.f;
-  if ((HW & 3) == 0) {   // 16-byte loads
-    // The mask first: where a piece's four mask values are all zero, (t m - g m)^2 is +0 for finite t and g and
-    // acc + (+0) == acc, so the piece's six colour loads fetch nothing (the reference mask covers about a sixth of
-    // a frame).  No branch does that: the colours come through buffer loads over the workgroup's pixel range, and a
-    // lane whose piece is not wanted (or lies past the end) presents an offset outside the range, for which the
-    // hardware returns zeros without a memory access.  Every piece then goes through the same expression in the
-    // same order as before; an unread piece contributes (0 * 0 - 0 * 0)^2 = +0.
-    constexpr int U = PIX_FWD / (LTPB * 4);
-    constexpr int UB = U < 4 ? U : 4;   // pieces whose colour loads are in flight together (24 VGPRs each)
-    static_assert(PIX_FWD % (LTPB * 4) == 0 && U % UB == 0, "a workgroup's pixels are whole rounds of one 16-byte piece per thread");
-    const unsigned range_bytes = (unsigned)(end - start) * 4u;   // <= PIX_FWD * 4
-    const __amdgpu_buffer_rsrc_t rm = pixel_range(m + b1 + start, range_bytes);
-    float4 mk[U];   // (the same way: a piece past the end reads as zeros, and no branch splits the loads up)
-#pragma unroll
-    for (int u = 0; u < U; ++u) mk[u] = load16_in_range(rm, (u * LTPB + tid) * 16);
-    __amdgpu_buffer_rsrc_t rt[3], rg[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      rt[c] = pixel_range(tex + b3 + (size_t)c * HW + start, range_bytes);
-      rg[c] = pixel_range(img + r3 + (size_t)c * HW + start, range_bytes);
-    }
-#pragma unroll
-    for (int u0 = 0; u0 < U; u0 += UB) {
-      float4 t[UB][3], g[UB][3];
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const float4 k = mk[u0 + u];
-        const bool want = k.x != 0.f || k.y != 0.f || k.z != 0.f || k.w != 0.f;
-        const int off = want ? ((u0 + u) * LTPB + tid) * 16 : OUT_OF_RANGE;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          t[u][c] = load16_in_range(rt[c], off);
-          g[u][c] = load16_in_range(rg[c], off);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const float4 k = mk[u0 + u];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float d0 = t[u][c].x * k.x - g[u][c].x * k.x, d1 = t[u][c].y * k.y - g[u][c].y * k.y;
-          const float d2 = t[u][c].z * k.z - g[u][c].z * k.z, d3 = t[u][c].w * k.w - g[u][c].w * k.w;
-          acc += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-        }
-      }
-    }
-  } else
-  for (int i = start + tid; i < end; i += LTPB) {
-    const float mk = m[b1 + i];
-    if (mk == 0.f) continue;   // adds +0 for finite colours: not read
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float d = tex[b3 + (size_t)c * HW + i] * mk - img[r3 + (size_t)c * HW + i] * mk;
-      acc += d * d;
-    }
-  }
-  acc = wave_sum(acc);
-  if ((tid & 63) == 0) s_red[tid >> 6] = acc;
-  __syncthreads();
+#include "acfm_loss_body_tex_mse.inc"
 }
 template <int PIX_FWD>
 __global__ __launch_bounds__(LTPB) void k_tex_mse(const float* __restrict__ tex,
@@ -286,70 +124,9 @@ __global__ __launch_bounds__(LTPB) void k_tex_mse(const float* __restrict__ tex,
                                                   const float* __restrict__ m, int HW, int RB,
                                                   float* __restrict__ out, RowScratch sc) {
   __shared__ float s_red[4];
-  const int n = blockIdx.y, tid = threadIdx.x;
-  const size_t b3 = (size_t)n * 3 * HW, r3 = (size_t)(n % RB) * 3 * HW, b1 = (size_t)(n % RB) * HW;
-  const int start = blockIdx.x * PIX_FWD;
-  const int end = min(start + PIX_FWD, HW);
-  float acc = 0.f;
-  if ((HW & 3) == 0) {   // 16-byte loads
-    // The mask first: where a piece's four mask values are all zero, (t m - g m)^2 is +0 for finite t and g and
-    // acc + (+0) == acc, so the piece's six colour loads fetch nothing (the reference mask covers about a sixth of
-    // a frame).  No branch does that: the colours come through buffer loads over the workgroup's pixel range, and a
-    // lane whose piece is not wanted (or lies past the end) presents an offset outside the range, for which the
-    // hardware returns zeros without a memory access.  Every piece then goes through the same expression in the
-    // same order as before; an unread piece contributes (0 * 0 - 0 * 0)^2 = +0.
-    constexpr int U = PIX_FWD / (LTPB * 4);
-    constexpr int UB = U < 4 ? U : 4;   // pieces whose colour loads are in flight together (24 VGPRs each)
-    static_assert(PIX_FWD % (LTPB * 4) == 0 && U % UB == 0, "a workgroup's pixels are whole rounds of one 16-byte piece per thread");
-    const unsigned range_bytes = (unsigned)(end - start) * 4u;   // <= PIX_FWD * 4
-    const __amdgpu_buffer_rsrc_t rm = pixel_range(m + b1 + start, range_bytes);
-    float4 mk[U];   // (the same way: a piece past the end reads as zeros, and no branch splits the loads up)
-#pragma unroll
-    for (int u = 0; u < U; ++u) mk[u] = load16_in_range(rm, (u * LTPB + tid) * 16);
-    __amdgpu_buffer_rsrc_t rt[3], rg[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      rt[c] = pixel_range(tex + b3 + (size_t)c * HW + start, range_bytes);
-      rg[c] = pixel_range(img + r3 + (size_t)c * HW + start, range_bytes);
-    }
-#pragma unroll
-    for (int u0 = 0; u0 < U; u0 += UB) {
-      float4 t[UB][3], g[UB][3];
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const float4 k = mk[u0 + u];
-        const bool want = k.x != 0.f || k.y != 0.f || k.z != 0.f || k.w != 0.f;
-        const int off = want ? ((u0 + u) * LTPB + tid) * 16 : OUT_OF_RANGE;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          t[u][c] = load16_in_range(rt[c], off);
-          g[u][c] = load16_in_range(rg[c], off);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const float4 k = mk[u0 + u];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float d0 = t[u][c].x * k.x - g[u][c].x * k.x, d1 = t[u][c].y * k.y - g[u][c].y * k.y;
-          const float d2 = t[u][c].z * k.z - g[u][c].z * k.z, d3 = t[u][c].w * k.w - g[u][c].w * k.w;
-          acc += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-        }
-      }
-    }
-  } else
-  for (int i = start + tid; i < end; i += LTPB) {
-    const float mk = m[b1 + i];
-    if (mk == 0.f) continue;   // adds +0 for finite colours: not read
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float d = tex[b3 + (size_t)c * HW + i] * mk - img[r3 + (size_t)c * HW + i] * mk;
-      acc += d * d;
-    }
-  }
-  acc = wave_sum(acc);
-  if ((tid & 63) == 0) s_red[tid >> 6] = acc;
-  __syncthreads();
+  const int n = blockIdx.y;
+  const unsigned blk = blockIdx.x;
+#include "acfm_loss_body_tex_mse.inc"
   if (tid >= 64) return;
   const float v = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) / (3.0f * (float)HW);
   if (sc.tickets) row_finish<1>(sc, n, (int)gridDim.x, (int)blockIdx.x, v, out + n);
@@ -416,101 +193,25 @@ __global__ void k_visible(const int64_t* __restrict__ p2f, const int64_t* __rest
 // straight from memory into LDS, 64 vertices a round, keeping the visible ones packed in ascending order
 // (ballot + prefix count) next to the index each came from.  A wave reads no other wave's quarter, so no
 // workgroup barrier stands between the staging and the search.
-// (bds_block: the body of k_bds_loss / k_bds_loss_sel below for workgroup `blk` of mesh n, for k_step_tail -- a copy of
-// their text for the reason given at mask_losses_block; true in wave 0, which then carries the workgroup's sum in
-// `contrib`.)
 // SEL: the lane's point is read through a slot list, sel [rows][S] (acfm_boundary_subset): lane p < S takes slot
 // s = sel[((n % RB) % rows) S + p] of its reference's P points; s < 0 is an empty entry (adds 0, argmin -1).  argmin
 // is then [N][S], and no gathered copy of the points exists.
+// ONE text, in two fragments, for k_bds_loss, k_bds_loss_sel and k_step_tail's role bds_block<SEL>:
+// acfm_loss_body_bds_search.inc up to the barrier behind the four waves' minima, acfm_loss_body_bds_merge.inc for wave
+// 0 behind it.  The fragments are #included at each of the three places, not called: with the body in a common
+// function (or the two kernels as one template) the compiler allocated the kernels' registers differently, and their
+// machine code is pinned (tools/isa_diff.py against the parent; DESIGN.md, "The step's tail in one launch").  What
+// differs stands in the including function: its LDS arrays, n and blk, SEL with sel / rows / S, where `contrib`
+// lives, and every return.
+// (bds_block: true in wave 0, which then carries the workgroup's sum in `contrib`.)
 template <bool SEL>
 __device__ __forceinline__ bool bds_block(const float* __restrict__ verts_xy, const float* __restrict__ bds,
                                           const uint8_t* __restrict__ vis, int V, int P, int RB, int n, int blk,
                                           int32_t* __restrict__ argmin, const int32_t* __restrict__ sel, int rows, int S,
                                           float (&s_best)[4][64], int (&s_bi)[4][64], float& contrib) {
-  extern __shared__ float s_xy[];  // [V][2]: per quarter, its visible vertices packed to the front; then int s_idx[V]
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  // the lane's boundary point first: its load is in flight while the vertices are staged
-  const int p = blk * 64 + lane;
-  float bx = 0.f, by = 0.f, bm = 0.f;
-  bool empty = false;
-  if constexpr (SEL) {
-    int s = -1;
-    if (p < S) s = sel[(size_t)((n % RB) % rows) * S + p];
-    empty = s < 0 || s >= P;
-    if (!empty) {
-      const float* b = bds + ((size_t)(n % RB) * P + s) * 3;
-      bx = b[0]; by = b[1]; bm = b[2];
-    }
-  } else {
-    if (p < P) {
-      const float* b = bds + ((size_t)(n % RB) * P + p) * 3;
-      bx = b[0]; by = b[1]; bm = b[2];
-    }
-  }
-  const int chunk = (V + 3) / 4, v0 = wv * chunk, v1 = min(V, v0 + chunk);
-  int* s_idx = reinterpret_cast<int*>(s_xy + 2 * (size_t)V);
-  int nvis = 0;
-  {
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    // (unconditional loads, four rounds in flight: with the loads behind the visibility test the staging was a
-    // chain of memory latencies)
-    for (int base = v0; base < v1; base += 4 * 64) {
-      uint8_t vz[4];
-      float2 xy[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int v = min(base + u * 64 + lane, v1 - 1);
-        vz[u] = vis[(size_t)n * V + v];
-        xy[u] = *reinterpret_cast<const float2*>(verts_xy + ((size_t)n * V + v) * 2);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int v = base + u * 64 + lane;
-        const bool keep = (v < v1) && vz[u] != 0;
-        const unsigned long long m = __ballot(keep);
-        if (keep) {
-          const int pos = v0 + nvis + __popcll(m & lt);
-          *reinterpret_cast<float2*>(s_xy + 2 * pos) = xy[u];
-          s_idx[pos] = v;
-        }
-        nvis += __popcll(m);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-  float best = 1000.0f;  // loss_utils.py:228: invisible vertices sit at distance 1000
-  int bi = -1;
-#pragma unroll 8
-  for (int v = v0; v < v0 + nvis; ++v) {
-    const float2 q = *reinterpret_cast<const float2*>(s_xy + 2 * v);
-    const float dx = bx - q.x, dy = by - q.y;
-    const float d = dx * dx + dy * dy;
-    if (d < best) { best = d; bi = v; }
-  }
-  if (bi >= 0) bi = s_idx[bi];
-  s_best[wv][lane] = best; s_bi[wv][lane] = bi;
-  __syncthreads();
+#include "acfm_loss_body_bds_search.inc"
   if (wv != 0) return false;
-#pragma unroll
-  for (int w = 1; w < 4; ++w) {
-    const float d = s_best[w][lane];
-    if (d < best) { best = d; bi = s_bi[w][lane]; }
-  }
-  contrib = 0.f;
-  if constexpr (SEL) {
-    if (p < S) {
-      contrib = empty ? 0.f : best * bm;
-      argmin[(size_t)n * S + p] = empty ? -1 : bi;
-    }
-  } else {
-    if (p < P) {
-      contrib = best * bm;
-      argmin[(size_t)n * P + p] = bi;
-    }
-  }
-  contrib = wave_sum(contrib);
+#include "acfm_loss_body_bds_merge.inc"
   return true;
 }
 __global__ __launch_bounds__(LTPB) void k_bds_loss(const float* __restrict__ verts_xy,
@@ -518,161 +219,37 @@ __global__ __launch_bounds__(LTPB) void k_bds_loss(const float* __restrict__ ver
                                                    const uint8_t* __restrict__ vis, int V, int P, int RB,
                                                    float* __restrict__ loss, int32_t* __restrict__ argmin,
                                                    RowScratch sc) {
-  extern __shared__ float s_xy[];  // [V][2]: per quarter, its visible vertices packed to the front; then int s_idx[V]
   __shared__ float s_best[4][64];
   __shared__ int s_bi[4][64];
-  const int n = blockIdx.y, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  // the lane's boundary point first: its load is in flight while the vertices are staged
-  const int p = blockIdx.x * 64 + lane;
-  float bx = 0.f, by = 0.f, bm = 0.f;
-  if (p < P) {
-    const float* b = bds + ((size_t)(n % RB) * P + p) * 3;
-    bx = b[0]; by = b[1]; bm = b[2];
-  }
-  const int chunk = (V + 3) / 4, v0 = wv * chunk, v1 = min(V, v0 + chunk);
-  int* s_idx = reinterpret_cast<int*>(s_xy + 2 * (size_t)V);
-  int nvis = 0;
-  {
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    // (unconditional loads, four rounds in flight: with the loads behind the visibility test the staging was a
-    // chain of memory latencies)
-    for (int base = v0; base < v1; base += 4 * 64) {
-      uint8_t vz[4];
-      float2 xy[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int v = min(base + u * 64 + lane, v1 - 1);
-        vz[u] = vis[(size_t)n * V + v];
-        xy[u] = *reinterpret_cast<const float2*>(verts_xy + ((size_t)n * V + v) * 2);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int v = base + u * 64 + lane;
-        const bool keep = (v < v1) && vz[u] != 0;
-        const unsigned long long m = __ballot(keep);
-        if (keep) {
-          const int pos = v0 + nvis + __popcll(m & lt);
-          *reinterpret_cast<float2*>(s_xy + 2 * pos) = xy[u];
-          s_idx[pos] = v;
-        }
-        nvis += __popcll(m);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-  float best = 1000.0f;  // loss_utils.py:228: invisible vertices sit at distance 1000
-  int bi = -1;
-#pragma unroll 8
-  for (int v = v0; v < v0 + nvis; ++v) {
-    const float2 q = *reinterpret_cast<const float2*>(s_xy + 2 * v);
-    const float dx = bx - q.x, dy = by - q.y;
-    const float d = dx * dx + dy * dy;
-    if (d < best) { best = d; bi = v; }
-  }
-  if (bi >= 0) bi = s_idx[bi];
-  s_best[wv][lane] = best; s_bi[wv][lane] = bi;
-  __syncthreads();
+  constexpr bool SEL = false;
+  const int32_t* sel = nullptr;
+  const int rows = 0, S = 0;
+  const int n = blockIdx.y;
+  const unsigned blk = blockIdx.x;
+#include "acfm_loss_body_bds_search.inc"
   if (wv != 0) return;
-#pragma unroll
-  for (int w = 1; w < 4; ++w) {
-    const float d = s_best[w][lane];
-    if (d < best) { best = d; bi = s_bi[w][lane]; }
-  }
-  float contrib = 0.f;
-  if (p < P) {
-    contrib = best * bm;
-    argmin[(size_t)n * P + p] = bi;
-  }
-  contrib = wave_sum(contrib);
+  float contrib;
+#include "acfm_loss_body_bds_merge.inc"
   if (sc.tickets) row_finish<1>(sc, n, (int)gridDim.x, (int)blockIdx.x, contrib, loss + n);
   else if (lane == 0) atomicAdd(&loss[n], contrib);
 }
 
-// k_bds_loss with the lane's point read through a slot list, sel [rows][S] (acfm_boundary_subset): lane p < S takes
-// slot s = sel[((n % RB) % rows) S + p] of its reference's P points; s < 0 is an empty entry (adds 0, argmin -1).
-// argmin is [N][S], and no gathered copy of the points exists.  Everything after the point's load is k_bds_loss line
-// for line -- written out a second time, not shared through a template: with the body in a common function the
-// compiler allocated k_bds_loss's registers differently, and that kernel's machine code is pinned
-// (tools/isa_diff.py against the parent).
+// k_bds_loss with the lane's point read through the slot list (SEL above).
 __global__ __launch_bounds__(LTPB) void k_bds_loss_sel(const float* __restrict__ verts_xy,
                                                        const float* __restrict__ bds,
                                                        const uint8_t* __restrict__ vis, int V, int P, int RB,
                                                        float* __restrict__ loss, int32_t* __restrict__ argmin,
                                                        RowScratch sc, const int32_t* __restrict__ sel, int rows,
                                                        int S) {
-  extern __shared__ float s_xy[];  // [V][2]: per quarter, its visible vertices packed to the front; then int s_idx[V]
   __shared__ float s_best[4][64];
   __shared__ int s_bi[4][64];
-  const int n = blockIdx.y, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  // the lane's boundary point first: its load is in flight while the vertices are staged
-  const int p = blockIdx.x * 64 + lane;
-  float bx = 0.f, by = 0.f, bm = 0.f;
-  int s = -1;
-  if (p < S) s = sel[(size_t)((n % RB) % rows) * S + p];
-  const bool empty = s < 0 || s >= P;
-  if (!empty) {
-    const float* b = bds + ((size_t)(n % RB) * P + s) * 3;
-    bx = b[0]; by = b[1]; bm = b[2];
-  }
-  const int chunk = (V + 3) / 4, v0 = wv * chunk, v1 = min(V, v0 + chunk);
-  int* s_idx = reinterpret_cast<int*>(s_xy + 2 * (size_t)V);
-  int nvis = 0;
-  {
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    // (unconditional loads, four rounds in flight: with the loads behind the visibility test the staging was a
-    // chain of memory latencies)
-    for (int base = v0; base < v1; base += 4 * 64) {
-      uint8_t vz[4];
-      float2 xy[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int v = min(base + u * 64 + lane, v1 - 1);
-        vz[u] = vis[(size_t)n * V + v];
-        xy[u] = *reinterpret_cast<const float2*>(verts_xy + ((size_t)n * V + v) * 2);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int v = base + u * 64 + lane;
-        const bool keep = (v < v1) && vz[u] != 0;
-        const unsigned long long m = __ballot(keep);
-        if (keep) {
-          const int pos = v0 + nvis + __popcll(m & lt);
-          *reinterpret_cast<float2*>(s_xy + 2 * pos) = xy[u];
-          s_idx[pos] = v;
-        }
-        nvis += __popcll(m);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-  float best = 1000.0f;  // loss_utils.py:228: invisible vertices sit at distance 1000
-  int bi = -1;
-#pragma unroll 8
-  for (int v = v0; v < v0 + nvis; ++v) {
-    const float2 q = *reinterpret_cast<const float2*>(s_xy + 2 * v);
-    const float dx = bx - q.x, dy = by - q.y;
-    const float d = dx * dx + dy * dy;
-    if (d < best) { best = d; bi = v; }
-  }
-  if (bi >= 0) bi = s_idx[bi];
-  s_best[wv][lane] = best; s_bi[wv][lane] = bi;
-  __syncthreads();
+  constexpr bool SEL = true;
+  const int n = blockIdx.y;
+  const unsigned blk = blockIdx.x;
+#include "acfm_loss_body_bds_search.inc"
   if (wv != 0) return;
-#pragma unroll
-  for (int w = 1; w < 4; ++w) {
-    const float d = s_best[w][lane];
-    if (d < best) { best = d; bi = s_bi[w][lane]; }
-  }
-  float contrib = 0.f;
-  if (p < S) {
-    contrib = empty ? 0.f : best * bm;
-    argmin[(size_t)n * S + p] = empty ? -1 : bi;
-  }
-  contrib = wave_sum(contrib);
+  float contrib;
+#include "acfm_loss_body_bds_merge.inc"
   if (sc.tickets) row_finish<1>(sc, n, (int)gridDim.x, (int)blockIdx.x, contrib, loss + n);
   else if (lane == 0) atomicAdd(&loss[n], contrib);
 }
@@ -680,77 +257,29 @@ __global__ __launch_bounds__(LTPB) void k_bds_loss_sel(const float* __restrict__
 // One workgroup per mesh: the points' contributions are summed per vertex in LDS (P <= ~1000 points
 // onto V vertices) and the whole [V,2] gradient row is stored, zeros included -- no global atomics
 // (64 k scattered memory-side atomics took 13 us) and no zero fill of the output.
+// (one text for both kernels, acfm_loss_body_bds_bwd.inc: two kernels that include it, not one template, for the
+// reason given at the forward kernels)
 __global__ __launch_bounds__(256) void k_bds_loss_bwd(const float* __restrict__ verts_xy,
                                                       const float* __restrict__ bds,
                                                       const int32_t* __restrict__ argmin,
                                                       const float* __restrict__ gl, int V, int P, int RB,
                                                       float* __restrict__ gv) {
-  extern __shared__ float s_g[];  // [V][2]
-  const int n = blockIdx.x, tid = threadIdx.x;
-  for (int i = tid; i < 2 * V; i += 256) s_g[i] = 0.f;
-  __syncthreads();
-  const float go = gl[n];
-  for (int p0 = tid; p0 < P; p0 += 4 * 256) {      // four points per thread in flight
-    int v[4];
-    float bx[4], by[4], bm[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int p = min(p0 + u * 256, P - 1);
-      v[u] = (p0 + u * 256 < P) ? argmin[(size_t)n * P + p] : -1;
-      const float* b = bds + ((size_t)(n % RB) * P + p) * 3;
-      bx[u] = b[0]; by[u] = b[1]; bm[u] = b[2];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float g = go * bm[u];
-      if (v[u] < 0 || g == 0.f) continue;
-      const float* x = verts_xy + ((size_t)n * V + v[u]) * 2;
-      atomicAdd(&s_g[2 * v[u]], 2.0f * (x[0] - bx[u]) * g);
-      atomicAdd(&s_g[2 * v[u] + 1], 2.0f * (x[1] - by[u]) * g);
-    }
-  }
-  __syncthreads();
-  float* o = gv + (size_t)n * V * 2;
-  for (int i = tid; i < 2 * V; i += 256) o[i] = s_g[i];
+  constexpr bool SEL = false;
+  const int32_t* sel = nullptr;
+  const int rows = 0, S = 0;
+#include "acfm_loss_body_bds_bwd.inc"
 }
 
 // k_bds_loss_bwd over the entries of argmin [N][S]: entry p belongs to slot sel[((n % RB) % rows) S + p] (see
-// k_bds_loss_sel, also for why this is a second kernel and not a template).
+// k_bds_loss_sel).
 __global__ __launch_bounds__(256) void k_bds_loss_sel_bwd(const float* __restrict__ verts_xy,
                                                           const float* __restrict__ bds,
                                                           const int32_t* __restrict__ argmin,
                                                           const float* __restrict__ gl, int V, int P, int RB,
                                                           float* __restrict__ gv, const int32_t* __restrict__ sel,
                                                           int rows, int S) {
-  extern __shared__ float s_g[];  // [V][2]
-  const int n = blockIdx.x, tid = threadIdx.x;
-  for (int i = tid; i < 2 * V; i += 256) s_g[i] = 0.f;
-  __syncthreads();
-  const float go = gl[n];
-  for (int p0 = tid; p0 < S; p0 += 4 * 256) {      // four points per thread in flight
-    int v[4];
-    float bx[4], by[4], bm[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int p = min(p0 + u * 256, S - 1);
-      v[u] = (p0 + u * 256 < S) ? argmin[(size_t)n * S + p] : -1;
-      int s = sel[(size_t)((n % RB) % rows) * S + p];
-      if (s < 0 || s >= P) { s = 0; v[u] = -1; }   // an empty entry (its argmin is -1 already)
-      const float* b = bds + ((size_t)(n % RB) * P + s) * 3;
-      bx[u] = b[0]; by[u] = b[1]; bm[u] = b[2];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float g = go * bm[u];
-      if (v[u] < 0 || g == 0.f) continue;
-      const float* x = verts_xy + ((size_t)n * V + v[u]) * 2;
-      atomicAdd(&s_g[2 * v[u]], 2.0f * (x[0] - bx[u]) * g);
-      atomicAdd(&s_g[2 * v[u] + 1], 2.0f * (x[1] - by[u]) * g);
-    }
-  }
-  __syncthreads();
-  float* o = gv + (size_t)n * V * 2;
-  for (int i = tid; i < 2 * V; i += 256) o[i] = s_g[i];
+  constexpr bool SEL = true;
+#include "acfm_loss_body_bds_bwd.inc"
 }
 
 // ---- optical-flow loss (loss_utils.py:419-474), one workgroup per (clip, frame k >= 1) --------------

@@ -33,81 +33,30 @@ struct RowScratch {
   float* partials;     // [N][nblk][C], any contents
 };
 // Called by one whole wave (lanes 0..63 of it); lane c < C carries the workgroup's partial sum c in `mine`.
+// The hand-over with the ticket, and the in-order sum, are one text each for this function and row_finish_published:
+// two fragments included in both (why not a common function: see the fragments).  What differs between the two stands
+// here: the return behind the ticket and the way the row leaves.
 template <int C>
 __device__ __forceinline__ void row_finish(const RowScratch& sc, int row, int nblk, int blk, float mine,
                                            float* __restrict__ out_row) {
-  const int lane = threadIdx.x & 63;
-  unsigned* slot = reinterpret_cast<unsigned*>(sc.partials) + ((size_t)row * nblk + blk) * C;
-  unsigned old = 0u;
-  if (lane < C)
-    old = __hip_atomic_exchange(slot + lane, __float_as_uint(mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("" ::"v"(old));   // the old values are back: the exchanges were performed
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  unsigned ticket = 0u;
-  if (lane == 0) ticket = atomicInc(&sc.tickets[row], (unsigned)(nblk - 1));
-  ticket = __shfl(ticket, 0, 64);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#include "acfm_row_finish_handover.inc"
   if (ticket != (unsigned)(nblk - 1)) return;
-  const unsigned* rowp = reinterpret_cast<const unsigned*>(sc.partials) + (size_t)row * nblk * C;
-  float acc[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) acc[c] = 0.f;
-  for (int b0 = 0; b0 < nblk; b0 += 64) {    // lane l holds workgroup b0 + l; added one after the other, in order
-    float x[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-      x[c] = (b0 + lane < nblk) ? __uint_as_float(__hip_atomic_load(rowp + (size_t)(b0 + lane) * C + c, __ATOMIC_RELAXED,
-                                                                    __HIP_MEMORY_SCOPE_AGENT))
-                                : 0.f;
-    const int cnt = min(64, nblk - b0);
-    for (int l = 0; l < cnt; ++l) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) acc[c] += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[c]), l));
-    }
-  }
+#include "acfm_row_finish_sum.inc"
 #pragma unroll
   for (int c = 0; c < C; ++c)
     if (lane == c) out_row[c] = acc[c];
 }
 
 // row_finish for a launch whose workgroups go on to read the rows that OTHER workgroups finished (k_step_tail's
-// total).  The hand-over, the ticket and the sum are row_finish line for line -- written out a second time, not shared:
-// with the sum in a common function the compiler scheduled every kernel that calls row_finish differently, and their
-// machine code is pinned (tools/isa_diff.py against the parent) -- so a row has the same bits.  The row then leaves
-// as returning device-scope exchanges, like the partials, and has been performed where every XCD sees it when this
-// returns true: in the wave that finished the row, and in no other.
+// total).  The hand-over, the ticket and the sum are row_finish's own text (the two fragments), so a row has the same
+// bits.  The row then leaves as returning device-scope exchanges, like the partials, and has been performed where
+// every XCD sees it when this returns true: in the wave that finished the row, and in no other.
 template <int C>
 __device__ __forceinline__ bool row_finish_published(const RowScratch& sc, int row, int nblk, int blk, float mine,
                                                      float* __restrict__ out_row) {
-  const int lane = threadIdx.x & 63;
-  unsigned* slot = reinterpret_cast<unsigned*>(sc.partials) + ((size_t)row * nblk + blk) * C;
-  unsigned old = 0u;
-  if (lane < C)
-    old = __hip_atomic_exchange(slot + lane, __float_as_uint(mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("" ::"v"(old));   // the old values are back: the exchanges were performed
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  unsigned ticket = 0u;
-  if (lane == 0) ticket = atomicInc(&sc.tickets[row], (unsigned)(nblk - 1));
-  ticket = __shfl(ticket, 0, 64);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#include "acfm_row_finish_handover.inc"
   if (ticket != (unsigned)(nblk - 1)) return false;
-  const unsigned* rowp = reinterpret_cast<const unsigned*>(sc.partials) + (size_t)row * nblk * C;
-  float acc[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) acc[c] = 0.f;
-  for (int b0 = 0; b0 < nblk; b0 += 64) {    // lane l holds workgroup b0 + l; added one after the other, in order
-    float x[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-      x[c] = (b0 + lane < nblk) ? __uint_as_float(__hip_atomic_load(rowp + (size_t)(b0 + lane) * C + c, __ATOMIC_RELAXED,
-                                                                    __HIP_MEMORY_SCOPE_AGENT))
-                                : 0.f;
-    const int cnt = min(64, nblk - b0);
-    for (int l = 0; l < cnt; ++l) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) acc[c] += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[c]), l));
-    }
-  }
+#include "acfm_row_finish_sum.inc"
   float v = 0.f;
 #pragma unroll
   for (int c = 0; c < C; ++c)

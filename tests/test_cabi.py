@@ -61,7 +61,7 @@ def test_product_does_not_import_oracle():
     pkg = os.path.join(ROOT, "acfm_video_3d_reconstruction_amd")
     for dp, _, fns in os.walk(pkg):
         for fn in fns:
-            if fn.endswith((".py", ".hip", ".h", ".cpp")):
+            if fn.endswith((".py", ".hip", ".h", ".inc", ".cpp")):
                 src = open(os.path.join(dp, fn)).read()
                 assert not re.search(r"^\s*(from|import)\s+oracle", src, flags=re.M), fn
                 assert "libacfm_oracle" not in src, fn
