@@ -145,6 +145,14 @@ SIGNATURES = {
     "acfm_lpips_mask_weights": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "acfm_lpips_masked_mean_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "acfm_lpips_masked_mean_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "acfm_kp_weights_forward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "acfm_kp_weights_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "acfm_kp_head_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "acfm_kp_head_workspace_bytes": (_sz, [_i, _i]),
+    "acfm_kp_head_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+                                   _sz, _vp]),
+    "acfm_camera_loss_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+    "acfm_camera_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]),
 }
 
 _ERR = {1: "ACFM_E_BADARG (shape/parameter outside what the kernels support)",

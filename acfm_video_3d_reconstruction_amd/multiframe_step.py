@@ -52,8 +52,11 @@ def _y_rotation_quats(num_guesses):
 
 class MultiframeStep(nn.Module):
     def __init__(self, mean_v, faces, lbs_logits, num_training_frames, img_size=256, vert2kp=None, prior_stream=False,
-                 boundary_sampler=None, **opts):
+                 boundary_sampler=None, supervision_kernels=False, **opts):
         super().__init__()
+        # supervision_kernels=True (GPU tensors only): the keypoint term comes from keypoints.KeypointHead and the camera
+        # head's loss from ops.camera_loss (csrc/acfm_keypoints.hip) instead of the chains of torch ops below
+        self.supervision_kernels, self._kp_head = bool(supervision_kernels), None
         # boundary_sampling.BoundarySampler: the boundary loss draws its <= n_samples points on the device (main.py:
         # 715-716 draws on the host), so the step can be captured with batch["boundaries"] of any length; the lists'
         # true lengths are read from batch.get("boundary_counts") (int32 [B*T] on the device)
@@ -95,6 +98,13 @@ class MultiframeStep(nn.Module):
         from .sharding import SharedShapeExchange
         extra = [self.vert2kp] if isinstance(self.vert2kp, nn.Parameter) else []
         return SharedShapeExchange(self.solver, extra_params=extra, group=group, average=average)
+
+    def _keypoint_head(self):
+        # (kept beside the module tree, and rebuilt when vert2kp is replaced: the state dict keeps its keys)
+        if self._kp_head is None or self._kp_head[0].vert2kp is not self.vert2kp:
+            from .keypoints import KeypointHead
+            self._kp_head = [KeypointHead(self.vert2kp)]
+        return self._kp_head[0]
 
     def set_num_guesses(self, k):
         """train_utils.py:236-241: after the first epochs only the k most probable hypotheses of
@@ -174,7 +184,11 @@ class MultiframeStep(nn.Module):
         _, mask_loss, sil_cons = self._silhouette_terms(mean_v, faces, cam, batch, G)
         total = o.mask_loss_wt * mask_loss.reshape(G, N) + o.of_loss_wt * self._flow_term(mean_v, cam, batch, G) \
             + o.boundaries_reg_wt * sil_cons.reshape(G, N)
-        if o.kp_loss_wt > 0 and self.vert2kp is not None:
+        if o.kp_loss_wt > 0 and self.vert2kp is not None and self.supervision_kernels and cam.is_cuda:
+            # the mean shape once, the frames' keypoints once: hypothesis g*N + n reads row 0 / row n of them
+            kp = self._keypoint_head()(self.solver.mean_v[None], cam, batch["kps"]).loss
+            total = total + o.kp_loss_wt * kp.reshape(G, N)
+        elif o.kp_loss_wt > 0 and self.vert2kp is not None:
             kp_v = torch.matmul(torch.softmax(self.vert2kp, dim=1), mean_v)
             kp = loss_utils.kp_l2_loss(self.renderer.project_points(kp_v, cam), batch["kps"].repeat(G, 1, 1),
                                        reduction="none")
@@ -258,11 +272,17 @@ class MultiframeStep(nn.Module):
                 raise ValueError("optical-flow term has %d elements for %d hypotheses x %d frames (num_frames must be 2, "
                                  "multiframe/main.py:684-686)" % (of_term.numel(), G, N))
             tl.append(of_term); tw.append(o.of_loss_wt); tg.append(-1); ta.append(0.0)
+        kernels = self.supervision_kernels and cam.is_cuda
         if o.kp_loss_wt > 0 and self.vert2kp is not None:
-            kp_v = torch.matmul(torch.softmax(self.vert2kp, dim=1), pred_v)
-            kp = loss_utils.kp_l2_loss(self.renderer.project_points(kp_v, cam), batch["kps"].repeat(G, 1, 1),
-                                       reduction="none")
+            if kernels:     # the N deformed shapes and the frames' keypoints unrepeated, the G*N cameras
+                kp_out = self._keypoint_head()(pred_v1, cam, batch["kps"])
+                kp_pred, kp = kp_out.kp_pred, kp_out.loss
+            else:
+                kp_v = torch.matmul(torch.softmax(self.vert2kp, dim=1), pred_v)
+                kp_pred = self.renderer.project_points(kp_v, cam)
+                kp = loss_utils.kp_l2_loss(kp_pred, batch["kps"].repeat(G, 1, 1), reduction="none")
             tl.append(kp); tw.append(o.kp_loss_wt); tg.append(-1); ta.append(0.0)
+            terms.update(kp_loss=kp.reshape(G, N).detach(), kp_pred=kp_pred.detach())
         have_tex = textures is not None and imgs is not None
         if have_tex:
             # texture branch on detached geometry, original + mirrored camera (main.py:627-636, 655-662); the LPIPS
@@ -314,9 +334,13 @@ class MultiframeStep(nn.Module):
             loss = loss + o.deform_reg_wt * cycle                # main.py:749 (deform_reg_wt weighs the texture cycle term)
             terms["cycle"] = cycle.detach()
         if predicted_camera is not None:           # main.py:753-762: camera head vs the most probable hypothesis
-            best = probs.reshape(G, N).argmax(dim=0)
-            cam_sel = cam.reshape(G, N, 7)[best, torch.arange(N, device=cam.device)]
-            cam_head = loss_utils.camera_loss(predicted_camera, cam_sel.detach(), 0)
+            if kernels:
+                from . import ops
+                cam_head, _ = ops.camera_loss(predicted_camera, cams=cam, probs=probs.reshape(G, N))
+            else:
+                best = probs.reshape(G, N).argmax(dim=0)
+                cam_sel = cam.reshape(G, N, 7)[best, torch.arange(N, device=cam.device)]
+                cam_head = loss_utils.camera_loss(predicted_camera, cam_sel.detach(), 0)
             loss = loss + o.cam_loss_wt * cam_head
             terms["cam_loss"] = cam_head.detach()
         if o.optimize_deform:                      # main.py:763-765: encoder head vs the per-frame deformation embedding

@@ -911,6 +911,47 @@ int acfm_lpips_masked_mean_forward(const float* d, const float* M, int N, int Nr
 int acfm_lpips_masked_mean_backward(const float* grad_loss, const float* M, int N, int Nr, int P, float* grad_d,
                                     void* stream);
 
+/* ---- keypoint supervision (multiframe/main.py:503-511, 690-696, 753-762; loss_utils.py:256-289, 330-356) -------------
+ * replaces softmax(vert2kp) @ pred_v -> project_points -> kp_l2_loss, the vert2kp entropy prior, the camera head's
+ * loss against the most probable hypothesis (or a given camera) and evaluate.py:156-158's pixel error, with their
+ * autograd backward.  float32, contiguous.  Limits (else ACFM_E_BADARG): 1 <= K <= 64 keypoints, 1 <= V <= 65535,
+ * N <= 65535, N % Nv == 0, N % Ng == 0.  N == 0: returns 0, launches nothing.  No float atomics, no workgroup waits on
+ * another, fixed summation orders (bit-reproducible), nothing allocated: every call can be captured.
+ * acfm_kp_weights_forward: logits [K,V] -> A = softmax(logits, 1) [K,V]; stats [K,2] = (row maximum, log sum exp of
+ *   the shifted row), kept for the backward; entropy [1] = mean_k(-sum_v A logA), logA = (logit - max) - log sum: the
+ *   log-softmax form of entropy_loss(A), finite where A underflows to 0.  One launch.
+ * acfm_kp_weights_backward: grad_A [K,V] and grad_entropy [1] (device scalar), either may be NULL -> grad_logits [K,V].
+ * acfm_kp_head_forward: A [K,V], verts [Nv,V,3], cams [N,7], kp_gt [Ng,K,3] or NULL ->
+ *   kp_verts [Nv,K,3] = A @ verts[r]; kp_pred [N,K,2] = (x, y) of orthographic_proj_withz(kp_verts[n % Nv], cams[n], 0):
+ *   the bits of acfm_project_xy on kp_verts; with kp_gt (row n % Ng; vis_k = kp_gt[..,2] > 0)
+ *   loss [N] = mean_k(vis_k (|dx| + |dy|)) / (mean_k vis_k + 1e-4)  (kp_l2_loss, reduction='none'), and, if kp_err is
+ *   not NULL, kp_err [N,K] = sqrt(dx^2 + dy^2) img_size / 2.  Hypothesis n of frame n % Nv: the G = N / Nv hypotheses
+ *   of a frame share its vertices (and ground truth); no repeated copy is read.  One launch of Nv workgroups.
+ * acfm_kp_head_backward: grad_loss [N], grad_kp_pred [N,K,2], grad_kp_verts [Nv,K,3] (each may be NULL; d|x| at 0 is
+ *   0) -> grad_A [K,V], grad_verts [Nv,V,3], grad_cams [N,7] (each may be NULL: not computed).  ws: at least
+ *   acfm_kp_head_workspace_bytes(K, Nv) bytes, any contents (fewer: ACFM_E_WORKSPACE).  Two launches, one without grad_A.
+ * acfm_camera_loss_forward: cam_pred [N,7] against cam_ref [N,7], or (cam_ref NULL) against row g*(n) N + n of
+ *   cams [G N,7] with g*(n) = the first maximum over g of probs [G,N], written to best [N] (int64) ->
+ *   loss [1] = mean_n max(1 - |Re(q_pred (x) conj(q_ref))| - margin, 0) + mean_{3N} max((pred - ref)[:3]^2 - margin, 0)
+ *   (loss_utils.camera_loss).  One workgroup.
+ * acfm_camera_loss_backward: grad_loss [1] -> grad_cam_pred [N,7] (the reference camera gets none); at a hinge tie the
+ *   slope is 1/2 (torch.max(a, zeros)), d|x| at 0 is 0.  best: what the forward wrote (cam_ref NULL). */
+int acfm_kp_weights_forward(const float* logits, int K, int V, float* A, float* entropy, float* stats, void* stream);
+int acfm_kp_weights_backward(const float* logits, const float* A, const float* stats, const float* grad_A,
+                             const float* grad_entropy, int K, int V, float* grad_logits, void* stream);
+int acfm_kp_head_forward(const float* A, const float* verts, const float* cams, const float* kp_gt, int K, int V, int N,
+                         int Nv, int Ng, float img_size, float* kp_verts, float* kp_pred, float* loss, float* kp_err,
+                         void* stream);
+size_t acfm_kp_head_workspace_bytes(int K, int Nv);
+int acfm_kp_head_backward(const float* A, const float* verts, const float* cams, const float* kp_gt,
+                          const float* kp_verts, const float* kp_pred, const float* grad_loss, const float* grad_kp_pred,
+                          const float* grad_kp_verts, int K, int V, int N, int Nv, int Ng, float* grad_A,
+                          float* grad_verts, float* grad_cams, void* ws, size_t ws_bytes, void* stream);
+int acfm_camera_loss_forward(const float* cam_pred, const float* cam_ref, const float* cams, const float* probs, int N,
+                             int G, float margin, float* loss, int64_t* best, void* stream);
+int acfm_camera_loss_backward(const float* cam_pred, const float* cam_ref, const float* cams, const int64_t* best,
+                              const float* grad_loss, int N, float margin, float* grad_cam_pred, void* stream);
+
 /* ---- on-device input preparation ----------------------------------------
  * replaces the per-batch CPU work of ShapeTrainer.set_input (multiframe/main.py:365-377) and
  * its device->host->device round trip of the masks.

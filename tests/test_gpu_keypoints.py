@@ -1,0 +1,580 @@
+"""GPU: ops.kp_weights / ops.kp_head / ops.camera_loss (csrc/acfm_keypoints.hip), keypoints.KeypointHead and the opt-in
+wiring of MultiframeStep against the reference's lines (mesh_net.py:504-519's softmax, main.py:690-696, 753-762,
+geom_utils.py:48-59, loss_utils.py:256-289, 330-356, evaluate.py:156-158) evaluated by torch on the CPU in float64 on
+the same float32-rounded inputs, gradients by autograd.
+
+Bars (the convention of test_gpu_uv_atlas.py).  Every case also evaluates the same lines in torch-CPU float32 and
+measures THAT error against float64; the GPU's error may be at most twice it (two float32 evaluations of one formula in
+different summation orders), with floors of 1e-6 absolute forward (values of magnitude <= ~1; the pixel error is
+compared in NDC units, i.e. divided by img_size / 2) and 1e-6 of max|grad| per gradient tensor -- and, as a condition, no
+forward bar above 1e-5 and no gradient bar above 1e-4 of max|grad|.  Ground-truth keypoints are a prediction plus an
+offset of magnitude in [0.02, 0.3]; a keypoint whose float64 residual comes within 2e-3 of the L1 kink under any camera
+that shares it is made invisible, and the test asserts |dx|, |dy| > 1e-3 on every visible one.  Every figure is printed
+before it is asserted."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+IMG = 64
+SHAPES = [(1, 5, 1, 1, 1), (3, 64, 2, 1, 2), (15, 70, 2, 3, 2), (17, 129, 3, 2, 6), (33, 100, 1, 4, 1),
+          (64, 65, 2, 1, 2), (15, 642, 4, 3, 4)]          # (K, V, Nv, G, Ng); N = Nv * G
+
+
+def _d():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _cams(n, g):
+    c = torch.randn(n, 7, generator=g)
+    c[:, 0] = 0.7 + 0.2 * torch.rand(n, generator=g)
+    c[:, 1:3] *= 0.05
+    c[:, 3:] = torch.nn.functional.normalize(c[:, 3:], dim=1)
+    return c
+
+
+def _ham(a, b):
+    a0, a1, a2, a3 = a.unbind(-1)
+    b0, b1, b2, b3 = b.unbind(-1)
+    return torch.stack([a0 * b0 - a1 * b1 - a2 * b2 - a3 * b3, a0 * b1 + a1 * b0 + a2 * b3 - a3 * b2,
+                        a0 * b2 - a1 * b3 + a2 * b0 + a3 * b1, a0 * b3 + a1 * b2 - a2 * b1 + a3 * b0], -1)
+
+
+def _project_lines(X, cam):
+    """geom_utils.orthographic_proj (:48-59) with quat_rotate (:134-152) and hamilton_product (:107-131)."""
+    q = cam[:, None, 3:7].expand(-1, X.shape[1], -1)
+    qc = torch.cat([q[..., :1], -1 * q[..., 1:]], -1)
+    X4 = torch.cat([X[..., :1] * 0, X], -1)
+    rot = _ham(q, _ham(X4, qc))[..., 1:4]
+    return cam[:, 0].reshape(-1, 1, 1) * rot[..., :2] + cam[:, 1:3].reshape(cam.shape[0], 1, -1)
+
+
+def _lines(logits, verts, cams, gt, log_softmax=False):
+    """The reference's lines on tensors of one dtype, with its repeat(G, ...) copies.  -> A, entropy, kp_verts [Nv,K,3],
+    kp_pred, loss, kp_err in NDC units."""
+    N = cams.shape[0]
+    A = torch.softmax(logits, dim=1)
+    if log_softmax:
+        ls = torch.log_softmax(logits, dim=1)
+        ent = torch.mean(-torch.sum(ls.exp() * ls, 1))
+    else:
+        ent = torch.mean(-torch.sum(A * torch.log(A), 1))                       # loss_utils.entropy_loss
+    kp_verts = torch.matmul(A, verts)
+    kp_pred = _project_lines(kp_verts.repeat(N // verts.shape[0], 1, 1), cams)
+    loss = err = None
+    if gt is not None:
+        kps = gt.repeat(N // gt.shape[0], 1, 1)
+        vis = kps[..., 2].gt(0).to(kp_pred.dtype)
+        loss = ((kp_pred - kps[..., :2]).abs().sum(-1) * vis).mean(-1) / (vis.mean(-1) + 1e-4)   # kp_l2_loss, 'none'
+        err = torch.norm((kp_pred + 1) * IMG / 2 - (kps[..., :2] + 1) * IMG / 2, dim=2) / (IMG / 2)
+    return A, ent, kp_verts, kp_pred, loss, err
+
+
+def _gpu(logits, verts, cams, gt):
+    from acfm_video_3d_reconstruction_amd import ops
+    A, ent = ops.kp_weights(logits)
+    kp_verts, kp_pred, loss, err = ops.kp_head(A, verts, cams, gt, IMG if gt is not None else None, gt is not None)
+    return A, ent, kp_verts, kp_pred, loss, None if err is None else err / (IMG / 2)
+
+
+FWD = ("A", "entropy", "kp_verts", "kp_pred", "loss", "kp_err")
+PROBES = ("through A", "through the entropy", "through both", "grad_loss", "all three gradients + entropy")
+
+
+def make_gt(logits, verts, cams, Ng, g, all_visible_row=True):
+    """Ground truth [Ng,K,3]: the float64 prediction of the first camera of each row plus an offset of magnitude in
+    [0.02, 0.3] with a random sign; visibility column drawn from {2.5, 1, 0, -1}; row 0 has every keypoint visible (when
+    there is more than one row); keypoints near the kink under any camera of the row are made invisible (-1)."""
+    K = logits.shape[0]
+    N = cams.shape[0]
+    pred = _lines(logits.double(), verts.double(), cams.double(), None)[3]               # [N,K,2]
+    off = (0.02 + 0.28 * torch.rand(Ng, K, 2, generator=g)) * (torch.randint(0, 2, (Ng, K, 2), generator=g) * 2 - 1)
+    xy = (pred[:Ng] + off.double()).float()
+    vis = torch.tensor([2.5, 1., 1., 0., -1.])[torch.randint(0, 5, (Ng, K), generator=g)]
+    if all_visible_row and Ng > 1:
+        vis[0] = 1.
+    res = (pred - xy.double().repeat(N // Ng, 1, 1)).abs().reshape(N // Ng, Ng, K, 2)
+    near = (res < 2e-3).any(-1).any(0)
+    vis[near] = -1.
+    if not bool((vis > 0).any()):
+        vis[0, 0] = 1.
+        assert not bool(near[0, 0])
+    return torch.cat([xy, vis[..., None]], 2)
+
+
+def assert_away_from_kink(logits, verts, cams, gt):
+    pred = _lines(logits.double(), verts.double(), cams.double(), None)[3]
+    kps = gt.double().repeat(cams.shape[0] // gt.shape[0], 1, 1)
+    res = (pred - kps[..., :2]).abs()[kps[..., 2] > 0]
+    print("  visible keypoints %d of %d, smallest |residual| %.3e" % (res.shape[0], kps.shape[0] * kps.shape[1],
+                                                                     float(res.min())))
+    assert res.numel() > 0 and float(res.min()) > 1e-3
+
+
+class Case:
+    """One shape: inputs, the float64 reference, the torch-CPU float32 evaluation, the bars, the GPU's run."""
+
+    def __init__(self, K, V, Nv, G, Ng, seed=0):
+        g = _gen(100 + seed)
+        self.tag = "K=%d V=%d Nv=%d G=%d Ng=%d" % (K, V, Nv, G, Ng)
+        N = Nv * G
+        self.logits = 3 * torch.randn(K, V, generator=g)
+        for k in range(K):                                   # safe_ln(1e-10) entries, as mesh_net.py:504-519 leaves them
+            self.logits[k, torch.randperm(V, generator=g)[:min(50, V // 3)]] = -23.
+        self.verts = 0.5 * torch.randn(Nv, V, 3, generator=g)
+        self.cams = _cams(N, g)
+        self.gt = make_gt(self.logits, self.verts, self.cams, Ng, g)
+        self.w = dict(gA=torch.randn(K, V, generator=g), ge=torch.randn((), generator=g),
+                      gl=torch.randn(N, generator=g), gp=torch.randn(N, K, 2, generator=g),
+                      gv=torch.randn(Nv, K, 3, generator=g))
+        print(self.tag)
+        assert_away_from_kink(self.logits, self.verts, self.cams, self.gt)
+        ev = {dt: self.evaluate(_lines, torch.device("cpu"), dt) for dt in (torch.float64, torch.float32)}
+        self.ref = ev[torch.float64]
+        self.bars = {}
+        for name, want in self.ref.items():
+            cpu = float((ev[torch.float32][name].double() - want).abs().max())
+            if name in FWD:
+                scale, bar = 1.0, max(2 * cpu, 1e-6)
+                assert bar <= 1e-5, (name, bar)
+            else:
+                scale = float(want.abs().max())
+                bar = max(2 * cpu, 1e-6 * scale)
+                assert bar <= 1e-4 * scale, (name, bar, scale)
+            self.bars[name] = (bar, scale, cpu)
+        self.got = self.evaluate(_gpu, _d(), torch.float32)
+
+    def evaluate(self, fn, dev, dt):
+        x, v, c = [t.to(device=dev, dtype=dt).clone().requires_grad_(True) for t in (self.logits, self.verts, self.cams)]
+        w = {k: t.to(device=dev, dtype=dt) for k, t in self.w.items()}
+        A, ent, kpv, kpp, loss, err = fn(x, v, c, self.gt.to(device=dev, dtype=dt))
+        out = dict(zip(FWD, [t.detach() for t in (A, ent, kpv, kpp, loss, err)]))
+        objectives = {PROBES[0]: ((A * w["gA"]).sum(), (x,)), PROBES[1]: (ent * w["ge"], (x,)),
+                      PROBES[2]: ((A * w["gA"]).sum() + ent * w["ge"], (x,)),
+                      PROBES[3]: ((loss * w["gl"]).sum(), (x, v, c)),
+                      PROBES[4]: ((loss * w["gl"]).sum() + (kpp * w["gp"]).sum() + (kpv * w["gv"]).sum()
+                                  + ent * w["ge"], (x, v, c))}
+        for probe, (obj, leaves) in objectives.items():
+            grads = torch.autograd.grad(obj, leaves, retain_graph=True)
+            for name, gr in zip(("logits", "verts", "cams"), grads):
+                out["d %s, %s" % (name, probe)] = gr.detach()
+        return {k: t.cpu() for k, t in out.items()}
+
+    def check(self):
+        bad = []
+        for name, want in self.ref.items():
+            got = self.got[name]
+            assert got.shape == want.shape and got.dtype == torch.float32, name
+            assert not torch.isnan(got).any(), name
+            bar, scale, cpu = self.bars[name]
+            e = float((got.double() - want).abs().max())
+            print("  %-52s GPU vs float64 %.3e, torch-CPU float32 %.3e, bar %.3e (scale %.3e)" % (name, e, cpu, bar, scale))
+            if e > bar:
+                bad.append((name, e, bar))
+        assert not bad, bad
+        return self
+
+
+@pytest.fixture(scope="module")
+def cases():
+    return {}
+
+
+def _case(cases, shape):
+    if shape not in cases:
+        cases[shape] = Case(*shape, seed=SHAPES.index(shape))
+    return cases[shape]
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=["K%d-V%d-Nv%d-G%d-Ng%d" % s for s in SHAPES])
+def test_against_the_reference_lines(cases, shape):
+    _case(cases, shape).check()
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=["K%d-V%d-Nv%d-G%d-Ng%d" % s for s in SHAPES])
+def test_projection_bits_and_reproducible(cases, shape):
+    """kp_pred is ops.project_xy of the kernel's own kp_verts under the cameras' rows, bit for bit; a second run of every
+    operator repeats every output and gradient bit for bit."""
+    from acfm_video_3d_reconstruction_amd import ops
+    c = _case(cases, shape)
+    d = _d()
+    N, Nv = c.cams.shape[0], c.verts.shape[0]
+    want = ops.project_xy(c.got["kp_verts"].to(d).repeat(N // Nv, 1, 1), c.cams.to(d), 0.)
+    assert torch.equal(want.cpu(), c.got["kp_pred"])
+    again = c.evaluate(_gpu, d, torch.float32)
+    for name, t in c.got.items():
+        assert torch.equal(t, again[name]), name
+
+
+def test_inputs_without_grad_get_none(cases):
+    from acfm_video_3d_reconstruction_amd import ops
+    c = _case(cases, SHAPES[2])
+    d = _d()
+    for needs in ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1)):
+        x, v, cm = [t.to(d).clone().requires_grad_(bool(n)) for t, n in zip((c.logits, c.verts, c.cams), needs)]
+        A, ent = ops.kp_weights(x)
+        assert A.requires_grad == bool(needs[0])
+        kpv, kpp, loss, err = ops.kp_head(A, v, cm, c.gt.to(d), IMG, True)
+        assert not err.requires_grad
+        ((loss * c.w["gl"].to(d)).sum() + kpv.sum()).backward()
+        for t, n, name in zip((x, v, cm), needs, ("logits", "verts", "cams")):
+            assert (t.grad is not None) == bool(n), (needs, name)
+            if n:
+                key = "d %s, %s" % (name, PROBES[3])
+                assert t.grad.shape == c.ref[key].shape and bool(torch.isfinite(t.grad).all())
+    # nothing requires grad: no graph at all; no ground truth: no loss, no error
+    out = ops.kp_head(ops.kp_weights(c.logits.to(d))[0], c.verts.to(d), c.cams.to(d))
+    assert out[2] is None and out[3] is None and not out[0].requires_grad and not out[1].requires_grad
+    assert torch.equal(out[1].cpu(), c.got["kp_pred"])
+
+
+def test_visibility_edge_cases(cases):
+    """A frame with no visible keypoint: loss 0, zero gradients, nothing NaN; visibility negative or exactly 0 counts as
+    invisible (their coordinates are never felt); every keypoint visible."""
+    from acfm_video_3d_reconstruction_amd import ops
+    c = _case(cases, SHAPES[2])                       # K=15, V=70, Nv=2, G=3, Ng=2: N=6, frame = n % 2
+    d = _d()
+    gt = c.gt.clone()
+    gt[1, :, 2] = torch.tensor([0., -1., -0.]).repeat(5)                 # frame 1: nothing visible
+    assert bool((gt[0, :, 2] > 0).all())                                  # frame 0: everything visible
+    x, v, cm = [t.to(d).clone().requires_grad_(True) for t in (c.logits, c.verts, c.cams)]
+    A, _ = ops.kp_weights(x)
+    _, _, loss, err = ops.kp_head(A, v, cm, gt.to(d), IMG, True)
+    assert torch.equal(loss[1::2], torch.zeros(3, device=d)) and bool((loss[0::2] > 0).all())
+    gl = torch.zeros(6, device=d)
+    gl[1::2] = torch.tensor([1., -2., 3.], device=d)                     # only the frames that see nothing
+    gx, gv, gc = torch.autograd.grad((loss * gl).sum(), (x, v, cm), retain_graph=True)
+    for t in (gx, gv, gc):
+        assert torch.equal(t, torch.zeros_like(t))
+    gx, gv, gc = torch.autograd.grad(loss.sum(), (x, v, cm))
+    assert torch.equal(gc[1::2], torch.zeros(3, 7, device=d)) and float(gc[0::2].abs().min()) > 0
+    assert torch.equal(gv[1], torch.zeros_like(gv[1])) and float(gv[0].abs().max()) > 0
+    assert all(bool(torch.isfinite(t).all()) for t in (loss, err, gx, gv, gc))
+    # the coordinates of invisible keypoints do not matter, whatever the sign of the flag
+    gt2 = c.gt.clone()
+    inv = ~(gt2[..., 2] > 0)
+    assert int(inv.sum()) > 0 and bool((gt2[..., 2][inv] == 0).any()) and bool((gt2[..., 2][inv] < 0).any())
+    gt2[..., :2][inv] = 100.
+    loss2 = ops.kp_head(A.detach(), v.detach(), cm.detach(), gt2.to(d))[2]
+    assert torch.equal(loss2.cpu(), c.got["loss"])
+
+
+def test_zero_residual_has_zero_gradient():
+    """The ground truth of one visible keypoint set to the kernel's own prediction: its residual is exactly 0 and so is
+    everything that flows back through it (d|x| at 0 is 0, torch's rule); the other keypoints are unaffected."""
+    from acfm_video_3d_reconstruction_amd import ops
+    d = _d()
+    g = _gen(7)
+    K, V, k0 = 6, 40, 2
+    A = torch.softmax(torch.randn(K, V, generator=g), 1).to(d).requires_grad_(True)
+    verts = (0.5 * torch.randn(1, V, 3, generator=g)).to(d)
+    cams = _cams(1, g).to(d).requires_grad_(True)
+    pred = ops.kp_head(A, verts, cams)[1].detach()
+    gt = torch.cat([pred + 0.1, torch.ones(1, K, 1, device=d)], 2)
+    gt[0, k0, :2] = pred[0, k0]
+    loss = ops.kp_head(A, verts, cams, gt)[2]
+    gA, gc = torch.autograd.grad(loss.sum(), (A, cams))
+    assert torch.equal(gA[k0], torch.zeros(V, device=d))
+    others = [k for k in range(K) if k != k0]
+    assert float(gA[others].abs().max(1)[0].min()) > 0 and float(gc.abs().max()) > 0
+    only = torch.cat([pred, torch.zeros(1, K, 1, device=d)], 2)           # ... and alone: every gradient is exactly 0
+    only[0, k0, 2] = 1.
+    loss = ops.kp_head(A, verts, cams, only)[2]
+    gA, gc = torch.autograd.grad(loss.sum(), (A, cams))
+    assert float(loss) == 0.0 and torch.equal(gA, torch.zeros_like(gA)) and torch.equal(gc, torch.zeros_like(gc))
+
+
+def test_entropy_where_the_softmax_underflows():
+    """A row [0, -200, -200, ...]: A underflows to exactly 0, the reference's A * log(A) is NaN; the kernel's entropy and
+    its gradient are finite and equal the log-softmax form in float64."""
+    from acfm_video_3d_reconstruction_amd import ops
+    from acfm_video_3d_reconstruction_amd.nnutils import loss_utils
+    d = _d()
+    logits = torch.randn(3, 70, generator=_gen(8))
+    logits[1] = -200.
+    logits[1, 0] = 0.
+    assert torch.isnan(loss_utils.entropy_loss(torch.softmax(logits, 1)))
+    ev = {}
+    for dt in (torch.float64, torch.float32):
+        xr = logits.to(dt).clone().requires_grad_(True)
+        ls = torch.log_softmax(xr, 1)
+        e = torch.mean(-torch.sum(ls.exp() * ls, 1))
+        ev[dt] = (e.detach(), torch.autograd.grad(e, xr)[0])
+    want, gwant = ev[torch.float64]
+    bar_f = max(2 * abs(float(ev[torch.float32][0]) - float(want)), 1e-6)
+    bar_g = max(2 * float((ev[torch.float32][1].double() - gwant).abs().max()), 1e-6 * float(gwant.abs().max()))
+    x = logits.to(d).requires_grad_(True)
+    A, ent = ops.kp_weights(x)
+    gx, = torch.autograd.grad(ent, x)
+    ef, eg, scale = abs(float(ent) - float(want)), float((gx.cpu().double() - gwant).abs().max()), float(gwant.abs().max())
+    print("underflow row: entropy %.6f vs %.6f (%.3e, bar %.3e), gradient %.3e of max %.3e (bar %.3e)"
+          % (float(ent), float(want), ef, bar_f, eg, scale, bar_g))
+    assert bool((A[1, 1:] == 0).all()) and float(A[1, 0]) == 1.0
+    assert bool(torch.isfinite(ent)) and bool(torch.isfinite(gx).all())
+    assert bar_f <= 1e-5 and bar_g <= 1e-4 * scale and ef <= bar_f and eg <= bar_g
+    assert torch.equal(gx[1], torch.zeros(70, device=d))
+
+
+# ------------------------------------------------------------------------------------------------ camera loss
+def _camera_lines(pred, ref, margin):
+    """loss_utils.py:256-289 (hinge_loss without its .cuda(), quat_loss_geodesic's real part, camera_loss)."""
+    q1, q2 = pred[:, -4:], ref[:, -4:]
+    q2c = torch.cat([q2[:, :1], -1 * q2[:, 1:]], 1)
+    real = _ham(q1, q2c)[:, 0]
+    rot = torch.max((1 - real.abs())[:, None] - margin, torch.zeros(1, dtype=pred.dtype))
+    st = torch.max(((pred[:, :3] - ref[:, :3]) ** 2).view(-1) - margin, torch.zeros(1, dtype=pred.dtype))
+    return rot.mean() + st.mean(), real
+
+
+def _camera_inputs(N, G, seed):
+    g = _gen(200 + seed)
+    cams = _cams(G * N, g)
+    probs = torch.softmax(2 * torch.randn(G, N, generator=g), 0)
+    if G > 1:                                                 # best and second best at least 1e-3 apart
+        top = probs.topk(2, dim=0)[0]
+        probs[probs.argmax(0), torch.arange(N)] += (1e-2 * (top[0] - top[1] < 2e-3)).float()
+        top = probs.topk(2, dim=0)[0]
+        assert float((top[0] - top[1]).min()) >= 1e-3
+    best = probs.argmax(0)
+    ref = cams.reshape(G, N, 7)[best, torch.arange(N)]
+    pred = ref + 0.3 * torch.randn(N, 7, generator=g)
+    pred[:, 3:] = torch.nn.functional.normalize(pred[:, 3:], dim=1)
+    pred[0, 3:] = -pred[0, 3:]                                # a pair with a negative real part
+    return pred, cams, probs, best, ref
+
+
+@pytest.mark.parametrize("margin", [0., 0.05])
+@pytest.mark.parametrize("G", [1, 3])
+@pytest.mark.parametrize("N", [1, 5, 64])
+def test_camera_loss(N, G, margin):
+    from oracle import oracle as O
+    from acfm_video_3d_reconstruction_amd import ops
+    d = _d()
+    pred, cams, probs, best, ref = _camera_inputs(N, G, 10 * N + G)
+    ev = {}
+    for dt in (torch.float64, torch.float32):
+        p = pred.to(dt).clone().requires_grad_(True)
+        loss, real = _camera_lines(p, ref.to(dt), margin)
+        ev[dt] = (loss.detach(), torch.autograd.grad(loss, p)[0], real.detach())
+    l64, g64, real = ev[torch.float64]
+    assert float(real[0]) < 0 and abs(float(O.camera_loss(pred.double(), ref.double(), margin)) - float(l64)) < 1e-12
+    # (at margin 0 the squared differences sit on their hinge only where the difference, and with it the gradient, is 0)
+    hinge = (1 - real.abs()) - margin
+    if margin > 0:
+        hinge = torch.cat([hinge, ((pred[:, :3] - ref[:, :3]).double() ** 2).reshape(-1) - margin])
+    print("N=%d G=%d margin=%g: smallest |hinge argument| %.3e, %d of %d active" % (N, G, margin, float(hinge.abs().min()),
+                                                                              int((hinge > 0).sum()), hinge.numel()))
+    assert float(hinge.abs().min()) > 1e-6                                 # away from the hinge's kink
+    scale = float(g64.abs().max())
+    cpu_f, cpu_g = abs(float(ev[torch.float32][0]) - float(l64)), float((ev[torch.float32][1].double() - g64).abs().max())
+    bar_f, bar_g = max(2 * cpu_f, 1e-6), max(2 * cpu_g, 1e-6 * scale)
+    assert bar_f <= 1e-5 and bar_g <= 1e-4 * scale
+    runs = []
+    for mode in ("cam_ref", "cams + probs"):
+        for _ in range(2):
+            p = pred.to(d).requires_grad_(True)
+            if mode == "cam_ref":
+                loss, b = ops.camera_loss(p, ref.to(d), margin)
+                assert b is None
+            else:
+                loss, b = ops.camera_loss(p, margin=margin, cams=cams.to(d), probs=probs.to(d))
+                assert b.dtype == torch.int64 and torch.equal(b.cpu(), best)
+            gp, = torch.autograd.grad(loss, p)
+            runs.append((loss.detach().cpu(), gp.cpu()))
+        ef, eg = abs(float(runs[-1][0]) - float(l64)), float((runs[-1][1].double() - g64).abs().max())
+        print("  %-12s GPU vs float64: loss %.3e (torch-CPU float32 %.3e, bar %.3e), gradient %.3e (%.3e, bar %.3e)"
+              % (mode, ef, cpu_f, bar_f, eg, cpu_g, bar_g))
+        assert loss.dim() == 0 and ef <= bar_f and eg <= bar_g
+    for a, b in zip(runs[1:], runs[:-1]):                                  # both modes, both runs: the same bits
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+def test_camera_loss_ties():
+    """An exact tie of the probabilities picks the smaller g (torch.argmax's answer); cam_pred == cam_ref sits on the
+    hinge: finite loss and gradients (torch halves the gradient there; values not compared)."""
+    from acfm_video_3d_reconstruction_amd import ops
+    d = _d()
+    g = _gen(9)
+    N, G = 5, 3
+    cams = _cams(G * N, g)
+    probs = torch.softmax(torch.randn(G, N, generator=g), 0)
+    probs[:, 0] = torch.tensor([0.2, 0.4, 0.4])
+    probs[:, 3] = torch.tensor([0.375, 0.25, 0.375])
+    best = probs.argmax(0)
+    assert best[0] == 1 and best[3] == 0
+    pred = _cams(N, g).to(d).requires_grad_(True)
+    loss, b = ops.camera_loss(pred, cams=cams.to(d), probs=probs.to(d))
+    assert torch.equal(b.cpu(), best)
+    ref = cams.reshape(G, N, 7)[best, torch.arange(N)]
+    want, _ = _camera_lines(pred.detach().cpu().double(), ref.double(), 0.)
+    assert abs(float(loss) - float(want)) <= 1e-5
+    same = ref.to(d).clone().requires_grad_(True)
+    loss, _ = ops.camera_loss(same, ref.to(d), 0.)
+    gs, = torch.autograd.grad(loss, same)
+    assert bool(torch.isfinite(loss)) and bool(torch.isfinite(gs).all())
+    assert torch.equal(gs[:, :3], torch.zeros(N, 3, device=d))             # 2 (p - r) = 0 whatever the hinge's slope
+
+
+# ------------------------------------------------------------------------------------------------ capture
+def test_graph_capture():
+    """KeypointHead + ops.camera_loss, forward and backward, captured after one eager call; replayed twice with the
+    inputs changed in place, the outputs equal an eager run on the new inputs bit for bit."""
+    from acfm_video_3d_reconstruction_amd import ops
+    from acfm_video_3d_reconstruction_amd.keypoints import KeypointHead
+    d = _d()
+    K, V, Nv, G = 15, 70, 2, 3
+    N = Nv * G
+
+    def draw(seed):
+        g = _gen(300 + seed)
+        logits = 3 * torch.randn(K, V, generator=g)
+        verts, cams = 0.5 * torch.randn(Nv, V, 3, generator=g), _cams(N, g)
+        return dict(logits=logits, verts=verts, cams=cams, gt=make_gt(logits, verts, cams, Nv, g),
+                    pc=_cams(Nv, g), probs=torch.softmax(torch.randn(G, Nv, generator=g), 0), gl=torch.randn(N, generator=g))
+
+    cur = {k: t.to(d) for k, t in draw(0).items()}
+    head = KeypointHead(torch.nn.Parameter(cur.pop("logits"))).to(d)
+    for k in ("verts", "cams", "pc"):
+        cur[k].requires_grad_(True)
+
+    def step():
+        out = head(cur["verts"], cur["cams"], cur["gt"], img_size=IMG)
+        cl, best = ops.camera_loss(cur["pc"], cams=cur["cams"], probs=cur["probs"])
+        total = (out.loss * cur["gl"]).sum() + head.entropy() + cl
+        grads = torch.autograd.grad(total, (head.vert2kp, cur["verts"], cur["cams"], cur["pc"]))
+        return (out.kp_verts.detach(), out.kp_pred.detach(), out.loss.detach(), out.kp_err, cl.detach(), best,
+                total.detach()) + grads
+
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        step()
+    torch.cuda.current_stream().wait_stream(s)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        outs = step()
+    for seed in (1, 2):
+        new = draw(seed)
+        with torch.no_grad():
+            head.vert2kp.copy_(new.pop("logits").to(d))
+            for k, t in new.items():
+                cur[k].copy_(t.to(d))
+        graph.replay()
+        torch.cuda.synchronize()
+        got = [t.clone() for t in outs]
+        ref = step()
+        assert float(got[-1].abs().max()) > 0 and float(got[7].abs().max()) > 0
+        for i, (a, b) in enumerate(zip(got, ref)):
+            assert torch.equal(a, b), (seed, i)
+
+
+# ------------------------------------------------------------------------------------------------ step wiring
+def test_multiframe_step_wiring(meshes):
+    """MultiframeStep(supervision_kernels=True) against the default on the tiny batch of test_gpu_losses.py's step test,
+    kp_loss_wt > 0, vert2kp a Parameter, predicted_camera given.  The flag-off run in place of the float32 host
+    evaluation; bars: the project's parity levels directly, 1e-5 forward (of max(1, |value|)) and 1e-4 of max|grad|.
+    The rest of the step's backward accumulates with float atomics, so two runs of ONE configuration differ in their
+    gradients' last bits: that difference is printed beside each figure.  The flag-off step gives the same forward bits
+    as a step built without the argument, wherever two steps built without it give the same bits."""
+    from acfm_video_3d_reconstruction_amd import image_utils as IU
+    from acfm_video_3d_reconstruction_amd.multiframe_step import MultiframeStep
+    from acfm_video_3d_reconstruction_amd.synthetic import fps_lbs_logits, make_cams
+    d = _d()
+    rng = np.random.default_rng(0)
+    v, f = meshes["bird_v"], meshes["bird_f"]
+    B, T, G, H, Kh, K = 2, 2, 3, 64, 15, 15
+    N = B * T
+    logits = 3 * torch.randn(K, v.shape[0], generator=_gen(11))
+
+    def build(**kw):
+        torch.manual_seed(0)
+        return MultiframeStep(torch.tensor(v, device=d), torch.tensor(f, device=d),
+                              torch.tensor(fps_lbs_logits(v, Kh), device=d), num_training_frames=10, img_size=H,
+                              vert2kp=torch.nn.Parameter(logits.clone()), num_guesses=G, num_lbs=Kh, scale_lr_decay=1.0,
+                              kp_loss_wt=1.0, **kw).to(d)
+
+    steps = dict(default=build(), control=build(), off=build(supervision_kernels=False),
+                 on=build(supervision_kernels=True))
+    assert sorted(steps["on"].state_dict()) == sorted(steps["default"].state_dict())
+    s0 = steps["default"]
+    gt_cams = torch.tensor(make_cams(N, rng, extent=float(np.abs(v).max())), device=d)
+    with torch.no_grad():
+        gt_mask, _ = s0.renderer(s0.solver.mean_v[None].repeat(N, 1, 1), s0.faces1[None].expand(N, -1, -1), gt_cams)
+        gt_mask = (gt_mask > 0.5).float()
+    g = _gen(12)
+    batch = dict(masks=gt_mask, edts_barrier=IU.compute_dt(gt_mask, norm=False)[:, None].contiguous(),
+                 boundaries=IU.compute_boundaries(gt_mask), frames_idx=torch.tensor([[0, 1], [4, 5]], device=d),
+                 mirror_flag=torch.tensor([0, 0, 1, 1], device=d), transforms=torch.tensor([[1., 0, 0, 0]] * N, device=d),
+                 optical_flows=torch.randn(B, T, H, H, 2, generator=g).to(d), kps=torch.zeros(N, K, 3, device=d))
+    delta = (0.01 * torch.randn(N, Kh, 3, generator=g)).to(d)
+    pc0 = _cams(N, g).to(d)
+    # ground truth from the default step's own prediction (hypothesis 0) + offsets, away from the kink under every hypothesis
+    with torch.no_grad():
+        pred = s0(batch, delta, predicted_camera=pc0)[1]["kp_pred"].cpu().double()
+    off = (0.02 + 0.28 * torch.rand(N, K, 2, generator=g)) * (torch.randint(0, 2, (N, K, 2), generator=g) * 2 - 1)
+    xy = (pred[:N] + off.double()).float()
+    vis = torch.tensor([1., 1., 1., 0., -1.])[torch.randint(0, 5, (N, K), generator=g)]
+    near = ((pred - xy.double().repeat(G, 1, 1)).abs().reshape(G, N, K, 2) < 2e-3).any(-1).any(0)
+    vis[near] = -1.
+    res = (pred - xy.double().repeat(G, 1, 1)).abs()[vis.repeat(G, 1) > 0]
+    print("step: %d of %d keypoint slots visible, smallest |residual| %.3e" % (res.shape[0], G * N * K, float(res.min())))
+    assert float(res.min()) > 1e-3 and int((vis > 0).sum()) > N * K // 3
+    batch["kps"] = torch.cat([xy, vis[..., None]], 2).to(d)
+
+    def run(step):
+        step.zero_grad(set_to_none=True)
+        pc = pc0.clone().requires_grad_(True)
+        loss, terms = step(batch, delta, predicted_camera=pc)
+        loss.backward()
+        grads = {"vert2kp": step.vert2kp.grad, "lbs": step.lbs.grad, "mean_v": step.mean_v.grad, "predicted_camera": pc.grad}
+        grads.update({"camera table %d" % i: e.weight.grad for i, e in enumerate(step.cameras)})
+        assert all(t is not None for t in grads.values())
+        return loss.detach(), terms, {k: t.detach().clone() for k, t in grads.items()}
+
+    with torch.no_grad():                                      # every instance has the same history of calls
+        for name in ("control", "off", "on"):
+            steps[name](batch, delta, predicted_camera=pc0)
+    l_def, t_def, g_def = run(steps["default"])
+    l_again, t_again, _ = run(steps["control"])
+    l_off, t_off, g_off = run(steps["off"])
+    l_on, t_on, g_on = run(steps["on"])
+    assert set(t_def) == set(t_off) and {"kp_loss", "kp_pred", "cam_loss"} <= set(t_off)
+    # flag off against no flag: the same bits wherever two steps built without the flag (default, control) give the
+    # same bits (some of the step's older kernels sum with float atomics), the forward parity level elsewhere
+    t_def["total"], t_again["total"], t_off["total"] = l_def, l_again, l_off
+    loose = []
+    for k in sorted(t_def):
+        if torch.equal(t_def[k], t_again[k]):
+            assert torch.equal(t_def[k], t_off[k]), k
+        else:
+            loose.append(k)
+            a, b = t_def[k].float(), t_off[k].float()
+            assert float((a - b).abs().max()) <= 1e-5 * max(1.0, float(a.abs().max())), k
+    print("step: terms on which two steps built without the flag differ in their last bits: %s" % (loose or "none"))
+    assert "kp_pred" not in loose or "pred_v" in loose           # the keypoint lines themselves are reproducible
+    for t in (t_def, t_again, t_off):
+        del t["total"]
+    assert set(t_on) == set(t_off) and tuple(t_on["kp_loss"].shape) == (G, N) and not t_on["kp_loss"].requires_grad
+    bad = []
+    for name, a, b in (("total", l_on, l_off), ("kp_loss", t_on["kp_loss"], t_off["kp_loss"]),
+                       ("cam_loss", t_on["cam_loss"], t_off["cam_loss"]), ("kp_pred", t_on["kp_pred"], t_off["kp_pred"])):
+        e, bar = float((a - b).abs().max()), 1e-5 * max(1.0, float(b.abs().max()))
+        print("step %-10s flag on vs off %.3e (bar %.3e, max |value| %.3e)" % (name, e, bar, float(b.abs().max())))
+        if e > bar:
+            bad.append((name, e, bar))
+    assert float(t_off["kp_loss"].abs().min()) > 0 and float(t_off["cam_loss"]) > 0
+    for name in g_off:
+        scale = float(g_off[name].abs().max())
+        e, noise = float((g_on[name] - g_off[name]).abs().max()), float((g_def[name] - g_off[name]).abs().max())
+        print("step d %-18s flag on vs off %.3e = %.3e of max|grad| %.3e (bar 1e-4); two flag-off runs differ by %.3e"
+              % (name, e, e / scale, scale, noise / scale))
+        assert scale > 0
+        if e > 1e-4 * scale:
+            bad.append((name, e, 1e-4 * scale))
+    assert not bad, bad
