@@ -422,10 +422,16 @@ __device__ __forceinline__ void walk_wave(LT& L, const Tile& t, int H, int list_
 }
 
 // Bins the faces of mesh t.n against the wave's 8x8 block and calls walk(count) whenever the LDS
-// list is complete or could overflow.  The faces come from the bitmask of the block's 16x16
+// list is FULL (count == LT::CAP) or complete.  The faces come from the bitmask of the block's 16x16
 // coarse tile (k_setup): lane i expands mask word i into the wave's face-id list (ascending), then
 // 64 ids per round lane i tests face i's box; survivors are compacted with one ballot, face
-// order kept.  No barriers: the workgroup is one wave.
+// order kept.  A round appends only the survivors that fit; when some do not, the id cursor is put
+// back to the first of them and the round after the walk starts there (its box is loaded again: no
+// per-lane state lives through the walk).  Every walk but a block's last therefore runs on a full
+// list: a walk's shell (sub-list passes, depth deal, barriers, pairing, flush) is paid
+// ceil(candidates / CAP) times per block, and the 16-lane groups are balanced over CAP candidates
+// at a time.  Progress: a round either takes 64 ids or fills the list and takes at least one.
+// No barriers: the workgroup is one wave.
 __device__ __forceinline__ int wave_inclusive_scan(int x, int lane) {
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
@@ -462,8 +468,9 @@ __device__ __forceinline__ void bin_and_walk(const RasterWs& ws, const Tile& t, 
   int list_n = 0;
   // one loop with a single walk() site (the walk body is large and holds the per-pixel lists in
   // registers: a second inlined copy costs registers): refill the id list from the next mask
-  // chunk when it runs dry, take up to 64 ids, test + append, walk when the list could overflow
-  // or everything has been appended
+  // chunk when it runs dry, take up to 64 ids, test + append what fits, walk when the list is full
+  // or everything has been appended.  (s_fl is refilled only once i0 >= total, so a cursor that
+  // was put back never reads a refilled list.)
   int w0 = -64, total = 0, i0 = 0, f0 = 0, fe = 0;
   bool direct = false, done = false;
 #pragma unroll 1
@@ -508,8 +515,8 @@ __device__ __forceinline__ void bin_and_walk(const RasterWs& ws, const Tile& t, 
         pass = !(t.t_xmin > b.y || t.t_xmax < b.x || t.t_ymin > b.w || t.t_ymax < b.z);
       }
       const unsigned long long bal = __ballot(pass);
-      if (pass) {
-        const int pos = list_n + __popcll(bal & lt);
+      const int pos = list_n + __popcll(bal & lt);
+      if (pass && pos < LT::CAP) {
         const size_t o = (size_t)t.n * F + f;
         L.box[pos] = b;
         L.a[pos] = ws.rec[o].a;
@@ -519,8 +526,15 @@ __device__ __forceinline__ void bin_and_walk(const RasterWs& ws, const Tile& t, 
         if constexpr (has_edge_const<LT>::value) { L.e0[pos] = ws.rec[o].e0; L.e1[pos] = ws.rec[o].e1; }
       }
       list_n += __popcll(bal);
+      if (list_n > LT::CAP) {
+        // more survivors than room: the list is full, the cursor goes back to the first survivor that did not fit and
+        // the next round tests the ids from there again (a few box loads; nothing of the round lives through the walk)
+        const int back = RT + 1 - (int)__ffsll((long long)__ballot(pass && pos >= LT::CAP));
+        if (direct) f0 -= back; else i0 -= back;
+        list_n = LT::CAP;
+      }
     }
-    if (list_n > LT::CAP - RT || (done && list_n > 0)) {
+    if (list_n == LT::CAP || (done && list_n > 0)) {
       wave_lds_sync();
       walk(list_n);
       wave_lds_sync();
@@ -652,7 +666,11 @@ __device__ __forceinline__ void shift_insert_block(unsigned long long (&key)[K],
 // the IEEE-exact division of point_line_dist) and a flag for an edge with |e|^2 <= kEps -- computed once per face by
 // k_setup with the very operations the walk used to repeat for every (pixel, face) pair: two more 16-byte LDS
 // entries per candidate (32 B), ~33 instruction slots fewer per walk iteration, bit-identical values.
-constexpr int FWD_CAP = 88;   // K-nearest candidate list: 96 B x 88 + sub-lists + id list + cull lists = 10 208 B <= 10 240
+// K-nearest candidate list: 96 B x 88 + sub-lists + id list + cull lists = 10 208 B <= 10 240.  bin_and_walk fills it to
+// the last slot before a walk (a block with more than 88 candidates walks ceil(n / 88) times), so the limits of
+// walk_wave -- byte-sized sub-list entries, two list entries per lane in the depth deal (CAP <= 128) -- are met by
+// every full walk, not only by rare overflows.
+constexpr int FWD_CAP = 88;
 template <int CAP_>
 struct CandListET : CandListT<CAP_> {
   float4 e0[CAP_];   // FaceRec::e0: (|e01|^2, |e02|^2, 1/|e01|^2, 1/|e02|^2)   -- the pair the packed pipe evaluates together
@@ -1284,7 +1302,9 @@ __global__ __launch_bounds__(64 * COVER_WPB) void k_tex_cover(RasterWs ws, int N
 }
 
 // ------------------------------------------------------------------------------- backward
-constexpr int BWD_CAP = 64;   // candidate-list capacity of the backward (LDS per wave: 108 B per slot)
+// candidate-list capacity of the backward (LDS per wave: 108 B per slot).  bin_and_walk walks on a full list, so every
+// walk but a block's last sees all 64 slots: s_acc has one row per slot, the flush loop covers list_n <= 64 in one pass
+constexpr int BWD_CAP = 64;
 using BwdList = CandListT<BWD_CAP>;
 __device__ __forceinline__ void acc_add(float* p, float v) { atomicAdd(p, v); }
 __device__ __forceinline__ void acc_add(long long* p, float v) {
@@ -1340,6 +1360,7 @@ __device__ __forceinline__ void sil_bwd_block(const RasterWs& ws, const Tile& t,
   float coef_p = 0.f;
   unsigned long long kth_p = KEY_NONE;
   bin_and_walk(ws, t, F, H, L, s_fl, 0.f, [&](int list_n) {
+    DIAG_ADD(1, 1); DIAG_ADD(2, list_n);
     walk_wave<false, true>(L, t, H, list_n, blur, nullptr,
                            [&](const Cand& cd, bool in_box, int ord, bool helping, float exf, float eyf) {
       const float coef_e = helping ? coef_p : coef;

@@ -37,5 +37,6 @@ loss = (mk - gt).abs().mean()
 torch.cuda.synchronize(); raw.acfm_debug_counters(c, 1)
 loss.backward(); torch.cuda.synchronize()
 raw.acfm_debug_counters(c, 0)
-print("backward: walk iterations %d, lanes having a face %.1f / 64, in a face's box %.1f / 64, (group, face) pairs %d" % (
-    c[3], c[10] / max(c[3], 1), c[4] / max(c[3], 1), c[12]))
+print("backward: walk calls %d, candidates (sum list_n) %d, walk iterations %d, lanes having a face %.1f / 64, "
+      "in a face's box %.1f / 64, (group, face) pairs %d" % (
+    c[1], c[2], c[3], c[10] / max(c[3], 1), c[4] / max(c[3], 1), c[12]))
