@@ -81,6 +81,9 @@ SIGNATURES = {
     "acfm_interpolate_face_attributes": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _vp, _vp, _vp]),
     "acfm_interpolate_face_attributes_backward": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp, _vp, _vp, _sz, _vp,
                                                        _vp]),
+    "acfm_uv_texels": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "acfm_uv_texels_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+                                     _sz, _vp, _vp]),
     "acfm_tex_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp,
                               _vp, _sz, _i, _f, _i, _vp, _vp]),
     "acfm_vertex_color_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz,

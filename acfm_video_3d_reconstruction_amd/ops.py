@@ -1529,6 +1529,82 @@ def interpolate_face_attributes(pix_to_face, barycentric_coords, face_attributes
     return _Interpolate.apply(barycentric_coords, face_attributes, pix_to_face)
 
 
+UV_PADDING_MODES = ("border", "zeros")
+
+
+class _UvTexels(torch.autograd.Function):
+    """TexturesUV.sample_textures (acfm_uv_texels{,_backward}); gradients to bary, faces_verts_uvs and
+    maps, each formed only when asked for."""
+
+    @staticmethod
+    def forward(ctx, bary, fvuv, maps, p2f, align, pad):
+        p2f, b, fv, m = _i64c(p2f), _f32c(bary), _f32c(fvuv), _f32c(maps)
+        N, H, W, K = p2f.shape
+        P = N * H * W
+        Fp, Hm, Wm = fv.shape[0], m.shape[1], m.shape[2]
+        out = torch.empty(p2f.shape + (3,), dtype=torch.float32, device=p2f.device)
+        tune = _lib.tuning()[1]
+        P_ = _lib.ptr
+        _lib.call("acfm_uv_texels", p2f.device, P_(p2f), P_(b), P_(fv), P_(m), P, K, H * W, Fp, N, Hm, Wm, align, pad,
+                  P_(out), _lib.tuning_ptr(tune))
+        ctx.save_for_backward(p2f, b, fv, m)
+        ctx.cfg = (P, K, H * W, Fp, N, Hm, Wm, align, pad, tune)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need_b, need_fv, need_m = ctx.needs_input_grad[:3]
+        if g is None or not (need_b or need_fv or need_m):
+            return (None,) * 6
+        p2f, b, fv, m = ctx.saved_tensors
+        P, K, HW, Fp, N, Hm, Wm, align, pad, tune = ctx.cfg
+        gb = torch.empty_like(b) if need_b else None
+        gfv = torch.empty_like(fv) if need_fv else None
+        gm = torch.empty_like(m) if need_m else None
+        n_acc = (fv.numel() if need_fv else 0) + (m.numel() if need_m else 0)
+        ws, nb = _det_ws(tune, n_acc, p2f.device) if n_acc else (None, 0)
+        P_ = _lib.ptr
+        _lib.call("acfm_uv_texels_backward", p2f.device, P_(p2f), P_(b), P_(fv), P_(m), P_(_f32c(g)), P, K, HW, Fp, N,
+                  Hm, Wm, align, pad, P_(gm), P_(gb), P_(gfv), P_(ws), nb, _lib.tuning_ptr(tune))
+        return gb, gfv, gm, None, None, None
+
+
+def uv_texels(pix_to_face, bary_coords, faces_verts_uvs, maps, align_corners=True, padding_mode="border"):
+    """PyTorch3D 0.3.0 TexturesUV.sample_textures: pix_to_face [N,H,W,K], bary_coords [N,H,W,K,3],
+    faces_verts_uvs [F_packed,3,2] (= verts_uvs[faces_uvs], mesh after mesh), maps [N,Hm,Wm,3] -> texels [N,H,W,K,3]
+    = grid_sample(maps[n] flipped along its height, 2 uv - 1, bilinear, padding_mode, align_corners) at uv = sum_i
+    bary_i faces_verts_uvs[f, i].  The map is read in place (no K-fold copy); empty slots are not zeroed, they hold
+    the sample at uv = (0, 0).  Differentiable with respect to the three float inputs."""
+    if pix_to_face.dim() != 4:
+        raise ValueError("pix_to_face must be [N,H,W,K], got %s" % (tuple(pix_to_face.shape),))
+    K = int(pix_to_face.shape[-1])
+    if K not in FRAGMENT_K:
+        raise ValueError("faces_per_pixel=%d is not supported (one of %s)" % (K, FRAGMENT_K))
+    if tuple(bary_coords.shape) != tuple(pix_to_face.shape) + (3,):
+        raise ValueError("bary_coords must be %s, got %s" % (tuple(pix_to_face.shape) + (3,),
+                                                             tuple(bary_coords.shape)))
+    if faces_verts_uvs.dim() != 3 or tuple(faces_verts_uvs.shape[1:]) != (3, 2) or faces_verts_uvs.shape[0] < 1:
+        raise ValueError("faces_verts_uvs must be [F_packed,3,2], got %s" % (tuple(faces_verts_uvs.shape),))
+    if maps.dim() != 4 or maps.shape[3] != 3 or maps.shape[0] != pix_to_face.shape[0]:
+        raise ValueError("maps must be [N,Hm,Wm,3] with N = %d, got %s" % (pix_to_face.shape[0], tuple(maps.shape)))
+    if padding_mode not in UV_PADDING_MODES:
+        raise ValueError("padding_mode=%r is not supported (one of %s)" % (padding_mode, UV_PADDING_MODES))
+    lo = 2 if align_corners else 1
+    if min(maps.shape[1], maps.shape[2]) < lo or max(maps.shape[1], maps.shape[2]) > 16384:
+        raise ValueError("maps must have sides in [%d, 16384]%s, got %s"
+                         % (lo, " with align_corners=True" if align_corners else "", tuple(maps.shape)))
+    if pix_to_face.numel() == 0:
+        raise ValueError("pix_to_face is empty: %s" % (tuple(pix_to_face.shape),))
+    for name, t in (("bary_coords", bary_coords), ("faces_verts_uvs", faces_verts_uvs), ("maps", maps)):
+        if t.dtype != torch.float32:
+            raise ValueError("%s must be float32 (half storage is not supported on the shader path), got %s"
+                             % (name, t.dtype))
+    _lib.require_gpu(pix_to_face, bary_coords, faces_verts_uvs, maps)
+    return _UvTexels.apply(bary_coords, faces_verts_uvs, maps, pix_to_face, int(bool(align_corners)),
+                           UV_PADDING_MODES.index(padding_mode))
+
+
 # ------------------------------------------------------------------------------ texture
 # atlas gradient: gather per face over the pixels of its box (acfm_tex_backward_faces, R <= 8) instead
 # of one global float atomic per pixel and channel (acfm_tex_backward); both are kept and tested

@@ -487,6 +487,21 @@ int acfm_interpolate_face_attributes_backward(const int64_t* pix_to_face, const 
                                               const float* grad_out, size_t P, int K, int F_packed, int D,
                                               float* grad_bary, float* grad_face_attrs, void* ws, size_t ws_bytes,
                                               const AcfmRasterTuning* tuning, void* stream);
+/* TexturesUV.sample_textures (App-A.11): texels [P,K,3] = grid_sample(maps[n] flipped along its height, 2 uv - 1,
+ * bilinear) at uv = sum_i bary_i faces_verts_uvs[f,i,:] ((0,0) in empty slots, which are not zeroed), with
+ * faces_verts_uvs [F_packed,3,2], maps [N,Hm,Wm,3] read in place and n = p / pix_per_mesh (P = N pix_per_mesh).
+ * align_corners 0 / 1 (then Hm, Wm >= 2); padding_mode 0 = "border", 1 = "zeros"; Hm, Wm <= 16384. */
+int acfm_uv_texels(const int64_t* pix_to_face, const float* bary, const float* faces_verts_uvs, const float* maps,
+                   size_t P, int K, int pix_per_mesh, int F_packed, int N, int Hm, int Wm, int align_corners,
+                   int padding_mode, float* texels, const AcfmRasterTuning* tuning, void* stream);
+/* Backward of the above (App-A.11), recomputed from the same inputs; each output may be NULL: grad_maps [N,Hm,Wm,3]
+ * and grad_faces_verts_uvs [F_packed,3,2] (scattered: float atomics, or in deterministic mode integer pairs in `ws`,
+ * 16 bytes per element of the requested ones, grad_maps first), grad_bary [P,K,3] (0 in empty slots). */
+int acfm_uv_texels_backward(const int64_t* pix_to_face, const float* bary, const float* faces_verts_uvs,
+                            const float* maps, const float* grad_texels, size_t P, int K, int pix_per_mesh,
+                            int F_packed, int N, int Hm, int Wm, int align_corners, int padding_mode, float* grad_maps,
+                            float* grad_bary, float* grad_faces_verts_uvs, void* ws, size_t ws_bytes,
+                            const AcfmRasterTuning* tuning, void* stream);
 
 /* ---- atlas-textured render -----------------------------------------------------------
  * replaces NeuralRenderer.forward, texture branch with atlas=True
