@@ -31,6 +31,14 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Pixel coordinate of an NDC coordinate, i = H-1 - ((c+1)H - 1)/2, held to [-2, H + 1] so that its floor / ceil fits
+// an int with the pixel of slack the callers add: a vertex far outside the image (|c| H / 2 beyond 2^31) saturated the
+// conversion and the slack overflowed.  The callers test "< 0" and ">= H" and then clamp to [0, H - 1]: all of that
+// comes out the same for the held value.
+__device__ __forceinline__ float ndc_to_pix_held(float c, float hf) {
+  return fminf(fmaxf(hf - 1.0f - ((c + 1.0f) * hf - 1.0f) * 0.5f, -2.0f), hf + 1.0f);
+}
+
 // ------------------------------------------------------------------------------- face tests
 struct Hit { float pz, sd, c0, c1, c2, d01, d02, d12; };
 

@@ -135,12 +135,12 @@ __global__ __launch_bounds__(TPB) void k_setup(const float* __restrict__ verts,
     ws.vidx[o] = make_int4(i0, i1, i2, 0);
     ws.fvis[o] = 0;
     if (!degenerate) {
-      // pixel index of an NDC coordinate: i = H-1 - ((c+1)H - 1)/2; one pixel of slack
+      // pixel index of an NDC coordinate (ndc_to_pix_held); one pixel of slack
       const float hf = (float)H;
-      int xa = (int)floorf(hf - 1.0f - ((b.y + 1.0f) * hf - 1.0f) * 0.5f) - 1;
-      int xb = (int)ceilf(hf - 1.0f - ((b.x + 1.0f) * hf - 1.0f) * 0.5f) + 1;
-      int ya = (int)floorf(hf - 1.0f - ((b.w + 1.0f) * hf - 1.0f) * 0.5f) - 1;
-      int yb = (int)ceilf(hf - 1.0f - ((b.z + 1.0f) * hf - 1.0f) * 0.5f) + 1;
+      int xa = (int)floorf(ndc_to_pix_held(b.y, hf)) - 1;
+      int xb = (int)ceilf(ndc_to_pix_held(b.x, hf)) + 1;
+      int ya = (int)floorf(ndc_to_pix_held(b.w, hf)) - 1;
+      int yb = (int)ceilf(ndc_to_pix_held(b.z, hf)) + 1;
       if (xb >= 0 && yb >= 0 && xa < H && ya < H) {
         xa = max(xa, 0); ya = max(ya, 0); xb = min(xb, H - 1); yb = min(yb, H - 1);
         const unsigned bit = 1u << (f & 31);

@@ -152,10 +152,10 @@ __global__ __launch_bounds__(256, TEXG_WAVES) void k_tex_bwd_faces(RasterWs ws, 
       if (b.x <= b.y && b.z <= b.w) {                        // not a degenerate face (inf, -inf, ..) or an emptied box
         // pixel range of the box: k_setup's formula with one pixel of slack, then tightened to the
         // pixels that pass the forward's own test (pixel centre inside the box, same float expressions)
-        xa = (int)floorf(hf - 1.0f - ((b.y + 1.0f) * hf - 1.0f) * 0.5f) - 1;
-        int xb = (int)ceilf(hf - 1.0f - ((b.x + 1.0f) * hf - 1.0f) * 0.5f) + 1;
-        ya = (int)floorf(hf - 1.0f - ((b.w + 1.0f) * hf - 1.0f) * 0.5f) - 1;
-        int yb = (int)ceilf(hf - 1.0f - ((b.z + 1.0f) * hf - 1.0f) * 0.5f) + 1;
+        xa = (int)floorf(ndc_to_pix_held(b.y, hf)) - 1;
+        int xb = (int)ceilf(ndc_to_pix_held(b.x, hf)) + 1;
+        ya = (int)floorf(ndc_to_pix_held(b.w, hf)) - 1;
+        int yb = (int)ceilf(ndc_to_pix_held(b.z, hf)) + 1;
         if (!(xb < 0 || yb < 0 || xa >= H || ya >= H)) {
           xa = max(xa, 0); ya = max(ya, 0); xb = min(xb, H - 1); yb = min(yb, H - 1);
           for (int it = 0; it < 3 && xa <= xb && pix_to_ndc(H - 1 - xa, H) > b.y; ++it) ++xa;

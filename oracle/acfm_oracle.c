@@ -22,7 +22,8 @@
  * generated from the importable reference modules (tests/golden/make_golden.py).
  * The RASTERIZER part is "parity unpinned": the reference ships no tests or fixtures for
  * it and PyTorch3D cannot be imported here, so it is anchored on analytic known-answer
- * tests (tests/test_oracle_raster.py) only.
+ * tests (tests/test_oracle_raster.py) and on a float64 restatement of its accept / reject
+ * rules on hand-built scenes (tests/test_raster_scenes.py) only.
  *
  * Numerics: fp32 throughout, compiled with -ffp-contract=off so that every multiply and
  * add rounds separately, exactly like the chain of separate torch kernels in the
