@@ -1,0 +1,409 @@
+"""Hostile, fenced memory for the operators' own allocations (a helper of the guard tests; not a conftest).
+
+The operators take every output, gradient and workspace from torch.empty / torch.empty_like, i.e. from torch's
+caching allocator, which usually hands back the block a test has just freed -- still holding the previous, correct
+result.  Under `armed(pattern)` every such allocation made by the package on a GPU instead lies inside a larger
+buffer filled with a poison pattern:
+
+    with armed("A") as g:
+        out = ops.something(...)
+    g.check()             # both fences of every allocation are bit-intact (a failure names the call site)
+    g.unwritten()         # per allocation: inner elements that still hold the pattern
+
+Two patterns exist so that two armed runs can be compared: a result that depends on a word nobody wrote differs
+between them (A is a NaN, B is finite; the integer bytes differ too).  Both integer patterns are negative as int32
+and int64: ids follow the -1 / >= 0 convention, so a word read by mistake as an index is rejected, not dereferenced.
+
+The patch replaces the module attributes torch.empty and torch.empty_like for the duration of the `with` block only,
+and intercepts a call only when the calling frame's module belongs to the package, the device is a GPU and
+pin_memory is not set.  Everything else goes to the real function.
+"""
+import contextlib
+import linecache
+import os
+import re
+import sys
+import threading
+import time
+from unittest import mock
+
+import torch
+
+PACKAGE = "acfm_video_3d_reconstruction_amd"
+
+# 64 KiB on each side.  The widest tile a wave stages is 64 rows of K = 32 x 3 floats = 24 KiB: covered twice.  A
+# multiple of 256 bytes, so the inner pointer keeps the alignment that ops._a16, ld4_real and the float4 paths assume.
+PAD_BYTES = 64 * 1024
+
+# per pattern: (float32 word, float16 word, integer byte, float64 word, bfloat16 word)
+PATTERNS = {
+    "A": (0x7FE5A5A5, 0x7EA5, 0xA5, 0x7FF5A5A5A5A5A5A5, 0x7FE5),     # NaNs
+    "B": (0x7F7FA5A5, 0x7BA5, 0xC3, 0x7FEFA5A5A5A5A5A5, 0x7F7F),     # finite
+}
+
+# Allocations that are unwritten by contract: "<file>:<function>:<name assigned>" -> one line citing the kernel line
+# that makes the unwritten part unreachable.  Single allocations only, never an operator or a file; each is covered by
+# the independence property of a guard case in which the unwritten part is non-empty.
+ALLOWED = {
+    "ops.py:_SilRender.forward:kth":
+        "acfm_raster.hip fwd_fill_block: kth is left alone on empty blocks; the backward reads it only where "
+        "mask != 0 (test_gpu_guards_raster.py: test_sil_render[empty_blocks ...])",
+    "ops.py:_lazy_pix_to_face.make_full:kth":
+        "acfm_raster.hip fwd_fill_block, as above: the re-render of a lazy pix_to_face has no backward, its kth is "
+        "dropped unread (test_gpu_guards_raster.py: test_sil_render[empty_blocks K20 lazy])",
+    "ops.py:_Chamfer.forward:ix":
+        "acfm_fit.hip k_chamfer `if (live) idx[..] = bi`: a row at or past its cloud's length gets no index; ch_side "
+        "clamps the backward to the same lengths (test_gpu_guards_fit.py: test_chamfer[lengths])",
+    "ops.py:_Chamfer.forward:iy":
+        "acfm_fit.hip k_chamfer, as idx_x (test_gpu_guards_fit.py: test_chamfer[lengths])",
+    "ops.py:_LaplacianSmoothing.forward:state":
+        "acfm_mesh.hip acfm_laplacian_smoothing: the per-mesh path (lap_blocked) keeps Wv in LDS and leaves state[0, 3P) "
+        "alone; k_lap_mesh_bwd is handed rowsum, glv and wface only (test_gpu_guards_fit.py: "
+        "test_laplacian_smoothing[eq-9x7-True-cot])",
+}
+
+_INT_VIEW = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+_REAL_EMPTY, _REAL_EMPTY_LIKE = torch.empty, torch.empty_like
+
+
+def _signed(word, bits):
+    return word - (1 << bits) if word >> (bits - 1) else word
+
+
+def pattern_word(pattern, dtype):
+    """-> (integer view dtype, fill value) of `pattern` for elements of `dtype`."""
+    f32, f16, byte, f64, bf16 = PATTERNS[pattern]
+    size = torch.empty((), dtype=dtype).element_size()
+    if dtype == torch.float32:
+        return torch.int32, _signed(f32, 32)
+    if dtype == torch.float16:
+        return torch.int16, _signed(f16, 16)
+    if dtype == torch.float64:
+        return torch.int64, _signed(f64, 64)
+    if dtype == torch.bfloat16:
+        return torch.int16, _signed(bf16, 16)
+    if dtype.is_floating_point or dtype.is_complex:
+        raise TypeError("guards: no pattern for %s" % dtype)
+    if size == 1:
+        return torch.uint8, byte
+    word = int.from_bytes(bytes([byte]) * size, "little")
+    return _INT_VIEW[size], _signed(word, 8 * size)
+
+
+def _guarded_alloc(shape, dtype, device, pattern):
+    """-> (base, pad, n, inner view): n elements of `shape` between two fences of `pad` elements, all poisoned."""
+    n = 1
+    for s in shape:
+        n *= int(s)
+    pad = PAD_BYTES // torch.empty((), dtype=dtype).element_size()
+    base = _REAL_EMPTY(n + 2 * pad, dtype=dtype, device=device)
+    view, word = pattern_word(pattern, dtype)
+    base.view(view).fill_(word)
+    return base, pad, n, base[pad:pad + n].view(tuple(int(s) for s in shape))
+
+
+class Record:
+    __slots__ = ("base", "pad", "n", "shape", "dtype", "site", "name")
+
+    def __init__(self, base, pad, n, shape, dtype, site, name):
+        self.base, self.pad, self.n, self.shape, self.dtype, self.site, self.name = base, pad, n, shape, dtype, site, name
+
+    @property
+    def workspace(self):
+        return self.dtype == torch.uint8 and len(self.shape) == 1
+
+    def __repr__(self):
+        return "%s (%s) %s %s" % (self.name, self.site, tuple(self.shape), str(self.dtype).replace("torch.", ""))
+
+
+_ASSIGN = re.compile(r"^\s*([A-Za-z_][\w.\[\]]*(?:\s*,\s*[A-Za-z_][\w.\[\]]*)*)\s*=[^=]")
+
+
+_SCOPE = re.compile(r"^(\s*)(?:class|def)\s+(\w+)")
+_QUALNAMES = {}
+
+
+def _qualname(code):
+    """Class.function of a code object, read off the source's indentation (co_qualname needs Python 3.11)."""
+    hit = _QUALNAMES.get(code)
+    if hit is None:
+        lines = linecache.getlines(code.co_filename)
+        names = [code.co_name]
+        at = min(code.co_firstlineno, len(lines)) - 1
+        indent = len(lines[at]) - len(lines[at].lstrip()) if lines else 0
+        for i in range(at - 1, -1, -1):
+            if indent == 0:
+                break
+            m = _SCOPE.match(lines[i])
+            if m and len(m.group(1)) < indent:
+                names.insert(0, m.group(2))
+                indent = len(m.group(1))
+        hit = _QUALNAMES[code] = ".".join(names)
+    return hit
+
+
+def _call_site(frame):
+    """-> ("ops.py:123", "ops.py:_SilRender.forward:kth") of the allocating frame."""
+    code = frame.f_code
+    fname = os.path.basename(code.co_filename)
+    site = "%s:%d" % (fname, frame.f_lineno)
+    func = _qualname(code)
+    # the statement may span lines: walk up to the line that holds the assignment
+    target = None
+    for ln in range(frame.f_lineno, max(frame.f_lineno - 6, code.co_firstlineno - 1), -1):
+        line = linecache.getline(code.co_filename, ln)
+        if line.lstrip().startswith("return"):
+            target = "return"
+            break
+        m = _ASSIGN.match(line)
+        if m:
+            target = m.group(1).replace(" ", "")
+            break
+    return site, "%s:%s:%s" % (fname, func, target if target else "line%d" % frame.f_lineno)
+
+
+def _is_capturing():
+    return torch.cuda.is_available() and torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+
+
+class Guard:
+    """What one `armed` block intercepted."""
+
+    def __init__(self, pattern, modules=(PACKAGE,), any_device=False):
+        if pattern not in PATTERNS:
+            raise ValueError("pattern must be one of %s" % sorted(PATTERNS))
+        self.pattern, self.modules, self.any_device = pattern, tuple(modules), bool(any_device)
+        self.records = []
+        self._lock = threading.Lock()   # autograd runs the backwards on a thread of its own
+
+    # ------------------------------------------------------------------ the two replacements
+    def _ours(self, frame, device, kwargs):
+        mod = frame.f_globals.get("__name__", "")
+        if not any(mod == m or mod.startswith(m + ".") for m in self.modules):
+            return False
+        if kwargs.get("pin_memory"):
+            return False
+        if kwargs.get("out") is not None or kwargs.get("layout", torch.strided) is not torch.strided:
+            return False
+        return self.any_device or device.type == "cuda"
+
+    def _make(self, frame, shape, dtype, device, requires_grad):
+        if _is_capturing():
+            raise RuntimeError("guards.armed: the current stream is capturing; the poison fill would be recorded")
+        base, pad, n, inner = _guarded_alloc(shape, dtype, device, self.pattern)
+        site, name = _call_site(frame)
+        with self._lock:
+            self.records.append(Record(base, pad, n, tuple(inner.shape), dtype, site, name))
+        SEEN.add("%s (%s)" % (name, site))
+        return inner.requires_grad_(True) if requires_grad else inner
+
+    def _empty(self, *size, **kwargs):
+        frame = sys._getframe(1)
+        dev = kwargs.get("device")
+        if dev is None:
+            device = _REAL_EMPTY(0).device
+        else:
+            device = torch.device(dev) if not isinstance(dev, torch.device) else dev
+        if not self._ours(frame, device, kwargs):
+            return _REAL_EMPTY(*size, **kwargs)
+        if "size" in kwargs:
+            size = (kwargs["size"],)
+        if len(size) == 1 and not isinstance(size[0], int):
+            size = tuple(size[0])
+        dtype = kwargs.get("dtype") or torch.get_default_dtype()
+        return self._make(frame, size, dtype, device, kwargs.get("requires_grad", False))
+
+    def _empty_like(self, t, **kwargs):
+        frame = sys._getframe(1)
+        dev = kwargs.get("device")
+        device = t.device if dev is None else (torch.device(dev) if not isinstance(dev, torch.device) else dev)
+        if not self._ours(frame, device, kwargs):
+            return _REAL_EMPTY_LIKE(t, **kwargs)
+        return self._make(frame, tuple(t.shape), kwargs.get("dtype") or t.dtype, device,
+                          kwargs.get("requires_grad", False))
+
+    # ------------------------------------------------------------------ inputs
+    def fenced(self, t):
+        """A contiguous copy of the floating tensor `t` inside a NaN-filled buffer, whose fences check() covers."""
+        out, rec = _fenced(t)
+        with self._lock:
+            self.records.append(rec)
+        return out
+
+    # ------------------------------------------------------------------ after the block
+    def _sync(self):
+        if torch.cuda.is_available() and torch.cuda.is_initialized():
+            torch.cuda.synchronize()
+
+    def _count(self, rec, lo, hi, equal):
+        if hi <= lo:
+            return None
+        view, word = pattern_word("A" if rec.name == "fenced" else self.pattern, rec.dtype)    # (inputs: always NaNs)
+        part = rec.base.view(view)[lo:hi]
+        return ((part == word) if equal else (part != word)).sum()
+
+    def _counts(self, jobs):
+        """jobs: [(key, 0-dim count tensor or None)] -> [(key, int)] with one transfer per device."""
+        live = [(k, c) for k, c in jobs if c is not None]
+        out = {id(k): 0 for k, _ in jobs}
+        by_dev = {}
+        for k, c in live:
+            by_dev.setdefault(c.device, []).append((k, c))
+        for group in by_dev.values():
+            vals = torch.stack([c for _, c in group]).cpu().tolist()
+            for (k, _), v in zip(group, vals):
+                out[id(k)] = int(v)
+        return [(k, out[id(k)]) for k, _ in jobs]
+
+    def broken_fences(self):
+        """-> ["<allocation>: N words changed before / past ..."], empty when every fence is bit-intact."""
+        self._sync()
+        jobs = []
+        for r in self.records:
+            jobs.append(((r, "before"), self._count(r, 0, r.pad, False)))
+            jobs.append(((r, "past"), self._count(r, r.pad + r.n, r.n + 2 * r.pad, False)))
+        return ["%r: %d element(s) changed %s the buffer" % (k[0], v, "before" if k[1] == "before" else "past the end of")
+                for k, v in self._counts(jobs) if v]
+
+    def check(self):
+        bad = self.broken_fences()
+        assert not bad, "fence broken (pattern %s):\n  %s" % (self.pattern, "\n  ".join(bad))
+
+    def unwritten(self, allowed=None):
+        """-> {allocation name: inner elements still holding the pattern}, zeros left out.  One-dimensional uint8
+        allocations are workspaces and exempt; `allowed` (default ALLOWED) names the ones unwritten by contract."""
+        allowed = ALLOWED if allowed is None else allowed
+        self._sync()
+        jobs = [(r, self._count(r, r.pad, r.pad + r.n, True)) for r in self.records
+                if not r.workspace and r.name != "fenced" and r.name not in allowed]
+        out = {}
+        for r, v in self._counts(jobs):
+            if v:
+                key = "%s (%s)" % (r.name, r.site)
+                out[key] = out.get(key, 0) + v
+        return out
+
+    def sites(self):
+        return sorted({r.name for r in self.records if r.name != "fenced"})
+
+
+def _fenced(t):
+    if not t.is_floating_point():
+        raise TypeError("guards.fenced: floating inputs only (index tensors are neither fenced nor poisoned)")
+    base, pad, n, inner = _guarded_alloc(tuple(t.shape), t.dtype, t.device, "A")
+    inner.copy_(t.detach())
+    rec = Record(base, pad, n, tuple(t.shape), t.dtype, "fenced", "fenced")
+    return (inner.requires_grad_(True) if t.requires_grad else inner), rec
+
+
+def fenced(t):
+    """A contiguous copy of the floating input tensor `t` that lives inside a NaN-filled buffer (64 KiB each side):
+    a kernel that reads one element before or past its input reads a NaN.  A leaf that requires a gradient if `t`
+    does.  Not for index tensors (faces, edges, ids, lengths)."""
+    return _fenced(t)[0]
+
+
+SEEN = set()      # "name (file:line)" of every allocation any armed block of this process intercepted
+
+
+@contextlib.contextmanager
+def armed(pattern, modules=(PACKAGE,), any_device=False):
+    """Poison and fence every torch.empty / torch.empty_like the package makes on a GPU inside the block; -> Guard.
+    `modules` / `any_device` widen the filter (for the helper's own CPU test)."""
+    if _is_capturing():
+        raise RuntimeError("guards.armed: the current stream is capturing (graph capture is out of scope)")
+    g = Guard(pattern, modules, any_device)
+    with mock.patch.object(torch, "empty", g._empty), mock.patch.object(torch, "empty_like", g._empty_like):
+        yield g
+
+
+# ---------------------------------------------------------------------------------- the four properties of a case
+def _bits(t):
+    return t.detach().contiguous().cpu().reshape(-1).view(torch.uint8) if t.numel() else t.detach().cpu().reshape(-1)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
+
+
+def _reset():
+    """Drop the package's cached scratch, so that every run allocates its own (under `armed`: poisoned)."""
+    from acfm_video_3d_reconstruction_amd import ops
+    ops.invalidate_setups()
+    ops.reset_loss_scratch()
+
+
+def run_case(fn, exact=True, reset=_reset, allowed=None, loose=()):
+    """fn(inp) -> {name: tensor}: runs a public operator forward and backward on inputs it builds itself, passing
+    every floating input tensor through `inp` first.  It is run unarmed, under armed("A") and under armed("B"), and
+    a fourth time with `inp` = fenced, and must hold:
+      (a) fences: check() passes in both armed runs;
+      (b) independence: every result is bit-identical across the runs (exact=True; a path with float atomics
+          passes exact=False, or names those results in `loose`, and holds them to its float64 reference inside
+          fn, in every run);
+      (c) completeness: unwritten() is empty outside ALLOWED in both armed runs;
+      (d) inputs: with fenced inputs the results equal the plain run bit for bit (exact=True).
+    -> (the results of the plain run, {"A": Guard, "B": Guard})."""
+    def ident(t):
+        return t
+    reset()
+    plain = fn(ident)
+    runs, held = {}, {}
+    for p in ("A", "B"):
+        reset()
+        with armed(p) as g:
+            runs[p] = fn(ident)
+        g.check()
+        held[p] = g
+    reset()
+    g = Guard("A")                   # unarmed: only the inputs are fenced
+    runs["fenced"] = fn(g.fenced)
+    g.check()
+    reset()
+    if exact:
+        for tag, res in runs.items():
+            assert sorted(res) == sorted(plain)
+            for k in plain:
+                if k in loose:
+                    continue
+                if plain[k] is None:
+                    assert res[k] is None, k
+                    continue
+                assert same_bits(plain[k], res[k]), \
+                    "%s differs between the plain run and the %s run (max |diff| %s)" % (
+                        k, tag, _maxdiff(plain[k], res[k]))
+    for p, g in held.items():        # after (b): a poison NaN that reached a result keeps its payload and counts here too
+        left = g.unwritten(allowed)
+        assert not left, "pattern %s: elements nobody wrote: %s" % (p, left)
+    return plain, held
+
+
+def still_poisoned(guard, name):
+    """Inner elements of the allocations called `name` that still hold the pattern (for the ALLOWED entries: the case
+    that covers one shows that its unwritten part is not empty)."""
+    guard._sync()
+    return sum(int(guard._count(r, r.pad, r.pad + r.n, True) or 0) for r in guard.records if r.name == name)
+
+
+def _maxdiff(a, b):
+    try:
+        return float((a.double() - b.double()).abs().max())
+    except Exception:     # NaNs, shapes
+        return "n/a"
+
+
+def module_report(name):
+    """A module-scoped autouse fixture that prints, once, the wall time of the file's tests and every allocation
+    `armed` intercepted during them."""
+    import pytest
+
+    @pytest.fixture(scope="module", autouse=True)
+    def _guards_report():
+        global SEEN
+        earlier, SEEN, t0 = SEEN, set(), time.time()
+        yield
+        mine, SEEN = sorted(SEEN), earlier | SEEN
+        print("\n[guards] %s: %.1f s wall, %d allocation sites intercepted:" % (name, time.time() - t0, len(mine)))
+        for s in mine:
+            print("[guards]   %s" % s)
+    return _guards_report

@@ -1,0 +1,305 @@
+"""GPU: the raster unit (projection, silhouette, texture, hard raster, fragments) on hostile, fenced memory.
+
+Every case runs a public operator forward and backward four times (tests/guards.py run_case): plain, with every
+buffer the operator allocates poisoned with pattern A (NaNs) and with pattern B (finite), and with its floating
+inputs inside NaN fences.  Asserted: no fence is touched, the results are the same bits in all four runs, and no
+element of an output or gradient still holds the poison.  The backwards run in the fixed-point mode
+(_lib.raster_tuning(deterministic=True)), so bits are the claim there too; the one path with float atomics and no such
+mode (acfm_tex_backward, R > 8) is held to the float64 sum of tests/test_gpu_atlas_grad_shapes.py in every run."""
+import numpy as np
+import pytest
+import torch
+
+import guards
+import raster_scenes as S
+from oracle import oracle as O
+
+pytestmark = pytest.mark.gpu
+_report = guards.module_report(__name__)
+
+
+def _dev():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch.device("cuda:0")
+
+
+def _leaf(a, d, grad=True):
+    return torch.tensor(a, device=d, requires_grad=grad)
+
+
+def _bird(meshes, N, seed=0):
+    from acfm_video_3d_reconstruction_amd.synthetic import batch_verts, make_cams
+    rng = np.random.default_rng(seed)
+    v, f = meshes["bird_v"], meshes["bird_f"]
+    return batch_verts(v, N, rng), make_cams(N, rng, extent=float(np.abs(v).max())), np.ascontiguousarray(f)
+
+
+def _empty_blocks(H=40):
+    """Two meshes of one small face each: 23 of the 25 8 x 8 blocks of either frame hold no face at all."""
+    return S._scene("empty_blocks", [[S._tri(H, (1, 1), (6, 1.5), (2, 6), 1.0)], [S._tri(H, (17, 18), (22, 17), (19, 23), 1.5)]],
+                    H, S.SIL_BLUR)
+
+
+def _scene_inputs(sc):
+    verts, cams = S.sil_inputs(sc)
+    return verts, cams, sc["faces"], sc["H"]
+
+
+def _G(shape, seed, d, scale=1.0):
+    return torch.tensor((np.random.default_rng(seed).standard_normal(shape) * scale).astype(np.float32), device=d)
+
+
+# ------------------------------------------------------------------------------------------------ projection
+@pytest.mark.parametrize("op", ["project", "project_xy"])
+def test_projection(op):
+    from acfm_video_3d_reconstruction_amd import ops
+    d = _dev()
+    rng = np.random.default_rng(1)
+    N, V = 3, 65
+    verts = rng.standard_normal((N, V, 3)).astype(np.float32)
+    cams = rng.standard_normal((N, 7)).astype(np.float32)
+
+    def fn(inp):
+        tv, tc = inp(_leaf(verts, d)), inp(_leaf(cams, d))
+        out = getattr(ops, op)(tv, tc, 0.5)
+        gv, gc = torch.autograd.grad(out, (tv, tc), inp(_G(out.shape, 2, d)))
+        return dict(out=out, gv=gv, gc=gc)
+    guards.run_case(fn)
+
+
+# ------------------------------------------------------------------------------------------------ silhouette
+# name -> (inputs, K, k_out, split, storage); inputs: a scene builder, or (N, H) of the bird
+SIL_CASES = {
+    "shared_edge K2 nearest": (lambda: S.shared_edge(16), 2, 1, 0, "f32"),
+    "shared_edge K20 all split": (lambda: S.shared_edge(16), 20, 20, 1, "f32"),
+    "dup_stack K2 lazy": (lambda: S.dup_stack(2, 3), 2, "lazy", 0, "f32"),
+    "dup_stack K20 lazy split": (lambda: S.dup_stack(20, 21), 20, "lazy", 1, "f32"),
+    "bird 3x40 K20 lazy": ((3, 40), 20, "lazy", 0, "f32"),
+    "bird 8x40 K2 all split": ((8, 40), 2, 2, 1, "f32"),
+    "bird 8x40 K20 nearest": ((8, 40), 20, 1, 0, "f32"),
+    "bird 3x37 K20 f16": ((3, 37), 20, 1, 0, "f16"),
+    "bird 3x37 K2 f16 split": ((3, 37), 2, 1, 1, "f16"),
+    "empty_blocks K20 lazy": (_empty_blocks, 20, "lazy", 0, "f32"),
+    "empty_blocks K2 all split": (_empty_blocks, 2, 2, 1, "f32"),
+}
+
+
+def _sil_inputs(meshes, src):
+    if callable(src):
+        return _scene_inputs(src())
+    verts, cams, f = _bird(meshes, src[0])
+    return verts, cams, f, src[1]
+
+
+@pytest.mark.parametrize("name", list(SIL_CASES))
+def test_sil_render(meshes, name):
+    """sil_render with the gradient of an explicit mask gradient and of the projection output; a lazy pix_to_face is
+    forced inside the armed block (its re-render allocates a second set of buffers)."""
+    from acfm_video_3d_reconstruction_amd import _lib, ops
+    d = _dev()
+    src, K, k_out, split, storage = SIL_CASES[name]
+    verts, cams, f, H = _sil_inputs(meshes, src)
+    N, V = verts.shape[:2]
+    tf = torch.from_numpy(f).to(d)
+
+    def fn(inp):
+        tv, tc = inp(_leaf(verts, d)), inp(_leaf(cams, d))
+        with _lib.raster_tuning(split=split, deterministic=True, record_cover=False):
+            mask, p2f = ops.sil_render(tv, tf, tc, H, K=K, k_out=k_out, storage=storage)
+            proj = p2f._acfm_proj[1]
+            vis = p2f._acfm_vis
+            full = p2f + 0                                     # forces a LazyPixToFace
+            loss = (mask.float() * _G((N, H, H), 3, d)).sum() + (proj * _G((N, V, 2), 4, d)).sum()
+            gv, gc = torch.autograd.grad(loss, (tv, tc))
+        return dict(mask=mask, p2f=full, vis=vis, proj=proj, gv=gv, gc=gc)
+    plain, held = guards.run_case(fn)
+    assert bool((plain["p2f"] >= 0).any()) and bool((plain["gv"] != 0).any())
+    if name.startswith("empty_blocks"):      # the ALLOWED entry: its unwritten part is there, and the gradient ignores it
+        assert plain["p2f"].shape == (N, H, H, K)
+        for g in held.values():
+            assert guards.still_poisoned(g, "ops.py:_SilRender.forward:kth") > 0
+
+
+@pytest.mark.parametrize("storage,H", [("f32", 40), ("f32", 37), ("f16", 37)])
+def test_sil_render_losses_shared_references(meshes, storage, H):
+    """The fused render + silhouette losses with gt / edt shared by G = 2 hypotheses; gradients from the losses.
+    H = 40: every 8 x 8 block is whole (fwd_fill_block_whole zeroes the empty blocks' partial sums); H = 37: the
+    generic fwd_fill_block does."""
+    from acfm_video_3d_reconstruction_amd import _lib, ops
+    d = _dev()
+    N, G = 4, 2
+    verts, cams, f = _bird(meshes, N, seed=5)
+    rng = np.random.default_rng(6)
+    gt = (rng.uniform(size=(N // G, H, H)) > 0.5).astype(np.float32)
+    edt = rng.uniform(0, 3, size=(N // G, H, H)).astype(np.float32)
+    tf = torch.from_numpy(f).to(d)
+
+    def fn(inp):
+        tv, tc = inp(_leaf(verts, d)), inp(_leaf(cams, d))
+        with _lib.raster_tuning(deterministic=True, record_cover=False):
+            losses, mask, p2f = ops.sil_render_losses(tv, tf, tc, H, gt=inp(_leaf(gt, d, False)), edt=inp(_leaf(edt, d, False)),
+                                                      k_out=1, storage=storage)
+            gv, gc = torch.autograd.grad(losses, (tv, tc), _G((N, 4), 7, d))
+        return dict(losses=losses, mask=mask, p2f=p2f + 0, gv=gv, gc=gc)
+    plain, _ = guards.run_case(fn)
+    assert bool((plain["gv"] != 0).any())
+
+
+@pytest.mark.parametrize("prefill,H", [(True, 40), (False, 40), (True, 37)])
+def test_sil_then_tex_on_the_same_tensors(meshes, prefill, H):
+    """record_cover=True: the texture render takes the silhouette render's workspace over and shades from its cover
+    plane (ws_ready = 2); with the prefill its constant planes on the empty blocks were stored by the silhouette kernel
+    into buffers it adopts (ws_ready = 3).  Both renders and both backwards."""
+    from acfm_video_3d_reconstruction_amd import _lib, ops
+    d = _dev()
+    N, R = 3, 3
+    verts, cams, f = _bird(meshes, N, seed=8)
+    F = f.shape[0]
+    atlas = np.random.default_rng(9).uniform(0, 1, (N, F, R, R, 3)).astype(np.float32)
+    tf = torch.from_numpy(f).to(d)
+    old = ops.PREFILL_TEX[0]
+
+    def fn(inp):
+        tv, tc, ta = inp(_leaf(verts, d)), inp(_leaf(cams, d)), inp(_leaf(atlas, d))
+        ops.PREFILL_TEX[0] = prefill
+        try:
+            with _lib.raster_tuning(deterministic=True, record_cover=True):
+                mask, p2f = ops.sil_render(tv, tf, tc, H, k_out=1)
+                imgs, sil, p2 = ops.tex_render(tv, tf, tc, ta, H)
+                gv, gc = torch.autograd.grad((mask * _G((N, H, H), 10, d)).sum(), (tv, tc))
+                ga, = torch.autograd.grad(imgs, ta, _G((N, 3, H, H), 11, d))
+        finally:
+            ops.PREFILL_TEX[0] = old
+        return dict(mask=mask, p2f=p2f + 0, imgs=imgs, sil=sil, p2=p2, gv=gv, gc=gc, ga=ga)
+    plain, held = guards.run_case(fn)
+    assert bool((plain["p2"] >= 0).any()) and bool((plain["ga"] != 0).any())
+    assert ("ops.py:_SilRender.forward:prefill" in held["A"].sites()) == prefill
+
+
+# ------------------------------------------------------------------------------------------------ texture
+def test_hard_raster_and_vertex_colors(meshes):
+    from acfm_video_3d_reconstruction_amd import ops
+    d = _dev()
+    N, H = 3, 40
+    verts, cams, f = _bird(meshes, N, seed=12)
+    proj = O.project(verts, cams)
+    rgb = np.random.default_rng(13).uniform(0, 1, (N, verts.shape[1], 3)).astype(np.float32)
+    tf = torch.from_numpy(f).to(d)
+
+    def fn(inp):
+        p2f = ops.hard_raster(inp(_leaf(proj, d, False)), tf, H)
+        imgs, sil, p2 = ops.vertex_color_render(inp(_leaf(verts, d, False)), tf, inp(_leaf(cams, d, False)),
+                                                inp(_leaf(rgb, d, False)), H)
+        return dict(p2f=p2f, vis=p2f._acfm_vis, imgs=imgs, sil=sil, p2=p2)
+    plain, _ = guards.run_case(fn)
+    assert bool((plain["p2f"] >= 0).any())
+
+
+@pytest.mark.parametrize("N,NA", [(3, 3), (4, 2)])
+def test_tex_render_gather(meshes, N, NA):
+    """tex_render and the gather form of the atlas gradient (acfm_tex_backward_faces, R = 3), atlas per mesh and shared."""
+    from acfm_video_3d_reconstruction_amd import ops
+    d = _dev()
+    H, R = 40, 3
+    verts, cams, f = _bird(meshes, N, seed=14)
+    atlas = np.random.default_rng(15).uniform(0, 1, (NA, f.shape[0], R, R, 3)).astype(np.float32)
+    tf = torch.from_numpy(f).to(d)
+
+    def fn(inp):
+        ta = inp(_leaf(atlas, d))
+        imgs, sil, p2 = ops.tex_render(inp(_leaf(verts, d, False)), tf, inp(_leaf(cams, d, False)), ta, H)
+        ga, = torch.autograd.grad(imgs, ta, inp(_G((N, 3, H, H), 16, d)))
+        return dict(imgs=imgs, sil=sil, p2=p2, ga=ga)
+    plain, _ = guards.run_case(fn)
+    assert bool((plain["ga"] != 0).any())
+
+
+@pytest.mark.parametrize("storage,H", [("f32", 40), ("f32", 37), ("f16", 37)])
+def test_tex_render_mse_fused(meshes, storage, H):
+    """The fused render + masked MSE (acfm_tex_mse_forward / acfm_tex_mse_backward_faces) at R = 2, the atlas and the
+    references shared by G = 2 hypotheses."""
+    from acfm_video_3d_reconstruction_amd import ops
+    d = _dev()
+    N, NA, R = 4, 2, 2
+    verts, cams, f = _bird(meshes, N, seed=17)
+    rng = np.random.default_rng(18)
+    atlas = rng.uniform(0, 1, (NA, f.shape[0], R, R, 3)).astype(np.float32)
+    ref = rng.uniform(0, 1, (NA, 3, H, H)).astype(np.float32)
+    msk = (rng.uniform(size=(NA, H, H)) > 0.3).astype(np.float32)
+    tf = torch.from_numpy(f).to(d)
+
+    def fn(inp):
+        ta = inp(_leaf(atlas, d))
+        loss, imgs, sil, p2 = ops.tex_render_mse(inp(_leaf(verts, d, False)), tf, inp(_leaf(cams, d, False)), ta,
+                                                 inp(_leaf(ref, d, False)), inp(_leaf(msk, d, False)), H, storage=storage)
+        ga, = torch.autograd.grad(loss, ta, _G((N,), 19, d))
+        return dict(loss=loss, imgs=imgs, sil=sil, p2=p2, ga=ga)
+    plain, _ = guards.run_case(fn)
+    assert bool((plain["ga"] != 0).any())
+
+
+def test_tex_render_scatter_R9(meshes):
+    """R = 9 is past the gather form: acfm_tex_backward adds with global float atomics and has no deterministic mode,
+    so the gradient is held to the float64 sum and the derived bound of test_gpu_atlas_grad_shapes in every run; the
+    forward is bits."""
+    from acfm_video_3d_reconstruction_amd import ops
+    from test_gpu_atlas_grad_shapes import _check_against_reference
+    d = _dev()
+    N, H, R = 3, 40, 9
+    verts, cams, f = _bird(meshes, N, seed=20)
+    atlas = np.random.default_rng(21).uniform(0, 1, (N, f.shape[0], R, R, 3)).astype(np.float32)
+    g = np.random.default_rng(22).standard_normal((N, 3, H, H)).astype(np.float32)
+    tidx = O.tex_render(verts, f, cams, atlas, H)[3]
+    tf = torch.from_numpy(f).to(d)
+    fwd = []
+
+    def fn(inp):
+        ta = inp(_leaf(atlas, d))
+        imgs, sil, p2 = ops.tex_render(inp(_leaf(verts, d, False)), tf, inp(_leaf(cams, d, False)), ta, H)
+        ga, = torch.autograd.grad(imgs, ta, inp(_leaf(g, d, False)))
+        _check_against_reference(ga.cpu().numpy(), tidx, g, N)
+        fwd.append(dict(imgs=imgs.detach(), sil=sil, p2=p2))
+        return dict(ga=ga)
+    guards.run_case(fn, exact=False)
+    assert len(fwd) == 4
+    for r in fwd[1:]:
+        for k in r:
+            assert guards.same_bits(r[k], fwd[0][k]), k
+
+
+# ------------------------------------------------------------------------------------------------ fragments
+def _frag_cases():
+    from acfm_video_3d_reconstruction_amd.ops import FRAGMENT_K
+    cases = [(K, 16, bool(i % 2), "all") for i, K in enumerate(FRAGMENT_K)]
+    cases += [(4, 16, clip, up) for clip in (False, True) for up in ("zbuf", "bary", "dists")]
+    cases += [(10, 16, True, "all"), (1, 40, False, "all"), (32, 40, True, "all"), (32, 40, False, "dists")]
+    return cases
+
+
+@pytest.mark.parametrize("K,H,clip,upstream", _frag_cases())
+def test_rasterize_fragments(meshes, K, H, clip, upstream):
+    """rasterize_fragments for every K the library instantiates; the backward with each single upstream gradient (the
+    other two NULL) and with all three, in the fixed-point mode."""
+    from acfm_video_3d_reconstruction_amd import _lib, ops
+    from test_gpu_fragments import _scene
+    d = _dev()
+    if H == 16:
+        sc = S.dup_stack(K, K + 1)
+        ndc, f = sc["ndc"], sc["faces"]
+    else:
+        ndc, f = _scene(meshes, "bird", 3, 23)
+    N = ndc.shape[0]
+    tf = torch.from_numpy(f).to(d)
+
+    def fn(inp):
+        tv = inp(_leaf(ndc, d))
+        with _lib.raster_tuning(deterministic=True):
+            p2f, zbuf, bary, dists = ops.rasterize_fragments(tv, tf, H, K, blur_radius=S.SIL_BLUR,
+                                                             clip_barycentric_coords=clip)
+            terms = dict(zbuf=(zbuf * _G((N, H, H, K), 24, d)).sum(), bary=(bary * _G((N, H, H, K, 3), 25, d)).sum(),
+                         dists=(dists * _G((N, H, H, K), 26, d, 100.0)).sum())
+            loss = sum(terms.values()) if upstream == "all" else terms[upstream]
+            gv, = torch.autograd.grad(loss, tv)
+        return dict(p2f=p2f, zbuf=zbuf, bary=bary, dists=dists, gv=gv)
+    plain, _ = guards.run_case(fn)
+    assert bool((plain["p2f"] >= 0).any()) and bool((plain["gv"] != 0).any())
