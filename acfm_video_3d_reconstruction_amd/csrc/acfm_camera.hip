@@ -102,7 +102,9 @@ __device__ __forceinline__ void cam_backward(const float* __restrict__ e, const 
 
 // The same straight from the per-hypothesis embedding tables (mesh_net.py:436-444: one nn.Embedding(frames, 7) per
 // hypothesis): row r = g N + n reads tables[sel ? sel[r] : g][frames_idx[n]]; the backward adds into dense per-table
-// gradients (zeroed by the caller; float atomics: frames of a batch are distinct, so every cell gets one add).
+// gradients (zeroed by the entry point; float atomics: a frame id that occurs twice in the batch, or two hypotheses that
+// select one table for a frame, sum in the cell as nn.Embedding's backward does; with distinct ids every cell gets one
+// add and the result does not depend on the order).
 // A frame id outside [0, n_frames) or a table id outside [0, n_tables) -- nn.Embedding raises on those (main.py:551-570)
 // -- never becomes an address: the forward writes a NaN camera for that row (the loss of the step is then NaN, loudly,
 // without a host synchronisation inside a captured step), the backward skips it; ops.camera_pipeline_tables(check=True)

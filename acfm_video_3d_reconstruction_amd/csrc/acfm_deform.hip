@@ -60,37 +60,6 @@ __global__ __launch_bounds__(256) void k_deform_apply(const float* __restrict__ 
   }
 }
 
-// grad_delta[n,k,c] = sum_v P[v,k] g[n,v,c];  grid (ceil(Kh/16), ceil(3N/64), ceil(V/VCHUNK)):
-// the long inner dimension (V) is split over workgroups, partial tiles are added with float
-// atomics into the zeroed output (the output is tiny: K_h x 3N).
-constexpr int VCHUNK = 64;
-__global__ __launch_bounds__(256) void k_deform_grad_delta(const float* __restrict__ P,
-                                                           const float* __restrict__ g, int N, int V,
-                                                           int Kh, float* __restrict__ gdelta) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int k0 = blockIdx.x * 16, j0 = (blockIdx.y * 4 + wv) * 16;
-  const int J = 3 * N;
-  if (j0 >= J) return;
-  const int vb = blockIdx.z * VCHUNK, ve = min(vb + VCHUNK, V);
-  const f32x4 acc = mfma_tile_16x16(
-      lane, vb, ve,
-      [&](int i, int v) { const int k = k0 + i; return (k < Kh && v < ve) ? P[(size_t)v * Kh + k] : 0.f; },
-      [&](int v, int jj) {
-        const int j = j0 + jj;
-        if (j >= J || v >= ve) return 0.f;
-        const int n = j / 3, c = j - 3 * n;
-        return g[((size_t)n * V + v) * 3 + c];
-      });
-  const int j = j0 + (lane & 15);
-  if (j >= J) return;
-  const int n = j / 3, c = j - 3 * n;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int k = k0 + (lane >> 4) * 4 + r;
-    if (k < Kh) atomicAdd(&gdelta[((size_t)n * Kh + k) * 3 + c], acc[r]);
-  }
-}
-
 // grad_P[v,k] = sum_{n,c} g[n,v,c] delta[n,k,c];  grid (ceil(V/16), ceil(Kh/64))
 __global__ __launch_bounds__(256) void k_deform_grad_P(const float* __restrict__ g,
                                                        const float* __restrict__ delta, int N, int V,
@@ -122,22 +91,10 @@ __global__ __launch_bounds__(256) void k_deform_grad_P(const float* __restrict__
   }
 }
 
-// grad_mean[v,c] = sum_n g[n,v,c]: frames split over blockIdx.y (8 per block), partial sums added
-// atomically into the zeroed output
-constexpr int MEAN_FRAMES = 8;
-__global__ void k_deform_grad_mean(const float* __restrict__ g, int N, int V3, float* __restrict__ gmean) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V3) return;
-  const int n0 = blockIdx.y * MEAN_FRAMES, n1 = min(n0 + MEAN_FRAMES, N);
-  float s = 0.f;
-  for (int n = n0; n < n1; ++n) s += g[(size_t)n * V3 + i];
-  atomicAdd(&gmean[i], s);
-}
-
 // grad_delta and grad_mean in ONE launch, without atomics or zero fills (they were two kernels and
 // two zero-fill launches: 21 us of launch latency for a few hundred KB of work):
-//   blocks [0, TK*TJ): one 16x16 tile of grad_delta each; the workgroup's four waves take a quarter of
-//     the inner dimension (V) each and the partial tiles are summed through LDS;
+//   blocks [0, TK*TJ): one 16x16 tile of grad_delta each; the workgroup's DM_WAVES waves take a share of
+//     the inner dimension (V) each and the partial tiles are summed through LDS, left to right;
 //   blocks [TK*TJ, ..): grad_mean, one thread per (v, c), four partial sums over the frames in flight.
 constexpr int DM_WAVES = 16;   // waves per workgroup of k_deform_bwd_dm
 __global__ __launch_bounds__(64 * DM_WAVES) void k_deform_bwd_dm(const float* __restrict__ P,
@@ -273,25 +230,17 @@ int acfm_deform_apply(const float* mean_v, const float* P, const float* delta, i
 int acfm_deform_apply_backward(const float* P, const float* delta, const float* grad_verts, int N, int V,
                                int Kh, float* grad_delta, float* grad_mean, float* grad_P, void* stream) {
   if (!P || !delta || !grad_verts || N <= 0 || V <= 0 || Kh <= 0 || N > 1000000) return ACFM_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(ACFM_PROF_DEFORM_BWD, st);
+  // k_deform_bwd_dm's tile and block indices are ints: a grid past 2^31 - 1 blocks (K_h in the hundreds of thousands
+  // at the largest N) is refused
   const int TK = (Kh + 15) / 16, TJ = (3 * N + 15) / 16;
   const int DMT = 64 * DM_WAVES;
-  if ((grad_delta || grad_mean) && (size_t)TK * TJ + (size_t)(3 * V + DMT - 1) / DMT <= 0x7fffffffull) {
+  if ((grad_delta || grad_mean) && (size_t)TK * TJ + (size_t)(3 * V + DMT - 1) / DMT > 0x7fffffffull)
+    return ACFM_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(ACFM_PROF_DEFORM_BWD, st);
+  if (grad_delta || grad_mean)
     hipLaunchKernelGGL(k_deform_bwd_dm, dim3((unsigned)(TK * TJ + (3 * V + DMT - 1) / DMT)), dim3(DMT), 0, st, P,
                        grad_verts, N, V, Kh, TK, TJ, grad_delta, grad_mean);
-  } else {
-    if (grad_delta) {
-      if (zero_async(grad_delta, sizeof(float) * 3 * (size_t)N * Kh, st) != ACFM_OK) return ACFM_E_LAUNCH;
-      hipLaunchKernelGGL(k_deform_grad_delta, dim3((Kh + 15) / 16, (3 * N + 63) / 64, (V + VCHUNK - 1) / VCHUNK),
-                         dim3(256), 0, st, P, grad_verts, N, V, Kh, grad_delta);
-    }
-    if (grad_mean) {
-      if (zero_async(grad_mean, sizeof(float) * 3 * (size_t)V, st) != ACFM_OK) return ACFM_E_LAUNCH;
-      hipLaunchKernelGGL(k_deform_grad_mean, dim3((3 * V + 255) / 256, (N + MEAN_FRAMES - 1) / MEAN_FRAMES),
-                         dim3(256), 0, st, grad_verts, N, 3 * V, grad_mean);
-    }
-  }
   if (grad_P)
     hipLaunchKernelGGL(k_deform_grad_P, dim3((V + 15) / 16, (Kh + 63) / 64), dim3(256), 0, st, grad_verts,
                        delta, N, V, Kh, grad_P);

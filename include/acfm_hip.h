@@ -112,7 +112,8 @@ int acfm_project_xy_backward(const float* verts, const float* cams, const float*
  * (factorised once per optimiser step, see deform.py):  verts[n] = mean_v + P delta[n].
  *   mean_v [V,3], P [V,K_h], delta [N,K_h,3] -> verts [N,V,3]   (f32 MFMA 16x16x4)
  * backward: grad_verts [N,V,3] -> grad_delta [N,K_h,3] = P^T g_n, grad_mean [V,3] = sum_n g_n,
- *   grad_P [V,K_h] = sum_n g_n delta_n^T (each may be NULL). */
+ *   grad_P [V,K_h] = sum_n g_n delta_n^T (each may be NULL).  grad_delta and grad_mean come from one launch of
+ *   ceil(K_h/16) ceil(3N/16) + ceil(3V/1024) workgroups: ACFM_E_BADARG if that passes 2^31 - 1. */
 int acfm_deform_apply(const float* mean_v, const float* P, const float* delta, int N, int V, int Kh,
                       float* verts, void* stream);
 int acfm_deform_apply_backward(const float* P, const float* delta, const float* grad_verts, int N, int V,

@@ -44,6 +44,18 @@ def test_library_exports_nothing_undeclared():
     assert not any("debug" in s for s in exported)
 
 
+def test_deform_apply_backward_refuses_a_grid_past_int_range():
+    """k_deform_bwd_dm indexes its ceil(Kh/16) ceil(3N/16) tiles with ints: past 2^31 - 1 workgroups the entry point
+    returns ACFM_E_BADARG (1) before anything is launched or read (the pointers here are never dereferenced)."""
+    from acfm_video_3d_reconstruction_amd import _lib
+    _lib.build()
+    fake = ctypes.c_void_p(0x1000)
+    args = (fake, fake, fake, 1000000, 1, 200000)              # 12500 x 187500 tiles = 2.34e9
+    assert _lib.lib().acfm_deform_apply_backward(*args, fake, fake, None, None) == 1
+    assert _lib.lib().acfm_deform_apply_backward(*args, fake, None, None, None) == 1
+    assert _lib.lib().acfm_deform_apply_backward(*args, None, fake, None, None) == 1
+
+
 def test_no_cpu_fallback():
     from acfm_video_3d_reconstruction_amd import ops
     from acfm_video_3d_reconstruction_amd.nnutils.nmr import NeuralRenderer
