@@ -260,7 +260,7 @@ class raster_tuning:
     def __init__(self, split=-5, grid_div=(0, 0, 0), deterministic=False, record_cover=None):
         """deterministic=True: the silhouette backward accumulates in fixed point (bit-reproducible run to run).
         record_cover: True / False forces ACFM_RECORD_COVER (the silhouette render leaves the nearest covering face
-        per pixel for a texture render that takes its workspace over) on / off; None lets ops.py decide -- on while
+        per pixel for a texture render that takes its workspace over) on / off; None lets ops/render.py decide -- on while
         texture renders do follow the silhouette renders on this device.
         (Bit 1 of the flags, half storage, is not set here: it changes buffer types, so the ops that support it take
         storage="f16" and set it themselves -- with_f16() below.)"""

@@ -27,12 +27,12 @@ _BUILT = ("only MaskFlownet's configuration is built (kernel_size=3, stride=1, p
 
 def set_trainable(flag):
     """Turn the backward kernels of the flow operators on or off for the whole process -> the previous value."""
-    previous, ops._FLOW_TRAINABLE = ops._FLOW_TRAINABLE, bool(flag)
+    previous, ops._FLOW_TRAINABLE[0] = ops._FLOW_TRAINABLE[0], bool(flag)
     return previous
 
 
 def is_trainable():
-    return ops._FLOW_TRAINABLE
+    return ops._FLOW_TRAINABLE[0]
 
 
 @contextlib.contextmanager

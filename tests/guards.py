@@ -45,18 +45,18 @@ PATTERNS = {
 # that makes the unwritten part unreachable.  Single allocations only, never an operator or a file; each is covered by
 # the independence property of a guard case in which the unwritten part is non-empty.
 ALLOWED = {
-    "ops.py:_SilRender.forward:kth":
+    "render.py:_SilRender.forward:kth":
         "acfm_raster.hip fwd_fill_block: kth is left alone on empty blocks; the backward reads it only where "
         "mask != 0 (test_gpu_guards_raster.py: test_sil_render[empty_blocks ...])",
-    "ops.py:_lazy_pix_to_face.make_full:kth":
+    "render.py:_lazy_pix_to_face.make_full:kth":
         "acfm_raster.hip fwd_fill_block, as above: the re-render of a lazy pix_to_face has no backward, its kth is "
         "dropped unread (test_gpu_guards_raster.py: test_sil_render[empty_blocks K20 lazy])",
-    "ops.py:_Chamfer.forward:ix":
+    "mesh_terms.py:_Chamfer.forward:ix":
         "acfm_fit.hip k_chamfer `if (live) idx[..] = bi`: a row at or past its cloud's length gets no index; ch_side "
         "clamps the backward to the same lengths (test_gpu_guards_fit.py: test_chamfer[lengths])",
-    "ops.py:_Chamfer.forward:iy":
+    "mesh_terms.py:_Chamfer.forward:iy":
         "acfm_fit.hip k_chamfer, as idx_x (test_gpu_guards_fit.py: test_chamfer[lengths])",
-    "ops.py:_LaplacianSmoothing.forward:state":
+    "mesh_terms.py:_LaplacianSmoothing.forward:state":
         "acfm_mesh.hip acfm_laplacian_smoothing: the per-mesh path (lap_blocked) keeps Wv in LDS and leaves state[0, 3P) "
         "alone; k_lap_mesh_bwd is handed rowsum, glv and wface only (test_gpu_guards_fit.py: "
         "test_laplacian_smoothing[eq-9x7-True-cot])",
@@ -143,7 +143,7 @@ def _qualname(code):
 
 
 def _call_site(frame):
-    """-> ("ops.py:123", "ops.py:_SilRender.forward:kth") of the allocating frame."""
+    """-> ("render.py:123", "render.py:_SilRender.forward:kth") of the allocating frame."""
     code = frame.f_code
     fname = os.path.basename(code.co_filename)
     site = "%s:%d" % (fname, frame.f_lineno)

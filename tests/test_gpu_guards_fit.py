@@ -62,7 +62,7 @@ def test_laplacian_smoothing(name, hinted, method):
     plain, held = guards.run_case(fn, loose=("loss", "gv"))
     if hinted and method == "cot":           # the ALLOWED entry: Wv of the per-mesh path stays unwritten
         for g in held.values():
-            assert guards.still_poisoned(g, "ops.py:_LaplacianSmoothing.forward:state") == 3 * c.P
+            assert guards.still_poisoned(g, "mesh_terms.py:_LaplacianSmoothing.forward:state") == 3 * c.P
 
 
 @pytest.mark.parametrize("name,hinted,template_grad", [("runs", True, True), ("runs", False, True), ("one-edge", True, False)])
@@ -139,8 +139,8 @@ def test_chamfer(name):
     plain, held = guards.run_case(fn, loose=("gx", "gy"))
     if name == "lengths":                    # the ALLOWED entries: the rows past the lengths are there and unwritten
         for g in held.values():
-            assert guards.still_poisoned(g, "ops.py:_Chamfer.forward:ix") == int((~live_x).sum())
-            assert guards.still_poisoned(g, "ops.py:_Chamfer.forward:iy") == int((~live_y).sum())
+            assert guards.still_poisoned(g, "mesh_terms.py:_Chamfer.forward:ix") == int((~live_x).sum())
+            assert guards.still_poisoned(g, "mesh_terms.py:_Chamfer.forward:iy") == int((~live_y).sum())
 
 
 def _chamfer_reference(c):

@@ -117,7 +117,7 @@ def test_sil_render(meshes, name):
     if name.startswith("empty_blocks"):      # the ALLOWED entry: its unwritten part is there, and the gradient ignores it
         assert plain["p2f"].shape == (N, H, H, K)
         for g in held.values():
-            assert guards.still_poisoned(g, "ops.py:_SilRender.forward:kth") > 0
+            assert guards.still_poisoned(g, "render.py:_SilRender.forward:kth") > 0
 
 
 @pytest.mark.parametrize("storage,H", [("f32", 40), ("f32", 37), ("f16", 37)])
@@ -173,7 +173,7 @@ def test_sil_then_tex_on_the_same_tensors(meshes, prefill, H):
         return dict(mask=mask, p2f=p2f + 0, imgs=imgs, sil=sil, p2=p2, gv=gv, gc=gc, ga=ga)
     plain, held = guards.run_case(fn)
     assert bool((plain["p2"] >= 0).any()) and bool((plain["ga"] != 0).any())
-    assert ("ops.py:_SilRender.forward:prefill" in held["A"].sites()) == prefill
+    assert ("render.py:_SilRender.forward:prefill" in held["A"].sites()) == prefill
 
 
 # ------------------------------------------------------------------------------------------------ texture

@@ -342,7 +342,7 @@ def test_texture_backward_gather_and_scatter_forms(meshes):
             faces = torch.from_numpy(f)[None].to(d).expand(n, -1, -1)
             got = {}
             for gather in (True, False):
-                ops.TEX_BWD_GATHER = gather
+                ops.TEX_BWD_GATHER[0] = gather
                 ops._SETUP.clear()
                 if share_ws:
                     ops.sil_render(tv, faces, tc, H)
@@ -354,7 +354,7 @@ def test_texture_backward_gather_and_scatter_forms(meshes):
                 np.testing.assert_allclose(got[gather], ref, rtol=1e-5, atol=1e-5)
             assert (got[True] != 0).sum() == (got[False] != 0).sum()
     finally:
-        ops.TEX_BWD_GATHER = True
+        ops.TEX_BWD_GATHER[0] = True
 
 
 def test_silhouette_nearest_plane_only(meshes):
