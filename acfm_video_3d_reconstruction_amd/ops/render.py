@@ -366,8 +366,10 @@ def _sil_apply(verts, faces, cams, gt, edt, img_size, K, blur, sigma, offset_z, 
     """_SilRender with the k_out / lazy resolution of both wrappers; -> (losses or None, mask, pix_to_face)."""
     f16 = _is_f16(storage)
     lazy = k_out == "lazy" and not f16 and K > 1
+    # (half storage: the default is the one plane it can write; a k_out the caller NAMES reaches the operator's check)
+    unnamed = k_out in (None, "lazy")
     losses, mask, p2f, vis, proj = _SilRender.apply(verts, faces, cams, gt, edt, img_size, K, blur, sigma, offset_z,
-                                                    1 if (f16 or lazy) else (K if k_out in (None, "lazy") else int(k_out)),
+                                                    1 if (lazy or (f16 and unnamed)) else (K if unnamed else int(k_out)),
                                                     f16, fused)
     if lazy:   # k_out="lazy": [N,H,H,K] whose slots 1.. are rendered on first use (LazyPixToFace)
         p2f = _lazy_pix_to_face(p2f, vis, _f32c(verts), expand_faces(faces, verts.shape[0]), _f32c(cams),
@@ -387,7 +389,8 @@ def sil_render(verts, faces, cams, img_size, K=SIL_K, blur=SIL_BLUR, sigma=SIL_S
     The visible-vertex bitmap the raster kernel produces on the side (vertices of every
     nearest face, = what bds_loss / optical_flow_loss derive from pix_to_face[..., 0]) rides
     along on the pix_to_face tensor object as `._acfm_vis`.
-    storage="f16": mask [N,H,H] float16, pix_to_face [N,H,H,1] int32 (BASELINE config 5); fp32 arithmetic."""
+    storage="f16": mask [N,H,H] float16, pix_to_face [N,H,H,1] int32 (BASELINE config 5); fp32 arithmetic.  That
+    plane is the default there; any other k_out given by number raises ValueError."""
     return _sil_apply(verts, faces, cams, None, None, img_size, K, blur, sigma, offset_z, k_out, storage, False)[1:]
 
 
