@@ -43,6 +43,11 @@ SIGNATURES = {
     "acfm_camera_mirror": (_i, [_vp, _i, _vp, _vp]),
     "acfm_camera_pipeline_tables": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
     "acfm_camera_pipeline_tables_backward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
+    "acfm_camera_pipeline_azel": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp]),
+    "acfm_camera_pipeline_azel_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp]),
+    "acfm_camera_pipeline_azel_tables": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp]),
+    "acfm_camera_pipeline_azel_tables_backward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f,
+                                                       _vp, _vp]),
     "acfm_camera_normalize": (_i, [_vp, _i, _vp, _vp]),
     "acfm_camera_normalize_backward": (_i, [_vp, _vp, _i, _vp, _vp]),
     "acfm_deform_solve_workspace_bytes": (_sz, [_i, _i]),

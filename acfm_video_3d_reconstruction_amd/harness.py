@@ -2,10 +2,13 @@
 (SURVEY section 8 rows a17, a20): camera decode / mirror / affine transforms and the
 hypothesis weighting.  Small differentiable device ops (the camera embeddings are optimised
 through them during pose warm-up, train_utils.py:186-213)."""
+import math
+
 import torch
 import torch.nn.functional as F
 
-from .pytorch3d_shim.transforms import matrix_to_quaternion, quaternion_multiply, standardize_quaternion
+from .pytorch3d_shim.transforms import (matrix_to_quaternion, quaternion_multiply, quaternion_raw_multiply,
+                                        standardize_quaternion)
 
 
 def decode_cameras(cam_emb, scale_lr_decay=1.0):
@@ -13,6 +16,25 @@ def decode_cameras(cam_emb, scale_lr_decay=1.0):
     (s = relu(decay*e0 + 1) + 1e-12, t = e1..2, q = normalize(e3..6))."""
     scales = F.relu(scale_lr_decay * cam_emb[..., :1] + 1) + 1e-12
     quats = F.normalize(cam_emb[..., 3:], dim=-1)
+    return torch.cat([scales, cam_emb[..., 1:3], quats], dim=-1)
+
+
+def decode_cameras_azel(cam_emb, scale_lr_decay=0.05, scale_bias=1.0, euler_range_deg=(30., 60., 60.)):
+    """The decode of --az_el_cam (multiframe/main.py:554-566 through MultiCamPredictor / Camera / QuatPredictorAzEle,
+    nnutils/mesh_net.py:310-385): embedding [...,6] = (scale, tx, ty, azimuth, elevation, cyclo-rotation) ->
+    (s = decay*e0 + bias, t = e1..2, q = q_cyc (x) (q_el (x) q_az)) with az = range*e3 about +y, el = pi - range*e4
+    about +x, cyc = range*e5 about +z; euler_range_deg = (az, el, cyc) in degrees.  No relu on the scale and no
+    renormalisation of q, as the reference has none.  float32 or float64, whichever cam_emb is."""
+    az_range, el_range, cyc_range = (math.pi / 180 * float(d) for d in euler_range_deg)
+    scales = scale_lr_decay * cam_emb[..., :1] + scale_bias
+    half_az = az_range * cam_emb[..., 3] / 2
+    half_el = (math.pi - el_range * cam_emb[..., 4]) / 2
+    half_cyc = cyc_range * cam_emb[..., 5] / 2
+    zero = torch.zeros_like(half_az)
+    q_az = torch.stack([torch.cos(half_az), zero, torch.sin(half_az), zero], -1)
+    q_el = torch.stack([torch.cos(half_el), torch.sin(half_el), zero, zero], -1)
+    q_cyc = torch.stack([torch.cos(half_cyc), zero, zero, torch.sin(half_cyc)], -1)
+    quats = quaternion_raw_multiply(q_cyc, quaternion_raw_multiply(q_el, q_az))
     return torch.cat([scales, cam_emb[..., 1:3], quats], dim=-1)
 
 

@@ -28,7 +28,8 @@ from .pytorch3d_shim.structures import Meshes
 DEFAULTS = dict(num_frames=2, num_guesses=8, num_lbs=15, kp_loss_wt=0., of_loss_wt=1., mask_loss_wt=1.,
                 rigid_wt=0.5, deform_reg_wt=1., handle_deform_reg_wt=0., boundaries_reg_wt=1., edt_reg_wt=0.1,
                 bdt_reg_wt=2., triangle_reg_wt=0.1, tex_loss_wt=.5, scale_lr_decay=0.05, optimize_deform=False,
-                optimize_deform_lr=100., drop_hypothesis=False, texture=False, cam_loss_wt=2., deform_loss_wt=2.)
+                optimize_deform_lr=100., drop_hypothesis=False, texture=False, cam_loss_wt=2., deform_loss_wt=2.,
+                az_el_cam=False, scale_bias=1.0, az_euler_range=30., el_euler_range=60., cyc_euler_range=60.)
 
 
 def texture_cycle_loss(textures, num_frames):
@@ -67,15 +68,26 @@ class MultiframeStep(nn.Module):
         self.prior_stream, self._prior_s = bool(prior_stream), None   # mesh priors beside the raster kernels (forward)
         G = self.opts.num_guesses
         self.num_cameras = G          # embeddings; opts.num_guesses may later drop below it (train_utils.py:236-241)
-        q0 = _y_rotation_quats(G)
         self.cameras = nn.ModuleList()
-        for g in range(G):                                       # mesh_net.py:436-444
-            emb = nn.Embedding(num_training_frames, 7)
-            with torch.no_grad():
-                emb.weight[:, 0] = 0
-                emb.weight[:, 1:3] = (torch.rand(2) - 0.5) * 0.1
-                emb.weight[:, 3:] = q0[g] + 0.1 * torch.rand(4)
-            self.cameras.append(emb)
+        if self.opts.az_el_cam:                                  # mesh_net.py:405-416
+            if G < 2:
+                raise ValueError("az_el_cam: num_guesses must be at least 2 (hypothesis g starts at the azimuth "
+                                 "g / (num_guesses - 1)), got %d" % G)
+            for g in range(G):
+                emb = nn.Embedding(num_training_frames, 6)
+                with torch.no_grad():
+                    emb.weight.zero_()
+                    emb.weight[:, 3] = g / (G - 1)
+                self.cameras.append(emb)
+        else:
+            q0 = _y_rotation_quats(G)
+            for g in range(G):                                   # mesh_net.py:436-444
+                emb = nn.Embedding(num_training_frames, 7)
+                with torch.no_grad():
+                    emb.weight[:, 0] = 0
+                    emb.weight[:, 1:3] = (torch.rand(2) - 0.5) * 0.1
+                    emb.weight[:, 3:] = q0[g] + 0.1 * torch.rand(4)
+                self.cameras.append(emb)
         self.prob_embeddings = nn.Embedding(num_training_frames, G)
         self.prob_embeddings.weight.data.fill_(1)               # mesh_net.py:445-446
         self.deform_emb = nn.Embedding(num_training_frames, self.opts.num_lbs * 3)
@@ -121,19 +133,29 @@ class MultiframeStep(nn.Module):
 
     # ------------------------------------------------------------------ cameras (main.py:551-584)
     def hypothesis_cameras(self, frames_idx, mirror_flag, transforms, detach=False, selected=None):
-        G = self.opts.num_guesses
+        o = self.opts
+        G = o.num_guesses
         w0 = self.cameras[0].weight
+        euler = (o.az_euler_range, o.el_euler_range, o.cyc_euler_range)
         if w0.is_cuda:   # look-ups + stack / top-k gather + decode + mirror + transform fused (csrc/acfm_camera.hip)
             from . import ops
-            cam_pred = ops.camera_pipeline_tables([emb.weight for emb in self.cameras], frames_idx, mirror_flag,
-                                                  transforms, self.opts.scale_lr_decay, num_guesses=G,
-                                                  selected=selected)
+            tables = [emb.weight for emb in self.cameras]
+            if o.az_el_cam:
+                cam_pred = ops.camera_pipeline_azel_tables(tables, frames_idx, mirror_flag, transforms, o.scale_lr_decay,
+                                                           o.scale_bias, euler, num_guesses=G, selected=selected)
+            else:
+                cam_pred = ops.camera_pipeline_tables(tables, frames_idx, mirror_flag, transforms, o.scale_lr_decay,
+                                                      num_guesses=G, selected=selected)
             return cam_pred.detach() if detach else cam_pred
-        cams = torch.stack([emb(frames_idx) for emb in self.cameras])          # [G_all,B,T,7]
-        if selected is not None:                                               # main.py:568-570
-            cams = torch.gather(cams, 0, selected[..., None].expand(-1, -1, -1, 7))
-        cams = cams.reshape(G, -1, 7)          # (host tensors: the reference's chain of torch ops, harness.py)
-        cam_pred = harness.decode_cameras(cams, self.opts.scale_lr_decay).reshape(-1, 7)
+        W = w0.shape[1]
+        cams = torch.stack([emb(frames_idx) for emb in self.cameras])          # [G_all,B,T,W]
+        if selected is not None:       # main.py:568-570 (:560-562 gathers the decoded rows: the decode is per row)
+            cams = torch.gather(cams, 0, selected[..., None].expand(-1, -1, -1, W))
+        cams = cams.reshape(G, -1, W)          # (host tensors: the reference's chain of torch ops, harness.py)
+        if o.az_el_cam:
+            cam_pred = harness.decode_cameras_azel(cams, o.scale_lr_decay, o.scale_bias, euler).reshape(-1, 7)
+        else:
+            cam_pred = harness.decode_cameras(cams, o.scale_lr_decay).reshape(-1, 7)
         cam_pred = harness.mirror_cameras(cam_pred, None, mirror_flag.repeat(G)[:, None])
         cam_pred = harness.transform_cameras(cam_pred, None, transforms.repeat(G, 1))
         return cam_pred.detach() if detach else cam_pred

@@ -28,8 +28,9 @@ from .render import (LazyPixToFace, PREFILL_TEX, SIL_BLUR, SIL_K, SIL_SIGMA, TEX
                      invalidate_setups, share_setup, sil_render, sil_render_losses, tex_render, tex_render_mse,
                      vertex_color_render, visible_vertices)
 from .geometry import (SOLVE_INFO_HANDOFF, _CameraNormalize, _CameraPipeline, _CameraPipelineTables, _DeformApply,
-                       _DeformSolve, _PRESOLVE_SINKS, _Project, _ProjectXY, _SOLVE_PENDING, camera_mirror,
-                       camera_normalize, camera_pipeline, camera_pipeline_tables, decode_solve_info, deform_apply,
+                       _DeformSolve, _PRESOLVE_SINKS, _Project, _ProjectXY, _SOLVE_PENDING, _azel_params,
+                       _check_table_ids, camera_mirror, camera_normalize, camera_pipeline, camera_pipeline_azel,
+                       camera_pipeline_azel_tables, camera_pipeline_tables, decode_solve_info, deform_apply,
                        deform_solve, drop_presolve_sink, project, project_xy, register_presolve_sink, solve_status)
 from .flow import (_Correlation, _DeformConv2d, _FLOW_TRAINABLE, _FORWARD_ONLY, _OFLoss, _correlation_args,
                    _correlation_forward, _dconv_args, _dconv_forward, _once, correlation, deform_conv2d, of_loss)

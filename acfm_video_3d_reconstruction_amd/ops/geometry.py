@@ -1,5 +1,6 @@
 """Projection, deformation (apply and solve) and cameras."""
 import ctypes
+import math
 
 import torch
 
@@ -235,12 +236,15 @@ def deform_solve(L, lbs_logits, check=False):
 
 
 # ------------------------------------------------------------------------------ cameras
+# The two embeddings -- (scale, trans, quaternion), 7 floats, and the (scale, trans, azimuth, elevation, cyclo-rotation)
+# of --az_el_cam, 6 floats -- share these bindings: `entry` names the C entry point (its backward is entry + "_backward"),
+# W the embedding width, params the decode parameters the entry point takes after (R, N).
 class _CameraPipeline(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, emb, mirror_flag, transforms, decay):
+    def forward(ctx, emb, mirror_flag, transforms, entry, W, params):
         _lib.require_gpu(emb, mirror_flag, transforms)
         e = _f32c(emb)
-        R = e.numel() // 7
+        R = e.numel() // W
         mf = mirror_flag.detach().reshape(-1).to(torch.int64).contiguous()
         tr = _f32c(transforms).reshape(-1, 4)
         N = mf.numel()
@@ -248,37 +252,57 @@ class _CameraPipeline(torch.autograd.Function):
             raise ValueError("camera rows %d must be a multiple of the %d frames (transforms %s)"
                              % (R, N, tuple(tr.shape)))
         out = torch.empty((R, 7), dtype=torch.float32, device=e.device)
-        _lib.call("acfm_camera_pipeline", e.device, _lib.ptr(e), _lib.ptr(mf), _lib.ptr(tr), R, N, float(decay),
-                  _lib.ptr(out))
+        _lib.call(entry, e.device, _lib.ptr(e), _lib.ptr(mf), _lib.ptr(tr), R, N, *params, _lib.ptr(out))
         ctx.save_for_backward(e, mf, tr)
-        ctx.decay = float(decay)
+        ctx.cfg = (entry, W, params)
         return out
 
     @staticmethod
     def backward(ctx, g):
         e, mf, tr = ctx.saved_tensors
-        R, N = e.numel() // 7, mf.numel()
+        entry, W, params = ctx.cfg
+        R, N = e.numel() // W, mf.numel()
         g = _f32c(g)
         ge = torch.empty_like(e)
-        _lib.call("acfm_camera_pipeline_backward", e.device, _lib.ptr(e), _lib.ptr(mf), _lib.ptr(tr), _lib.ptr(g), R, N,
-                  ctx.decay, _lib.ptr(ge))
-        return ge, None, None, None
+        _lib.call(entry + "_backward", e.device, _lib.ptr(e), _lib.ptr(mf), _lib.ptr(tr), _lib.ptr(g), R, N, *params,
+                  _lib.ptr(ge))
+        return ge, None, None, None, None, None
 
 
 def camera_pipeline(cam_emb, mirror_flag, transforms, scale_lr_decay=1.0):
     """Camera embeddings [G,N,7] (or [R,7], row r of frame r % N) -> cameras [R,7]: decode, mirror by
     the per-frame flag [N], crop/scale transform [N,4] (multiframe/main.py:551-584) in one kernel."""
-    return _CameraPipeline.apply(cam_emb, mirror_flag, transforms, scale_lr_decay)
+    return _CameraPipeline.apply(cam_emb, mirror_flag, transforms, "acfm_camera_pipeline", 7, (float(scale_lr_decay),))
+
+
+def _azel_params(scale_lr_decay, scale_bias, euler_range_deg):
+    """-> (decay, bias, az, el, cyc) as the kernels take them: the three ranges converted to radians, once, here."""
+    rng = tuple(float(d) for d in euler_range_deg)
+    if len(rng) != 3:
+        raise ValueError("euler_range_deg must be (az, el, cyc) in degrees, got %r" % (euler_range_deg,))
+    return (float(scale_lr_decay), float(scale_bias)) + tuple(math.pi / 180 * d for d in rng)
+
+
+def camera_pipeline_azel(cam_emb, mirror_flag, transforms, scale_lr_decay=0.05, scale_bias=1.0,
+                         euler_range_deg=(30., 60., 60.)):
+    """Az/el camera embeddings [G,N,6] (or [R,6], row r of frame r % N; columns scale, tx, ty, azimuth, elevation,
+    cyclo-rotation) -> cameras [R,7]: the decode of --az_el_cam (multiframe/main.py:554-566, mesh_net.py:310-385:
+    s = decay*e0 + bias, q = q_cyc (x) q_el (x) q_az from the angles (range*e3, pi - range*e4, range*e5)), then the
+    mirror and the crop/scale transform of camera_pipeline, in one kernel each way.  euler_range_deg = (az, el, cyc) in
+    degrees, as the reference's --az_euler_range / --el_euler_range / --cyc_euler_range are."""
+    return _CameraPipeline.apply(cam_emb, mirror_flag, transforms, "acfm_camera_pipeline_azel", 6,
+                                 _azel_params(scale_lr_decay, scale_bias, euler_range_deg))
 
 
 class _CameraPipelineTables(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, frames_idx, selected, mirror_flag, transforms, decay, G, *tables):
+    def forward(ctx, frames_idx, selected, mirror_flag, transforms, entry, W, params, G, *tables):
         _lib.require_gpu(frames_idx, mirror_flag, transforms, *tables)
+        what = entry[5:]
         ts = [_f32c(t) for t in tables]
         F = ts[0].shape[0]
-        if not 1 <= len(ts) <= 32 or any(t.dim() != 2 or tuple(t.shape) != (F, 7) for t in ts):
-            raise ValueError("camera_pipeline_tables: 1..32 embedding tables [frames, 7] of one size")
+        if not 1 <= len(ts) <= 32 or any(t.dim() != 2 or tuple(t.shape) != (F, W) for t in ts):
+            raise ValueError("%s: 1..32 embedding tables [frames, %d] of one size" % (what, W))
         fi = frames_idx.detach().reshape(-1).to(torch.int64).contiguous()
         mf = mirror_flag.detach().reshape(-1).to(torch.int64).contiguous()
         tr = _f32c(transforms).reshape(-1, 4)
@@ -287,31 +311,40 @@ class _CameraPipelineTables(torch.autograd.Function):
         sel = None if selected is None else selected.detach().reshape(-1).to(torch.int64).contiguous()
         if mf.numel() != N or tr.shape[0] != N or (sel is not None and sel.numel() != R) or \
                 (sel is None and int(G) > len(ts)):
-            raise ValueError("camera_pipeline_tables: %d frames, mirror flags %d, transforms %s, G = %d, %d tables"
-                             % (N, mf.numel(), tuple(tr.shape), G, len(ts)))
+            raise ValueError("%s: %d frames, mirror flags %d, transforms %s, G = %d, %d tables"
+                             % (what, N, mf.numel(), tuple(tr.shape), G, len(ts)))
         out = torch.empty((R, 7), dtype=torch.float32, device=ts[0].device)
         ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        _lib.call("acfm_camera_pipeline_tables", out.device, ptrs, len(ts), F, _lib.ptr(fi), _lib.ptr(sel), _lib.ptr(mf),
-                  _lib.ptr(tr), R, N, float(decay), _lib.ptr(out))
+        _lib.call(entry, out.device, ptrs, len(ts), F, _lib.ptr(fi), _lib.ptr(sel), _lib.ptr(mf), _lib.ptr(tr), R, N,
+                  *params, _lib.ptr(out))
         ctx.save_for_backward(fi, mf, tr, *ts) if sel is None else ctx.save_for_backward(fi, mf, tr, sel, *ts)
-        ctx.cfg = (float(decay), R, N, F, len(ts), sel is not None)
+        ctx.cfg = (entry, W, params, R, N, F, len(ts), sel is not None)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        decay, R, N, F, nt, has_sel = ctx.cfg
+        entry, W, params, R, N, F, nt, has_sel = ctx.cfg
         saved = ctx.saved_tensors
         fi, mf, tr = saved[:3]
         sel = saved[3] if has_sel else None
         ts = saved[4:] if has_sel else saved[3:]
         g = _f32c(g)
-        need = ctx.needs_input_grad[6:]
-        outs = [torch.empty((F, 7), dtype=torch.float32, device=g.device) if need[i] else None for i in range(nt)]
+        need = ctx.needs_input_grad[8:]
+        outs = [torch.empty((F, W), dtype=torch.float32, device=g.device) if need[i] else None for i in range(nt)]
         ptrs = (ctypes.c_void_p * nt)(*[t.data_ptr() for t in ts])
         gptrs = (ctypes.c_void_p * nt)(*[(o.data_ptr() if o is not None else None) for o in outs])
-        _lib.call("acfm_camera_pipeline_tables_backward", g.device, ptrs, nt, F, _lib.ptr(fi), _lib.ptr(sel), _lib.ptr(mf),
-                  _lib.ptr(tr), _lib.ptr(g), R, N, decay, gptrs)
-        return (None,) * 6 + tuple(outs)
+        _lib.call(entry + "_backward", g.device, ptrs, nt, F, _lib.ptr(fi), _lib.ptr(sel), _lib.ptr(mf), _lib.ptr(tr),
+                  _lib.ptr(g), R, N, *params, gptrs)
+        return (None,) * 8 + tuple(outs)
+
+
+def _check_table_ids(what, tables, frames_idx, selected):
+    nf = tables[0].shape[0]
+    lo, hi = int(frames_idx.min()), int(frames_idx.max())
+    if lo < 0 or hi >= nf:
+        raise IndexError("%s: frames_idx in [%d, %d] outside the %d rows of the embedding tables" % (what, lo, hi, nf))
+    if selected is not None and (int(selected.min()) < 0 or int(selected.max()) >= len(tables)):
+        raise IndexError("%s: selected hypothesis outside the %d tables" % (what, len(tables)))
 
 
 def camera_pipeline_tables(tables, frames_idx, mirror_flag, transforms, scale_lr_decay=1.0, num_guesses=None,
@@ -325,14 +358,23 @@ def camera_pipeline_tables(tables, frames_idx, mirror_flag, transforms, scale_lr
     (one synchronisation: for data-loader batches, not inside a captured step) and raises IndexError."""
     G = len(tables) if num_guesses is None else int(num_guesses)
     if check:
-        nf = tables[0].shape[0]
-        lo, hi = int(frames_idx.min()), int(frames_idx.max())
-        if lo < 0 or hi >= nf:
-            raise IndexError("camera_pipeline_tables: frames_idx in [%d, %d] outside the %d rows of the embedding tables"
-                             % (lo, hi, nf))
-        if selected is not None and (int(selected.min()) < 0 or int(selected.max()) >= len(tables)):
-            raise IndexError("camera_pipeline_tables: selected hypothesis outside the %d tables" % len(tables))
-    return _CameraPipelineTables.apply(frames_idx, selected, mirror_flag, transforms, scale_lr_decay, G, *tables)
+        _check_table_ids("camera_pipeline_tables", tables, frames_idx, selected)
+    return _CameraPipelineTables.apply(frames_idx, selected, mirror_flag, transforms, "acfm_camera_pipeline_tables", 7,
+                                       (float(scale_lr_decay),), G, *tables)
+
+
+def camera_pipeline_azel_tables(tables, frames_idx, mirror_flag, transforms, scale_lr_decay=0.05, scale_bias=1.0,
+                                euler_range_deg=(30., 60., 60.), num_guesses=None, selected=None, check=False):
+    """camera_pipeline_tables for the az/el embedding tables ([frames,6] each, mesh_net.py:405-416): the look-ups, the
+    stack / top-k gather and the camera_pipeline_azel chain in one kernel each way.  Row g*N + n reads
+    tables[selected[g, n] if given else g][frames_idx[n]]; the backward returns dense [frames,6] gradients, every cell
+    summed in a fixed order.  Out-of-range frames_idx / selected give that row a NaN camera and no gradient (never an
+    out-of-bounds access); check=True validates both on the host first (one synchronisation) and raises IndexError."""
+    G = len(tables) if num_guesses is None else int(num_guesses)
+    if check:
+        _check_table_ids("camera_pipeline_azel_tables", tables, frames_idx, selected)
+    return _CameraPipelineTables.apply(frames_idx, selected, mirror_flag, transforms, "acfm_camera_pipeline_azel_tables",
+                                       6, _azel_params(scale_lr_decay, scale_bias, euler_range_deg), G, *tables)
 
 
 def camera_mirror(cams):

@@ -231,6 +231,32 @@ int acfm_camera_pipeline_tables_backward(const void* const* tables, int n_tables
                                          const int64_t* selected, const int64_t* mirror_flag, const float* transforms,
                                          const float* grad_cams, int R, int N, float scale_lr_decay,
                                          void* const* grad_tables, void* stream);
+/* the four entry points above for the 6-float embedding of --az_el_cam (multiframe/main.py:442-450, 554-566;
+ * nnutils/mesh_net.py:310-385, 405-422): emb / tables / grad_emb / grad_tables have 6 columns (scale, tx, ty, azimuth,
+ * elevation, cyclo-rotation), everything else is as above.  Per row, with the ranges in RADIANS:
+ *   s = scale_lr_decay*e0 + scale_bias (no relu: a negative scale passes through), t = e1..2;
+ *   az = az_range*e3, el = pi - el_range*e4, cyc = cyc_range*e5;
+ *   q = q_cyc (x) (q_el (x) q_az), q_az = (cos az/2, 0, sin az/2, 0), q_el = (cos el/2, sin el/2, 0, 0),
+ *   q_cyc = (cos cyc/2, 0, 0, sin cyc/2): Hamilton products on (w, x, y, z), not renormalised;
+ *   then the same mirror blend and transform blend.  The parameters are per call; the library keeps none.
+ * One launch per call, the tables' backward included: it fills the dense gradients cell by cell, each the sum of the
+ * batch rows that looked it up in a fixed order (no atomics, no zero fill in front; bit-reproducible). */
+int acfm_camera_pipeline_azel(const float* emb, const int64_t* mirror_flag, const float* transforms, int R, int N,
+                              float scale_lr_decay, float scale_bias, float az_range, float el_range, float cyc_range,
+                              float* cams, void* stream);
+int acfm_camera_pipeline_azel_backward(const float* emb, const int64_t* mirror_flag, const float* transforms,
+                                       const float* grad_cams, int R, int N, float scale_lr_decay, float scale_bias,
+                                       float az_range, float el_range, float cyc_range, float* grad_emb, void* stream);
+int acfm_camera_pipeline_azel_tables(const void* const* tables, int n_tables, int n_frames, const int64_t* frames_idx,
+                                     const int64_t* selected, const int64_t* mirror_flag, const float* transforms, int R,
+                                     int N, float scale_lr_decay, float scale_bias, float az_range, float el_range,
+                                     float cyc_range, float* cams, void* stream);
+int acfm_camera_pipeline_azel_tables_backward(const void* const* tables, int n_tables, int n_frames,
+                                              const int64_t* frames_idx, const int64_t* selected,
+                                              const int64_t* mirror_flag, const float* transforms,
+                                              const float* grad_cams, int R, int N, float scale_lr_decay,
+                                              float scale_bias, float az_range, float el_range, float cyc_range,
+                                              void* const* grad_tables, void* stream);
 
 /* cam = (s, tx, ty, q / max(|q|, 1e-12)) of a raw [N,7] camera parameter: the per-iteration
  * torch.cat([scale, trans, F.normalize(quat)]) of the refinement loop (nnutils/predictor.py:301-308). */
