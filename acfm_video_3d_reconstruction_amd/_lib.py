@@ -13,6 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("ACFM_LIB") or os.path.join(_HERE, "libacfm_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
+ABI_VERSION = 2000  # acfm_version() of the header these signatures mirror; lib() refuses any other build
+
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 
 # name -> (restype, argtypes); must list every symbol of include/acfm_hip.h
@@ -34,10 +36,8 @@ SIGNATURES = {
     "acfm_deform_conv2d_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "acfm_deform_conv2d_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "acfm_deform_conv2d_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "acfm_of_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "acfm_of_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_of_loss_shared": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "acfm_of_loss_shared_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_of_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "acfm_of_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "acfm_camera_pipeline": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
     "acfm_camera_pipeline_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
     "acfm_camera_mirror": (_i, [_vp, _i, _vp, _vp]),
@@ -58,21 +58,13 @@ SIGNATURES = {
     "acfm_raster_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "acfm_stream_capture_id": (_i, [_vp, _vp]),
     "acfm_sil_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp,
-                              _sz, _vp, _vp]),
-    "acfm_sil_forward_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp,
-                                 _sz, _vp, _vp, _vp]),
-    "acfm_sil_backward_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp,
-                                  _sz, _i, _vp, _vp, _vp]),
-    "acfm_sil_loss_forward_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp,
-                                      _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
-    "acfm_sil_loss_backward_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _f, _f, _vp,
-                                       _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+                              _sz, _vp, _vp, _vp]),
     "acfm_sil_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp,
-                               _sz, _i, _vp, _vp]),
+                               _sz, _i, _vp, _vp, _vp]),
     "acfm_sil_loss_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp,
-                                   _vp, _vp, _vp, _sz, _vp, _vp]),
+                                   _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "acfm_sil_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _f, _f, _vp,
-                                    _vp, _vp, _sz, _i, _vp, _vp]),
+                                    _vp, _vp, _sz, _i, _vp, _vp, _vp]),
     "acfm_hard_raster": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "acfm_rasterize_fragments_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "acfm_rasterize_fragments": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
@@ -106,15 +98,12 @@ SIGNATURES = {
     "acfm_texture_cycle_scratch_floats": (_sz, [_i, _i, _i, _i]),
     "acfm_texture_cycle": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "acfm_texture_cycle_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_mask_losses": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "acfm_loss_partial_floats": (_sz, [_i, _i, _i]),
-    "acfm_mask_losses_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "acfm_tex_mse_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "acfm_bds_loss_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "acfm_mask_losses": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "acfm_step_losses_ws": (_sz, [_i, _i, _i, _i, _vp]),
     "acfm_step_losses_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "acfm_mask_losses_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "acfm_tex_mse": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "acfm_tex_mse": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "acfm_tex_mse_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "acfm_cot_laplacian": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "acfm_laplacian_smoothing_state_floats": (_sz, [_i, _i]),
@@ -126,10 +115,8 @@ SIGNATURES = {
     "acfm_edt": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "acfm_boundaries": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "acfm_visible_vertices": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_bds_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "acfm_bds_loss_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_bds_loss_sel_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "acfm_bds_loss_sel_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_bds_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "acfm_bds_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "acfm_boundary_subset": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "acfm_chamfer_partial_floats": (_sz, [_i, _i, _i]),
     "acfm_chamfer": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -143,7 +130,7 @@ SIGNATURES = {
     "acfm_uv_atlas_taps": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "acfm_uv_atlas_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "acfm_geodesic_lds_bytes": (_sz, [_i, _i, _i]),
-    "acfm_geodesic_distances": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "acfm_geodesic_distances": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "acfm_geodesic_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "acfm_geodesic_distances_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "acfm_lpips_input_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
@@ -185,6 +172,12 @@ def lib():
                 "libacfm_hip.so is missing (%s). Build it with `python -c \"import __graft_entry__ "
                 "as g; g.build()\"` or `make -C %s`. There is no CPU fallback." % (SO_PATH, CSRC))
         handle = ctypes.CDLL(SO_PATH)
+        handle.acfm_version.restype, handle.acfm_version.argtypes = SIGNATURES["acfm_version"]
+        found = handle.acfm_version()
+        if found != ABI_VERSION:   # before any other symbol: same names, other argument lists
+            raise RuntimeError(
+                "%s reports acfm_version() = %d, this package binds version %d of include/acfm_hip.h: the library is "
+                "a build of another tree. Rebuild it with `make -C %s`." % (SO_PATH, found, ABI_VERSION, CSRC))
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype, fn.argtypes = res, args
@@ -314,7 +307,7 @@ class SilExtras(ctypes.Structure):
 
 
 def sil_extras(proj_xy=None, grad_proj_xy=None, prefill=None):
-    """-> (ctypes pointer, the structure to keep alive) for the `_ex` silhouette entry points; tensors or None."""
+    """-> (ctypes pointer, the structure to keep alive) for the `extras` of the silhouette entry points; tensors or None."""
     p = lambda t: None if t is None else t.data_ptr()
     pf = prefill or (None, None, None, None)
     e = SilExtras(p(proj_xy), p(grad_proj_xy), p(pf[0]), p(pf[1]), p(pf[2]), p(pf[3]))

@@ -639,7 +639,7 @@ __global__ __launch_bounds__(256) void k_tex_cycle_bwd(const float* __restrict__
   grad[src] = g * go[0] * scale;
 }
 
-// Scratch of the *_ws entry points: `tickets`, one word per mesh, zero between launches; `partials`, [N][nblk][C]
+// Scratch of the three per-mesh loss sums: `tickets`, one word per mesh, zero between launches; `partials`, [N][nblk][C]
 // floats of any contents (sized for the most workgroups a launch of that shape can have).
 static inline int loss_blocks(int which, int n) {
   return which == ACFM_LOSS_BDS ? (n + 63) / 64 : (n + PIX_PER_BLOCK - 1) / PIX_PER_BLOCK;
@@ -669,8 +669,8 @@ size_t acfm_loss_partial_floats(int which, int N, int n) {
   return loss_partial_floats(which, N, n);
 }
 
-int acfm_mask_losses_ws(const float* mask, const float* gt, const float* edt, int N, int HW, int ref_batch,
-                        float* out, uint32_t* tickets, float* partials, size_t partial_floats, void* stream) {
+int acfm_mask_losses(const float* mask, const float* gt, const float* edt, int N, int HW, int ref_batch,
+                     float* out, uint32_t* tickets, float* partials, size_t partial_floats, void* stream) {
   if (!mask || !out || N <= 0 || N > 65535 || HW <= 0 || ref_batch <= 0 || N % ref_batch != 0) return ACFM_E_BADARG;
   RowScratch sc;
   if (const int rc = row_scratch(ACFM_LOSS_MASK, N, HW, tickets, partials, partial_floats, sc)) return rc;
@@ -684,10 +684,6 @@ int acfm_mask_losses_ws(const float* mask, const float* gt, const float* edt, in
     hipLaunchKernelGGL(k_mask_losses<PIX_PER_BLOCK>, dim3(chunks, N), dim3(LTPB), 0, st, mask, gt, edt, HW, ref_batch, out, sc);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
-}
-int acfm_mask_losses(const float* mask, const float* gt, const float* edt, int N, int HW, int ref_batch,
-                     float* out, void* stream) {
-  return acfm_mask_losses_ws(mask, gt, edt, N, HW, ref_batch, out, nullptr, nullptr, 0, stream);
 }
 
 int acfm_mask_losses_backward(const float* mask, const float* gt, const float* edt,
@@ -703,8 +699,8 @@ int acfm_mask_losses_backward(const float* mask, const float* gt, const float* e
   return ACFM_OK;
 }
 
-int acfm_tex_mse_ws(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,
-                    float* out, uint32_t* tickets, float* partials, size_t partial_floats, void* stream) {
+int acfm_tex_mse(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,
+                 float* out, uint32_t* tickets, float* partials, size_t partial_floats, void* stream) {
   if (!tex || !img || !mask || !out || N <= 0 || N > 65535 || HW <= 0 || ref_batch <= 0 || N % ref_batch != 0)
     return ACFM_E_BADARG;
   RowScratch sc;
@@ -719,10 +715,6 @@ int acfm_tex_mse_ws(const float* tex, const float* img, const float* mask, int N
     hipLaunchKernelGGL(k_tex_mse<PIX_PER_BLOCK>, dim3(chunks, N), dim3(LTPB), 0, st, tex, img, mask, HW, ref_batch, out, sc);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
-}
-int acfm_tex_mse(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,
-                 float* out, void* stream) {
-  return acfm_tex_mse_ws(tex, img, mask, N, HW, ref_batch, out, nullptr, nullptr, 0, stream);
 }
 
 int acfm_tex_mse_backward(const float* tex, const float* img, const float* mask, const float* grad_out,
@@ -787,7 +779,7 @@ int acfm_step_losses_forward(const acfm_step_mask_job* mask, const acfm_step_tex
               S <= 0 || bds->ref_batch <= 0 || N % bds->ref_batch != 0 ||
               (bds->sel && bds->rows != 1 && bds->rows != bds->ref_batch)))
     return ACFM_E_BADARG;
-  const size_t lds = bds ? sizeof(float) * 3 * (size_t)bds->V : 0;   // as acfm_bds_loss_ws
+  const size_t lds = bds ? sizeof(float) * 3 * (size_t)bds->V : 0;   // as acfm_bds_loss
   if (lds > 150 * 1024) return ACFM_E_BADARG;
   if (partial_floats < acfm_step_losses_ws(N, mask ? mask->HW : 0, tex ? tex->HW : 0, S, nullptr)) return ACFM_E_WORKSPACE;
   TailBds B = {};
@@ -931,82 +923,52 @@ int acfm_visible_vertices(const int64_t* pix_to_face, const int64_t* faces, int 
   return ACFM_OK;
 }
 
-int acfm_bds_loss_ws(const float* verts_xy, const float* bds, const uint8_t* vis, int N, int V, int P,
-                     int ref_batch, float* loss, int32_t* argmin, uint32_t* tickets, float* partials,
-                     size_t partial_floats, void* stream) {
+int acfm_bds_loss(const float* verts_xy, const float* bds, const uint8_t* vis, const int32_t* sel, int N, int V,
+                  int P, int ref_batch, int rows, int S, float* loss, int32_t* argmin, uint32_t* tickets,
+                  float* partials, size_t partial_floats, void* stream) {
   if (!verts_xy || !bds || !vis || !loss || !argmin || N <= 0 || N > 65535 || V <= 0 || P <= 0 || ref_batch <= 0 ||
-      N % ref_batch != 0)
+      N % ref_batch != 0 || (sel && (S <= 0 || (rows != 1 && rows != ref_batch))))
     return ACFM_E_BADARG;
   const size_t lds = sizeof(float) * 3 * (size_t)V;   // (x, y) per vertex + the index a packed vertex came from
   if (lds > 150 * 1024) return ACFM_E_BADARG;
+  const int n = sel ? S : P;   // points per mesh
   RowScratch sc;
-  if (const int rc = row_scratch(ACFM_LOSS_BDS, N, P, tickets, partials, partial_floats, sc)) return rc;
+  if (const int rc = row_scratch(ACFM_LOSS_BDS, N, n, tickets, partials, partial_floats, sc)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (!sc.tickets && zero_async(loss, sizeof(float) * (size_t)N, st) != ACFM_OK) return ACFM_E_LAUNCH;
   ProfScope ps(ACFM_PROF_BDS, st);
-  hipLaunchKernelGGL(k_bds_loss, dim3((P + 63) / 64, N), dim3(LTPB), lds, st, verts_xy, bds, vis,
-                     V, P, ref_batch, loss, argmin, sc);
+  if (sel)
+    hipLaunchKernelGGL(k_bds_loss_sel, dim3((n + 63) / 64, N), dim3(LTPB), lds, st, verts_xy, bds, vis,
+                       V, P, ref_batch, loss, argmin, sc, sel, rows, S);
+  else
+    hipLaunchKernelGGL(k_bds_loss, dim3((n + 63) / 64, N), dim3(LTPB), lds, st, verts_xy, bds, vis,
+                       V, P, ref_batch, loss, argmin, sc);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
 }
-int acfm_bds_loss(const float* verts_xy, const float* bds, const uint8_t* vis, int N, int V, int P,
-                  int ref_batch, float* loss, int32_t* argmin, void* stream) {
-  return acfm_bds_loss_ws(verts_xy, bds, vis, N, V, P, ref_batch, loss, argmin, nullptr, nullptr, 0, stream);
-}
 
-int acfm_bds_loss_backward(const float* verts_xy, const float* bds, const int32_t* argmin,
-                           const float* grad_loss, int N, int V, int P, int ref_batch, float* grad_verts_xy,
-                           void* stream) {
+int acfm_bds_loss_backward(const float* verts_xy, const float* bds, const int32_t* sel, const int32_t* argmin,
+                           const float* grad_loss, int N, int V, int P, int ref_batch, int rows, int S,
+                           float* grad_verts_xy, void* stream) {
   if (!verts_xy || !bds || !argmin || !grad_loss || !grad_verts_xy || N <= 0 || N > 65535 || V <= 0 ||
-      P <= 0 || ref_batch <= 0 || N % ref_batch != 0)
+      P <= 0 || ref_batch <= 0 || N % ref_batch != 0 || (sel && (S <= 0 || (rows != 1 && rows != ref_batch))))
     return ACFM_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = sizeof(float) * 2 * (size_t)V;
   if (lds > 150 * 1024) return ACFM_E_BADARG;
   ProfScope ps(ACFM_PROF_BDS_BWD, st);
-  hipLaunchKernelGGL(k_bds_loss_bwd, dim3(N), dim3(256), lds, st, verts_xy, bds, argmin,
-                     grad_loss, V, P, ref_batch, grad_verts_xy);
+  if (sel)
+    hipLaunchKernelGGL(k_bds_loss_sel_bwd, dim3(N), dim3(256), lds, st, verts_xy, bds, argmin, grad_loss, V, P,
+                       ref_batch, grad_verts_xy, sel, rows, S);
+  else
+    hipLaunchKernelGGL(k_bds_loss_bwd, dim3(N), dim3(256), lds, st, verts_xy, bds, argmin,
+                       grad_loss, V, P, ref_batch, grad_verts_xy);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
 }
 
-int acfm_bds_loss_sel_ws(const float* verts_xy, const float* bds, const uint8_t* vis, const int32_t* sel, int N, int V,
-                         int P, int ref_batch, int rows, int S, float* loss, int32_t* argmin, uint32_t* tickets,
-                         float* partials, size_t partial_floats, void* stream) {
-  if (!verts_xy || !bds || !vis || !sel || !loss || !argmin || N <= 0 || N > 65535 || V <= 0 || P <= 0 || S <= 0 ||
-      ref_batch <= 0 || N % ref_batch != 0 || (rows != 1 && rows != ref_batch))
-    return ACFM_E_BADARG;
-  const size_t lds = sizeof(float) * 3 * (size_t)V;
-  if (lds > 150 * 1024) return ACFM_E_BADARG;
-  RowScratch sc;
-  if (const int rc = row_scratch(ACFM_LOSS_BDS, N, S, tickets, partials, partial_floats, sc)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (!sc.tickets && zero_async(loss, sizeof(float) * (size_t)N, st) != ACFM_OK) return ACFM_E_LAUNCH;
-  ProfScope ps(ACFM_PROF_BDS, st);
-  hipLaunchKernelGGL(k_bds_loss_sel, dim3((S + 63) / 64, N), dim3(LTPB), lds, st, verts_xy, bds, vis,
-                     V, P, ref_batch, loss, argmin, sc, sel, rows, S);
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-int acfm_bds_loss_sel_backward(const float* verts_xy, const float* bds, const int32_t* sel, const int32_t* argmin,
-                               const float* grad_loss, int N, int V, int P, int ref_batch, int rows, int S,
-                               float* grad_verts_xy, void* stream) {
-  if (!verts_xy || !bds || !sel || !argmin || !grad_loss || !grad_verts_xy || N <= 0 || N > 65535 || V <= 0 ||
-      P <= 0 || S <= 0 || ref_batch <= 0 || N % ref_batch != 0 || (rows != 1 && rows != ref_batch))
-    return ACFM_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t lds = sizeof(float) * 2 * (size_t)V;
-  if (lds > 150 * 1024) return ACFM_E_BADARG;
-  ProfScope ps(ACFM_PROF_BDS_BWD, st);
-  hipLaunchKernelGGL(k_bds_loss_sel_bwd, dim3(N), dim3(256), lds, st, verts_xy, bds, argmin, grad_loss, V, P,
-                     ref_batch, grad_verts_xy, sel, rows, S);
-  ACFM_CHECK_LAUNCH();
-  return ACFM_OK;
-}
-
-int acfm_of_loss_shared(const float* proj, const float* flows, const float* masks, const uint8_t* vis, int B, int T,
-                        int V, int H, int W, int clips, int flip_t, float* loss, float* count, void* stream) {
+int acfm_of_loss(const float* proj, const float* flows, const float* masks, const uint8_t* vis, int B, int T,
+                 int V, int H, int W, int clips, int flip_t, float* loss, float* count, void* stream) {
   if (!proj || !flows || !vis || !loss || !count || B <= 0 || B > 65535 || T < 2 || T > 65535 || V <= 0 || H <= 0 ||
       W <= 0 || clips <= 0 || B % clips != 0)
     return ACFM_E_BADARG;
@@ -1017,9 +979,9 @@ int acfm_of_loss_shared(const float* proj, const float* flows, const float* mask
   return ACFM_OK;
 }
 
-int acfm_of_loss_shared_backward(const float* proj, const float* flows, const float* masks, const uint8_t* vis,
-                                 const float* count, const float* grad_loss, int B, int T, int V, int H, int W, int clips,
-                                 int flip_t, float* grad_proj, void* stream) {
+int acfm_of_loss_backward(const float* proj, const float* flows, const float* masks, const uint8_t* vis,
+                          const float* count, const float* grad_loss, int B, int T, int V, int H, int W, int clips,
+                          int flip_t, float* grad_proj, void* stream) {
   if (!proj || !flows || !vis || !count || !grad_loss || !grad_proj || B <= 0 || B > 65535 || T < 2 || T > 65535 ||
       V <= 0 || H <= 0 || W <= 0 || clips <= 0 || B % clips != 0)
     return ACFM_E_BADARG;
@@ -1030,17 +992,6 @@ int acfm_of_loss_shared_backward(const float* proj, const float* flows, const fl
                      grad_loss, T, V, H, W, grad_proj);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
-}
-
-int acfm_of_loss(const float* proj, const float* flows, const uint8_t* vis, int B, int T, int V, int H, int W,
-                 float* loss, float* count, void* stream) {
-  return acfm_of_loss_shared(proj, flows, nullptr, vis, B, T, V, H, W, B, 0, loss, count, stream);
-}
-
-int acfm_of_loss_backward(const float* proj, const float* flows, const uint8_t* vis, const float* count,
-                          const float* grad_loss, int B, int T, int V, int H, int W, float* grad_proj,
-                          void* stream) {
-  return acfm_of_loss_shared_backward(proj, flows, nullptr, vis, count, grad_loss, B, T, V, H, W, B, 0, grad_proj, stream);
 }
 
 }  // extern "C"

@@ -145,7 +145,7 @@ static int sil_forward_impl(const float* verts_world, const int64_t* faces, cons
                             void* mask, void* pix_to_face, uint64_t* kth, uint8_t* vis, void* wsp,
                             size_t ws_bytes, const AcfmRasterTuning* tuning, void* stream, bool fused,
                             const void* gt, const void* edt, int ref_batch, float* losses,
-                            const AcfmSilExtras* ex = nullptr) {
+                            const AcfmSilExtras* ex) {
   float* pf_imgs = ex ? ex->tex_imgs : nullptr;
   float* pf_sil = ex ? ex->tex_sil : nullptr;
   int64_t* pf_p2f = ex ? ex->tex_pix_to_face : nullptr;
@@ -196,42 +196,25 @@ static int sil_forward_impl(const float* verts_world, const int64_t* faces, cons
 int acfm_sil_forward(const float* verts_world, const int64_t* faces, const float* cams, int N, int V,
                      int F, int H, int K, int k_out, float blur_radius, float sigma, float offset_z,
                      void* mask, void* pix_to_face, uint64_t* kth, uint8_t* vis, void* wsp,
-                     size_t ws_bytes, const AcfmRasterTuning* tuning, void* stream) {
-  return sil_forward_impl(verts_world, faces, cams, N, V, F, H, K, k_out, blur_radius, sigma, offset_z, mask,
-                          pix_to_face, kth, vis, wsp, ws_bytes, tuning, stream, false, nullptr, nullptr, 1, nullptr);
-}
-
-int acfm_sil_forward_ex(const float* verts_world, const int64_t* faces, const float* cams, int N, int V,
-                        int F, int H, int K, int k_out, float blur_radius, float sigma, float offset_z,
-                        void* mask, void* pix_to_face, uint64_t* kth, uint8_t* vis, void* wsp,
-                        size_t ws_bytes, const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream) {
+                     size_t ws_bytes, const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream) {
   return sil_forward_impl(verts_world, faces, cams, N, V, F, H, K, k_out, blur_radius, sigma, offset_z, mask,
                           pix_to_face, kth, vis, wsp, ws_bytes, tuning, stream, false, nullptr, nullptr, 1, nullptr, extras);
-}
-
-int acfm_sil_loss_forward_ex(const float* verts_world, const int64_t* faces, const float* cams, const void* gt,
-                             const void* edt, int ref_batch, int N, int V, int F, int H, int K, int k_out,
-                             float blur_radius, float sigma, float offset_z, void* mask, void* pix_to_face,
-                             uint64_t* kth, uint8_t* vis, float* losses, void* wsp, size_t ws_bytes,
-                             const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream) {
-  return sil_forward_impl(verts_world, faces, cams, N, V, F, H, K, k_out, blur_radius, sigma, offset_z, mask,
-                          pix_to_face, kth, vis, wsp, ws_bytes, tuning, stream, true, gt, edt, ref_batch, losses, extras);
 }
 
 int acfm_sil_loss_forward(const float* verts_world, const int64_t* faces, const float* cams, const void* gt,
                           const void* edt, int ref_batch, int N, int V, int F, int H, int K, int k_out,
                           float blur_radius, float sigma, float offset_z, void* mask, void* pix_to_face,
                           uint64_t* kth, uint8_t* vis, float* losses, void* wsp, size_t ws_bytes,
-                          const AcfmRasterTuning* tuning, void* stream) {
+                          const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream) {
   return sil_forward_impl(verts_world, faces, cams, N, V, F, H, K, k_out, blur_radius, sigma, offset_z, mask,
-                          pix_to_face, kth, vis, wsp, ws_bytes, tuning, stream, true, gt, edt, ref_batch, losses);
+                          pix_to_face, kth, vis, wsp, ws_bytes, tuning, stream, true, gt, edt, ref_batch, losses, extras);
 }
 
 static int sil_backward_impl(const float* verts_world, const int64_t* faces, const float* cams,
                              const void* mask, const uint64_t* kth, BwdGrad bg, int N, int V,
                              int F, int H, float blur_radius, float sigma, float offset_z, float* grad_verts,
                              float* grad_cams, void* wsp, size_t ws_bytes, int ws_from_forward,
-                             const AcfmRasterTuning* tuning, void* stream, const float* gproj = nullptr) {
+                             const AcfmRasterTuning* tuning, void* stream, const float* gproj) {
   if (!verts_world || !faces || !cams || !mask || !kth || !wsp) return ACFM_E_BADARG;
   if (!bg.grad_mask && (!bg.go || bg.lrb <= 0 || N % bg.lrb != 0)) return ACFM_E_BADARG;
   if (bad_dims(N, V, F, H) || !(sigma > 0.f) || blur_radius < 0.f) return ACFM_E_BADARG;
@@ -264,38 +247,11 @@ int acfm_sil_backward(const float* verts_world, const int64_t* faces, const floa
                       const void* mask, const uint64_t* kth, const float* grad_mask, int N, int V,
                       int F, int H, float blur_radius, float sigma, float offset_z, float* grad_verts,
                       float* grad_cams, void* wsp, size_t ws_bytes, int ws_from_forward,
-                      const AcfmRasterTuning* tuning, void* stream) {
+                      const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream) {
   if (!grad_mask) return ACFM_E_BADARG;
   BwdGrad bg = {};
   bg.grad_mask = grad_mask;
   bg.lrb = 1;
-  return sil_backward_impl(verts_world, faces, cams, mask, kth, bg, N, V, F, H, blur_radius, sigma, offset_z,
-                           grad_verts, grad_cams, wsp, ws_bytes, ws_from_forward, tuning, stream);
-}
-
-int acfm_sil_backward_ex(const float* verts_world, const int64_t* faces, const float* cams,
-                         const void* mask, const uint64_t* kth, const float* grad_mask, int N, int V,
-                         int F, int H, float blur_radius, float sigma, float offset_z, float* grad_verts,
-                         float* grad_cams, void* wsp, size_t ws_bytes, int ws_from_forward,
-                         const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream) {
-  if (!grad_mask) return ACFM_E_BADARG;
-  BwdGrad bg = {};
-  bg.grad_mask = grad_mask;
-  bg.lrb = 1;
-  return sil_backward_impl(verts_world, faces, cams, mask, kth, bg, N, V, F, H, blur_radius, sigma, offset_z,
-                           grad_verts, grad_cams, wsp, ws_bytes, ws_from_forward, tuning, stream,
-                           extras ? extras->grad_proj_xy : nullptr);
-}
-
-int acfm_sil_loss_backward_ex(const float* verts_world, const int64_t* faces, const float* cams, const void* mask,
-                              const uint64_t* kth, const void* gt, const void* edt, int ref_batch,
-                              const float* grad_losses, int N, int V, int F, int H, float blur_radius, float sigma,
-                              float offset_z, float* grad_verts, float* grad_cams, void* wsp, size_t ws_bytes,
-                              int ws_from_forward, const AcfmRasterTuning* tuning, const AcfmSilExtras* extras,
-                              void* stream) {
-  if (!grad_losses) return ACFM_E_BADARG;
-  BwdGrad bg = {};
-  bg.lgt = gt; bg.ledt = edt; bg.go = grad_losses; bg.lrb = ref_batch;
   return sil_backward_impl(verts_world, faces, cams, mask, kth, bg, N, V, F, H, blur_radius, sigma, offset_z,
                            grad_verts, grad_cams, wsp, ws_bytes, ws_from_forward, tuning, stream,
                            extras ? extras->grad_proj_xy : nullptr);
@@ -305,12 +261,14 @@ int acfm_sil_loss_backward(const float* verts_world, const int64_t* faces, const
                            const uint64_t* kth, const void* gt, const void* edt, int ref_batch,
                            const float* grad_losses, int N, int V, int F, int H, float blur_radius, float sigma,
                            float offset_z, float* grad_verts, float* grad_cams, void* wsp, size_t ws_bytes,
-                           int ws_from_forward, const AcfmRasterTuning* tuning, void* stream) {
+                           int ws_from_forward, const AcfmRasterTuning* tuning, const AcfmSilExtras* extras,
+                           void* stream) {
   if (!grad_losses) return ACFM_E_BADARG;
   BwdGrad bg = {};
   bg.lgt = gt; bg.ledt = edt; bg.go = grad_losses; bg.lrb = ref_batch;
   return sil_backward_impl(verts_world, faces, cams, mask, kth, bg, N, V, F, H, blur_radius, sigma, offset_z,
-                           grad_verts, grad_cams, wsp, ws_bytes, ws_from_forward, tuning, stream);
+                           grad_verts, grad_cams, wsp, ws_bytes, ws_from_forward, tuning, stream,
+                           extras ? extras->grad_proj_xy : nullptr);
 }
 
 int acfm_hard_raster(const float* verts_proj, const int64_t* faces, int N, int V, int F, int H,

@@ -5,7 +5,7 @@
 
 namespace acfm {
 
-// ---- per-mesh sums in one launch: no zero fill of the output, no float atomics (the *_ws entry points) -------------
+// ---- per-mesh sums in one launch: no zero fill of the output, no float atomics (entry points given tickets) --------
 // Every workgroup of mesh `row` hands its C partial sums over in `partials`, draws a ticket, and the workgroup that
 // draws the mesh's last ticket adds the partials in workgroup order 0, 1, 2, ... and stores the result: the same
 // inputs give the same bits, and the output needs no prior contents.  The ticket is a WRAPPING increment

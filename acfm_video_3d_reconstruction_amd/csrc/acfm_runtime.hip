@@ -75,7 +75,7 @@ using namespace acfm;
 
 extern "C" {
 
-int acfm_version(void) { return 1001; }
+int acfm_version(void) { return 2000; }
 const char* acfm_arch(void) { return "gfx950"; }
 
 int acfm_stream_capture_id(void* stream, unsigned long long* id_host) {

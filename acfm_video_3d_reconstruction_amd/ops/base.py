@@ -213,7 +213,7 @@ def _a16(t):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
-# Scratch of the one-launch loss sums (acfm_mask_losses_ws, acfm_tex_mse_ws, acfm_bds_loss_ws: include/acfm_hip.h):
+# Scratch of the one-launch loss sums (acfm_mask_losses, acfm_tex_mse, acfm_bds_loss given tickets: include/acfm_hip.h):
 # per (device, stream, capture, loss) one ticket word per mesh -- zero before the first launch, left at zero by
 # every launch -- and a buffer for the workgroups' partial sums (any contents).  Keyed like that, two calls that can
 # be in flight at the same time never share them, and a captured graph keeps the addresses it was recorded with.
@@ -246,7 +246,7 @@ def _ticket_words(device, n, capturing):
 
 
 def _loss_scratch(device, which, N, n):
-    """-> (tickets, partials, floats in partials) for an acfm_*_ws call of loss `which` on the current stream."""
+    """-> (tickets, partials, floats in partials) for a ticket-form call of loss `which` on the current stream."""
     return _row_scratch(device, which, N, int(_lib.lib().acfm_loss_partial_floats(which, N, n)))
 
 

@@ -23,7 +23,7 @@ class _OFLoss(torch.autograd.Function):
                                 None if mk is None else tuple(mk.shape), B, T))
         loss = torch.empty((B, T - 1), dtype=torch.float32, device=p.device)
         cnt = torch.empty((B, T - 1), dtype=torch.float32, device=p.device)
-        _lib.call("acfm_of_loss_shared", p.device, _lib.ptr(p), _lib.ptr(fl), _lib.ptr(mk), _lib.ptr(vi), B, T, V, H, W,
+        _lib.call("acfm_of_loss", p.device, _lib.ptr(p), _lib.ptr(fl), _lib.ptr(mk), _lib.ptr(vi), B, T, V, H, W,
                   clips, int(bool(flip_t)), _lib.ptr(loss), _lib.ptr(cnt))
         ctx.save_for_backward(p, fl, vi, cnt) if mk is None else ctx.save_for_backward(p, fl, vi, cnt, mk)
         ctx.dims = (B, T, V, H, W, clips, int(bool(flip_t)), mk is not None)
@@ -36,7 +36,7 @@ class _OFLoss(torch.autograd.Function):
         mk = ctx.saved_tensors[4] if has_m else None
         g = _f32c(g)
         gp = torch.empty_like(p)
-        _lib.call("acfm_of_loss_shared_backward", p.device, _lib.ptr(p), _lib.ptr(fl), _lib.ptr(mk), _lib.ptr(vi),
+        _lib.call("acfm_of_loss_backward", p.device, _lib.ptr(p), _lib.ptr(fl), _lib.ptr(mk), _lib.ptr(vi),
                   _lib.ptr(cnt), _lib.ptr(g), B, T, V, H, W, clips, flip_t, _lib.ptr(gp))
         return gp, None, None, None, None, None, None
 

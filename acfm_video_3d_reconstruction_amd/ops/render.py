@@ -254,7 +254,7 @@ def _lazy_pix_to_face(plane0, vis, v, f, c, H, K, blur, sigma, offset_z):
         ws, nb = _workspace(N, V, F, H, v.device)          # its own workspace: the render's is still the backward's
         _lib.call("acfm_sil_forward", v.device, _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), N, V, F, H, K, K, float(blur),
                   float(sigma), float(offset_z), _lib.ptr(mask), _lib.ptr(full), _lib.ptr(kth), _lib.ptr(vis2),
-                  _lib.ptr(ws), nb, _lib.tuning_ptr(tune))
+                  _lib.ptr(ws), nb, _lib.tuning_ptr(tune), None)
         return full
 
     return LazyPixToFace(plane0, K, make_full, vis)
@@ -262,8 +262,8 @@ def _lazy_pix_to_face(plane0, vis, v, f, c, H, K, blur, sigma, offset_z):
 
 # ------------------------------------------------------------------------------ silhouette
 class _SilRender(torch.autograd.Function):
-    """Soft silhouette render (acfm_sil_forward_ex / acfm_sil_backward_ex); fused=True: the render and its [N,4]
-    silhouette-loss vector against gt / edt as one operator (acfm_sil_loss_forward_ex / acfm_sil_loss_backward_ex),
+    """Soft silhouette render (acfm_sil_forward / acfm_sil_backward); fused=True: the render and its [N,4]
+    silhouette-loss vector against gt / edt as one operator (acfm_sil_loss_forward / acfm_sil_loss_backward),
     the mask then carries no gradient.  -> (losses or None, mask, pix_to_face, vis, proj)."""
 
     @staticmethod
@@ -310,11 +310,11 @@ class _SilRender(torch.autograd.Function):
         exp, _ex_keep = _lib.sil_extras(proj_xy=proj, prefill=prefill)
         P = _lib.ptr
         if fused:
-            _lib.call("acfm_sil_loss_forward_ex", v.device, P(v), P(f), P(c), P(g), P(e), RB, N, V, F, H, K, int(k_out),
+            _lib.call("acfm_sil_loss_forward", v.device, P(v), P(f), P(c), P(g), P(e), RB, N, V, F, H, K, int(k_out),
                       float(blur), float(sigma), float(offset_z), P(mask), P(p2f), P(kth), P(vis), P(losses), P(ws), nb,
                       tp, exp)
         else:
-            _lib.call("acfm_sil_forward_ex", v.device, P(v), P(f), P(c), N, V, F, H, K, int(k_out), float(blur),
+            _lib.call("acfm_sil_forward", v.device, P(v), P(f), P(c), N, V, F, H, K, int(k_out), float(blur),
                       float(sigma), float(offset_z), P(mask), P(p2f), P(kth), P(vis), P(ws), nb, tp, exp)
         _remember_setup(v, c, f, H, offset_z, ws, nb, blur, tune, prefill)
         ctx.save_for_backward(v, f, c, mask, kth, g, e)
@@ -348,11 +348,11 @@ class _SilRender(torch.autograd.Function):
             pay = gmask.take("mask_losses", mask) if type(gmask) is LazyGrad else None
         if pay is not None:
             _m, lg, le, rb, go = pay
-            _lib.call("acfm_sil_loss_backward_ex", v.device, P(v), P(f), P(c), P(mask), P(kth), P(lg), P(le), rb, P(go),
+            _lib.call("acfm_sil_loss_backward", v.device, P(v), P(f), P(c), P(mask), P(kth), P(lg), P(le), rb, P(go),
                       N, V, F, H, blur, sigma, offset_z, P(gv), P(gc), P(ws), nb, 1, _lib.tuning_ptr(tune), exp)
         else:
             gm = _f32c(gmask)
-            _lib.call("acfm_sil_backward_ex", v.device, P(v), P(f), P(c), P(mask), P(kth), P(gm), N, V, F, H, blur,
+            _lib.call("acfm_sil_backward", v.device, P(v), P(f), P(c), P(mask), P(kth), P(gm), N, V, F, H, blur,
                       sigma, offset_z, P(gv), P(gc), P(ws), nb, 1, _lib.tuning_ptr(tune), exp)
         return (gv, None, gc) + none[3:]
 

@@ -30,7 +30,7 @@ class _MaskLosses(torch.autograd.Function):
         def launch():
             with torch.cuda.device(m.device):
                 tk, part, nf = _loss_scratch(m.device, _LOSS_MASK, N, HW)
-            _lib.call("acfm_mask_losses_ws", m.device, _lib.ptr(m), _lib.ptr(g), _lib.ptr(e), N, HW, RB, _lib.ptr(out),
+            _lib.call("acfm_mask_losses", m.device, _lib.ptr(m), _lib.ptr(g), _lib.ptr(e), N, HW, RB, _lib.ptr(out),
                       _lib.ptr(tk), _lib.ptr(part), nf)
         ctx.save_for_backward(m, g, e)
         ctx.rb = RB
@@ -85,7 +85,7 @@ class _TexMSE(torch.autograd.Function):
         def launch():
             with torch.cuda.device(t.device):
                 tk, part, nf = _loss_scratch(t.device, _LOSS_TEX_MSE, N, HW)
-            _lib.call("acfm_tex_mse_ws", t.device, _lib.ptr(t), _lib.ptr(i), _lib.ptr(m), N, HW, RB, _lib.ptr(out),
+            _lib.call("acfm_tex_mse", t.device, _lib.ptr(t), _lib.ptr(i), _lib.ptr(m), N, HW, RB, _lib.ptr(out),
                       _lib.ptr(tk), _lib.ptr(part), nf)
         ctx.save_for_backward(t, i, m)
         ctx.rb = RB
@@ -196,7 +196,7 @@ class _BdsLoss(torch.autograd.Function):
         def launch():
             with torch.cuda.device(v.device):
                 tk, part, nf = _loss_scratch(v.device, _LOSS_BDS, N, P)
-            _lib.call("acfm_bds_loss_ws", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vz), N, V, P, RB,
+            _lib.call("acfm_bds_loss", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vz), None, N, V, P, RB, 0, 0,
                       _lib.ptr(loss), _lib.ptr(arg), _lib.ptr(tk), _lib.ptr(part), nf)
         ctx.rb = RB
         ctx.job = None
@@ -219,13 +219,13 @@ class _BdsLoss(torch.autograd.Function):
         P = b.shape[1]
         g = _f32c(gl)
         gv = torch.empty_like(v)
-        _lib.call("acfm_bds_loss_backward", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(arg), _lib.ptr(g), N, V, P,
-                  ctx.rb, _lib.ptr(gv))
+        _lib.call("acfm_bds_loss_backward", v.device, _lib.ptr(v), _lib.ptr(b), None, _lib.ptr(arg), _lib.ptr(g), N, V, P,
+                  ctx.rb, 0, 0, _lib.ptr(gv))
         return gv, None, None
 
 
 class _BdsLossSel(torch.autograd.Function):
-    """_BdsLoss with every point read through a slot list (acfm_bds_loss_sel_ws): no gathered copy of the points."""
+    """_BdsLoss with every point read through a slot list (acfm_bds_loss with sel): no gathered copy of the points."""
 
     @staticmethod
     def forward(ctx, verts_xy, bds, vis, sel):
@@ -246,7 +246,7 @@ class _BdsLossSel(torch.autograd.Function):
         def launch():
             with torch.cuda.device(v.device):
                 tk, part, nf = _loss_scratch(v.device, _LOSS_BDS, N, S)
-            _lib.call("acfm_bds_loss_sel_ws", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vz), _lib.ptr(s),
+            _lib.call("acfm_bds_loss", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vz), _lib.ptr(s),
                       N, V, P, RB, rows, S, _lib.ptr(loss), _lib.ptr(arg), _lib.ptr(tk), _lib.ptr(part), nf)
         ctx.rb = RB
         ctx.job = None
@@ -270,7 +270,7 @@ class _BdsLossSel(torch.autograd.Function):
         rows, S = s.shape
         g = _f32c(gl)
         gv = torch.empty_like(v)
-        _lib.call("acfm_bds_loss_sel_backward", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(s), _lib.ptr(arg),
+        _lib.call("acfm_bds_loss_backward", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(s), _lib.ptr(arg),
                   _lib.ptr(g), N, V, P, ctx.rb, rows, S, _lib.ptr(gv))
         return gv, None, None, None
 

@@ -45,7 +45,10 @@ extern "C" {
 #define ACFM_RECORD_COVER 4
 
 /* library / device info ------------------------------------------------------------- */
-int acfm_version(void);              /* 1000*major + minor */
+/* acfm_version: 1000*major + minor, 2000 here.  The 2.x signatures are incompatible with 1.x: the entry points that 1.x
+ * had in a short and a long form keep the short name with the long argument list.  A caller compares the version with
+ * the header it was written against before it uses any other symbol (_lib.lib() does). */
+int acfm_version(void);
 const char* acfm_arch(void);         /* "gfx950" */
 
 /* 0 when `stream` is not being captured into a hipGraph, else the (non-zero) id of the capture
@@ -183,21 +186,17 @@ int acfm_deform_conv2d_backward(const float* grad_out, const float* input, const
  *   images, vis [B*T,V] visible-vertex bitmap of the hard raster  ->  loss [B,T-1]:
  *   sum over the kept vertices of |gt - (pix[k-1] - pix[k])|_1 / H / (kept + 1), gt = nearest pixel
  *   (grid_sample nearest, align_corners False, zeros), kept = visible in frame k and gt != 0;
- *   count [B,T-1] is saved for the backward pass (grad_loss [B,T-1] -> grad_proj [B*T,V,3]). */
-int acfm_of_loss(const float* proj, const float* flows, const uint8_t* vis, int B, int T, int V, int H, int W,
-                 float* loss, float* count, void* stream);
-int acfm_of_loss_backward(const float* proj, const float* flows, const uint8_t* vis, const float* count,
-                          const float* grad_loss, int B, int T, int V, int H, int W, float* grad_proj,
-                          void* stream);
-/* the same with the GT flows as the data loader holds them (multiframe/main.py:676-686 flips them in time, masks
- * them and repeats them for the G hypotheses every step; the loss reads V pixels per frame): flows [clips,T,H,W,2],
- * clip c of the B = G*clips rendered ones reads clip c % clips, frame k reads frame T-1-k if flip_t, and the value is
- * multiplied by masks [clips*T,H,W] at the same pixel of frame k if masks is not NULL. */
-int acfm_of_loss_shared(const float* proj, const float* flows, const float* masks, const uint8_t* vis, int B, int T,
-                        int V, int H, int W, int clips, int flip_t, float* loss, float* count, void* stream);
-int acfm_of_loss_shared_backward(const float* proj, const float* flows, const float* masks, const uint8_t* vis,
-                                 const float* count, const float* grad_loss, int B, int T, int V, int H, int W, int clips,
-                                 int flip_t, float* grad_proj, void* stream);
+ *   count [B,T-1] is saved for the backward pass (grad_loss [B,T-1] -> grad_proj [B*T,V,3]).
+ * The GT flows are read as the data loader holds them (multiframe/main.py:676-686 flips them in time, masks them and
+ * repeats them for the G hypotheses every step; the loss reads V pixels per frame): flows [clips,T,H,W,2], clip c of the
+ * B = G*clips rendered ones reads clip c % clips, frame k reads frame T-1-k if flip_t, and the value is multiplied by
+ * masks [clips*T,H,W] at the same pixel of frame k if masks is not NULL.  masks = NULL, clips = B, flip_t = 0: flows
+ * [B*T,H,W,2] as they are. */
+int acfm_of_loss(const float* proj, const float* flows, const float* masks, const uint8_t* vis, int B, int T, int V,
+                 int H, int W, int clips, int flip_t, float* loss, float* count, void* stream);
+int acfm_of_loss_backward(const float* proj, const float* flows, const float* masks, const uint8_t* vis,
+                          const float* count, const float* grad_loss, int B, int T, int V, int H, int W, int clips,
+                          int flip_t, float* grad_proj, void* stream);
 
 /* ---- camera hypothesis pipeline --------------------------------------------------------
  * replaces the camera decode + mirror_cameras + transform_cameras chain of ShapeTrainer.forward /
@@ -347,15 +346,11 @@ typedef struct AcfmRasterTuning {
  *      mask != 0 (all the backward reads) -- the 8x8 blocks no face comes near are not written
  *   -> vis [N,V] u8 (optional): 1 for every vertex of a face that is nearest in some pixel,
  *      i.e. the visible-vertex set of loss_utils.bds_loss (:214-224), fused into the raster
- * K in {2,4,8,10,20,32}. */
-int acfm_sil_forward(const float* verts_world, const int64_t* faces, const float* cams, int N,
-                     int V, int F, int H, int K, int k_out, float blur_radius, float sigma,
-                     float offset_z, void* mask /* [real] */, void* pix_to_face /* int64, or the int32 plane */,
-                     uint64_t* kth, uint8_t* vis, void* ws, size_t ws_bytes, const AcfmRasterTuning* tuning,
-                     void* stream);
-
-/* Extras of the silhouette render for what the reference's callers do NEXT TO it with the same vertices and cameras
- * (every field optional, NULL = not wanted; the `_ex` entry points are their plain namesakes + this structure):
+ * K in {2,4,8,10,20,32}.
+ *
+ * AcfmSilExtras, the last argument but one of the four silhouette entry points (acfm_sil_forward, acfm_sil_backward,
+ * acfm_sil_loss_forward, acfm_sil_loss_backward): what the reference's callers do NEXT TO the render with the same
+ * vertices and cameras.  extras == NULL, or a NULL field: not wanted.
  *   proj_xy         forward out [N,V,2]: NeuralRenderer.project_points(vertices, cams) (nmr.py:127-129), which the
  *                   trainer calls on the prediction it has just rendered (main.py:715, predictor.py:319): the face
  *                   setup projects the vertices anyway, so it hands (x, y) out instead of a second projection kernel;
@@ -375,15 +370,11 @@ typedef struct AcfmSilExtras {
   int64_t* tex_pix_to_face;   /* [N,H,H,1] */
   int32_t* tex_texel_idx;     /* [N,H,H] */
 } AcfmSilExtras;
-int acfm_sil_forward_ex(const float* verts_world, const int64_t* faces, const float* cams, int N,
-                        int V, int F, int H, int K, int k_out, float blur_radius, float sigma,
-                        float offset_z, void* mask, void* pix_to_face, uint64_t* kth, uint8_t* vis, void* ws,
-                        size_t ws_bytes, const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream);
-int acfm_sil_backward_ex(const float* verts_world, const int64_t* faces, const float* cams,
-                         const void* mask, const uint64_t* kth, const float* grad_mask, int N, int V,
-                         int F, int H, float blur_radius, float sigma, float offset_z,
-                         float* grad_verts, float* grad_cams, void* ws, size_t ws_bytes,
-                         int ws_from_forward, const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream);
+int acfm_sil_forward(const float* verts_world, const int64_t* faces, const float* cams, int N,
+                     int V, int F, int H, int K, int k_out, float blur_radius, float sigma,
+                     float offset_z, void* mask /* [real] */, void* pix_to_face /* int64, or the int32 plane */,
+                     uint64_t* kth, uint8_t* vis, void* ws, size_t ws_bytes, const AcfmRasterTuning* tuning,
+                     const AcfmSilExtras* extras, void* stream);
 
 /* replaces autograd through SoftSilhouetteShader + pytorch3d._C.rasterize_meshes_backward
  * (dists path) + the projection chain.  mask / kth are the forward's outputs;
@@ -394,7 +385,7 @@ int acfm_sil_backward(const float* verts_world, const int64_t* faces, const floa
                       const void* mask /* [real] */, const uint64_t* kth, const float* grad_mask, int N, int V,
                       int F, int H, float blur_radius, float sigma, float offset_z,
                       float* grad_verts, float* grad_cams, void* ws, size_t ws_bytes,
-                      int ws_from_forward, const AcfmRasterTuning* tuning, void* stream);
+                      int ws_from_forward, const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream);
 
 /* ---- fused soft silhouette + silhouette losses (opt-in) --------------------------------
  * acfm_sil_forward and acfm_mask_losses as ONE operator: the reference consumes the rendered mask at once
@@ -410,23 +401,13 @@ int acfm_sil_loss_forward(const float* verts_world, const int64_t* faces, const 
                           const void* edt /* [real] */, int ref_batch, int N, int V, int F, int H, int K, int k_out,
                           float blur_radius, float sigma, float offset_z, void* mask /* [real] */, void* pix_to_face,
                           uint64_t* kth, uint8_t* vis, float* losses, void* ws, size_t ws_bytes,
-                          const AcfmRasterTuning* tuning, void* stream);
+                          const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream);
 int acfm_sil_loss_backward(const float* verts_world, const int64_t* faces, const float* cams, const void* mask,
                            const uint64_t* kth, const void* gt, const void* edt, int ref_batch,
                            const float* grad_losses, int N, int V, int F, int H, float blur_radius, float sigma,
                            float offset_z, float* grad_verts, float* grad_cams, void* ws, size_t ws_bytes,
-                           int ws_from_forward, const AcfmRasterTuning* tuning, void* stream);
-int acfm_sil_loss_forward_ex(const float* verts_world, const int64_t* faces, const float* cams, const void* gt /* [real] */,
-                             const void* edt /* [real] */, int ref_batch, int N, int V, int F, int H, int K, int k_out,
-                             float blur_radius, float sigma, float offset_z, void* mask, void* pix_to_face,
-                             uint64_t* kth, uint8_t* vis, float* losses, void* ws, size_t ws_bytes,
-                             const AcfmRasterTuning* tuning, const AcfmSilExtras* extras, void* stream);
-int acfm_sil_loss_backward_ex(const float* verts_world, const int64_t* faces, const float* cams, const void* mask,
-                              const uint64_t* kth, const void* gt, const void* edt, int ref_batch,
-                              const float* grad_losses, int N, int V, int F, int H, float blur_radius, float sigma,
-                              float offset_z, float* grad_verts, float* grad_cams, void* ws, size_t ws_bytes,
-                              int ws_from_forward, const AcfmRasterTuning* tuning, const AcfmSilExtras* extras,
-                              void* stream);
+                           int ws_from_forward, const AcfmRasterTuning* tuning, const AcfmSilExtras* extras,
+                           void* stream);
 
 /* ---- hard rasteriser (K = 1, blur 0) -------------------------------------------------
  * replaces OF_NeuralRenderer.forward (multiframe/nnutils/nmr.py:224-238): verts are
@@ -543,8 +524,8 @@ int acfm_uv_texels_backward(const int64_t* pix_to_face, const float* bary, const
  * face setup are skipped and the blur-expanded boxes tightened by sqrt(ws_blur).
  * ws_ready == 2: that acfm_sil_forward ran with ACFM_RECORD_COVER (and the same tuning is passed here): the nearest
  * covering face of every pixel is read from the workspace, nothing is binned or walked.
- * ws_ready == 3: as 2, and that render was acfm_sil_forward_ex (AcfmSilExtras.tex_*) with THESE imgs / sil / pix_to_face / texel_idx
- * buffers: the blocks no face comes near hold their constants already and are not written again.
+ * ws_ready == 3: as 2, and that render was given THESE imgs / sil / pix_to_face / texel_idx buffers in
+ * AcfmSilExtras.tex_*: the blocks no face comes near hold their constants already and are not written again.
  * atlas_batch: number of distinct atlases, atlas [atlas_batch,F,R,R,3]; mesh n samples atlas
  * n % atlas_batch (the trainer renders G camera hypotheses of every frame with the frame's one
  * texture, textures.repeat(G, ...) at main.py:627-636: atlas_batch = N / G spares the copies, and
@@ -638,25 +619,25 @@ int acfm_texture_cycle_backward(const float* textures, const float* scratch, con
  * ref_batch (here and in the losses below): the number of distinct references; prediction n is
  * compared with reference n % ref_batch (gt, edt [ref_batch,HW]).  The trainer scores G camera
  * hypotheses per frame against the frame's one ground truth (masks.repeat(G, 1, 1) at
- * main.py:472-479, 644-662): ref_batch = N / G spares those copies; ref_batch = N is the plain case. */
-int acfm_mask_losses(const float* mask, const float* gt, const float* edt, int N, int HW, int ref_batch,
-                     float* out, void* stream);
-/* Scratch-backed forms of the three per-mesh loss sums (acfm_mask_losses_ws, acfm_tex_mse_ws, acfm_bds_loss_ws):
- * the same inputs and outputs in ONE launch.  The plain entry points zero the output with a launch of their own
- * and add the workgroups' sums to it with float atomics, in the order they arrive.  Here every workgroup hands
- * its sums over in `partials`, counts itself in `tickets`, and the workgroup that finishes a mesh last adds the
- * sums in workgroup order: no fill, and the same inputs give the same bits on every run.
+ * main.py:472-479, 644-662): ref_batch = N / G spares those copies; ref_batch = N is the plain case.
+ *
+ * The finish of the three per-mesh loss sums (acfm_mask_losses, acfm_tex_mse, acfm_bds_loss), chosen by their
+ * `tickets` / `partials` arguments; inputs and outputs are the same either way.
+ *   tickets == partials == NULL: the call zeroes the output with a launch of its own and the workgroups add their sums
+ *     to it with float atomics, in the order they arrive.  Only one of the two NULL: ACFM_E_BADARG.
+ *   Both given: ONE launch.  Every workgroup hands its sums over in `partials`, counts itself in `tickets`, and the
+ *     workgroup that finishes a mesh last adds the sums in workgroup order: no fill, and the same inputs give the same
+ *     bits on every run.
  *   tickets: N words, ALL ZERO before their first use; every launch leaves them at zero again, so any of the
  *     three entry points, with any shape of at most that many meshes, can follow on them.  (A launch that is
  *     killed midway leaves them undefined: zero them again.)
  *   partials: partial_floats >= acfm_loss_partial_floats(which, N, n) floats, n = HW for the two image losses and
- *     P for the boundary loss; any contents.  Too small: ACFM_E_WORKSPACE.
- *   Calls that can be in flight at the same time (different streams) need tickets and partials each.
- *   tickets == partials == NULL: the plain behaviour; only one of them NULL: ACFM_E_BADARG. */
+ *     the number of points per mesh for the boundary loss; any contents.  Too small: ACFM_E_WORKSPACE.
+ *   Calls that can be in flight at the same time (different streams) need tickets and partials each. */
 enum { ACFM_LOSS_MASK = 0, ACFM_LOSS_TEX_MSE = 1, ACFM_LOSS_BDS = 2 };
 size_t acfm_loss_partial_floats(int which, int N, int n);
-int acfm_mask_losses_ws(const float* mask, const float* gt, const float* edt, int N, int HW, int ref_batch,
-                        float* out, uint32_t* tickets, float* partials, size_t partial_floats, void* stream);
+int acfm_mask_losses(const float* mask, const float* gt, const float* edt, int N, int HW, int ref_batch,
+                     float* out, uint32_t* tickets, float* partials, size_t partial_floats, void* stream);
 /* grad_mask [N,HW] = w_l1[n]*sign(m-gt)/HW + w_edt[n]*edt/HW + IoU term
  * (w_inter[n]*gt + w_union[n]*(1-gt)); weights are per-mesh upstream gradients [N,4]. */
 int acfm_mask_losses_backward(const float* mask, const float* gt, const float* edt,
@@ -673,10 +654,8 @@ int acfm_mask_losses_backward(const float* mask, const float* gt, const float* e
  * the mask is zero does NOT reach the result unless a non-zero mask value shares its group of four, whereas
  * F.mse_loss(tex * mask, img * mask) returns NaN for it.  acfm_tex_mse_backward reads every pixel. */
 int acfm_tex_mse(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,
-                 float* out, void* stream);
-int acfm_tex_mse_ws(const float* tex, const float* img, const float* mask, int N, int HW, int ref_batch,
-                    float* out, uint32_t* tickets, float* partials, size_t partial_floats,
-                    void* stream);                                                  /* see acfm_mask_losses_ws */
+                 float* out, uint32_t* tickets, float* partials, size_t partial_floats,
+                 void* stream);                                    /* tickets / partials: see acfm_mask_losses */
 int acfm_tex_mse_backward(const float* tex, const float* img, const float* mask,
                           const float* grad_out, int N, int HW, int ref_batch, float* grad_tex, void* stream);
 
@@ -688,30 +667,24 @@ int acfm_visible_vertices(const int64_t* pix_to_face, const int64_t* faces, int 
                           int HW, int K, uint8_t* vis, void* stream);
 /* loss_utils.bds_loss (:204-237) given vis: for each boundary point the squared distance to
  * the nearest visible projected vertex (1000 where none), times the point's valid flag,
- * summed per mesh.  verts_xy [N,V,2], bds [ref_batch,P,3] -> loss [N], argmin [N,P] i32 (saved).
- * The forward keeps 12 B per vertex in dynamic LDS, the backward 8 B, at most 150 KB: V <= 12,800 forward (so the
- * backward's V <= 19,200 is never the limit); a larger V returns ACFM_E_BADARG. */
-int acfm_bds_loss(const float* verts_xy, const float* bds, const uint8_t* vis, int N, int V, int P,
-                  int ref_batch, float* loss, int32_t* argmin, void* stream);
-int acfm_bds_loss_ws(const float* verts_xy, const float* bds, const uint8_t* vis, int N, int V, int P,
-                     int ref_batch, float* loss, int32_t* argmin, uint32_t* tickets, float* partials,
-                     size_t partial_floats, void* stream);                          /* see acfm_mask_losses_ws */
-int acfm_bds_loss_backward(const float* verts_xy, const float* bds, const int32_t* argmin,
-                           const float* grad_loss, int N, int V, int P, int ref_batch, float* grad_verts_xy,
-                           void* stream);
-/* The boundary loss over a SUBSET of each reference's points, named by slot lists (acfm_boundary_subset below)
- * instead of a gathered copy -- replaces `indices = torch.randperm(P)[:n_samples]; bds = bds[..., indices, :]` of
- * loss_utils.bds_loss (:211-213) together with the distance search that follows it (:226-237).
+ * summed per mesh.  verts_xy [N,V,2], bds [ref_batch,P,3] -> loss [N], argmin i32 (saved).
+ *   sel == NULL: every point of the reference; argmin [N,P], rows and S are ignored, scratch is sized with n = P
+ *   (acfm_loss_partial_floats(ACFM_LOSS_BDS, N, P); tickets / partials: see acfm_mask_losses).
+ *   sel != NULL: a SUBSET of each reference's points, named by slot lists (acfm_boundary_subset below) instead of a
+ *   gathered copy -- replaces `indices = torch.randperm(P)[:n_samples]; bds = bds[..., indices, :]` of
+ *   loss_utils.bds_loss (:211-213) together with the distance search that follows it (:226-237).
  *   sel [rows,S] i32, rows = 1 (one list for every reference) or rows = ref_batch (reference b reads row b): entry p
  *   names slot sel[((n % ref_batch) % rows) S + p] of bds [ref_batch,P,3]; an entry < 0 (or >= P) is empty: it adds 0
- *   and its argmin is -1.  loss [N], argmin [N,S] i32.  Scratch as for acfm_bds_loss_ws with n = S
- *   (acfm_loss_partial_floats(ACFM_LOSS_BDS, N, S)); LDS limits as for acfm_bds_loss. */
-int acfm_bds_loss_sel_ws(const float* verts_xy, const float* bds, const uint8_t* vis, const int32_t* sel, int N, int V,
-                         int P, int ref_batch, int rows, int S, float* loss, int32_t* argmin, uint32_t* tickets,
-                         float* partials, size_t partial_floats, void* stream);
-int acfm_bds_loss_sel_backward(const float* verts_xy, const float* bds, const int32_t* sel, const int32_t* argmin,
-                               const float* grad_loss, int N, int V, int P, int ref_batch, int rows, int S,
-                               float* grad_verts_xy, void* stream);
+ *   and its argmin is -1.  argmin [N,S]; scratch is sized with n = S.
+ * The backward takes the sel (and rows, S) of its forward: grad_loss [N] -> grad_verts_xy [N,V,2].
+ * The forward keeps 12 B per vertex in dynamic LDS, the backward 8 B, at most 150 KB: V <= 12,800 forward (so the
+ * backward's V <= 19,200 is never the limit); a larger V returns ACFM_E_BADARG. */
+int acfm_bds_loss(const float* verts_xy, const float* bds, const uint8_t* vis, const int32_t* sel, int N, int V, int P,
+                  int ref_batch, int rows, int S, float* loss, int32_t* argmin, uint32_t* tickets, float* partials,
+                  size_t partial_floats, void* stream);
+int acfm_bds_loss_backward(const float* verts_xy, const float* bds, const int32_t* sel, const int32_t* argmin,
+                           const float* grad_loss, int N, int V, int P, int ref_batch, int rows, int S,
+                           float* grad_verts_xy, void* stream);
 /* acfm_boundary_subset: the draw itself, `torch.randperm(P)[:n_samples]` of loss_utils.bds_loss (:211), on the device:
  * a uniform random subset of min(n_samples, P_r) of the slots [0, P_r) of every row r, without replacement, written
  * in ascending slot order and followed by -1.  sel [rows,n_samples] i32.
@@ -733,12 +706,12 @@ int acfm_boundary_subset(int64_t* state, const int32_t* counts, int n_counts, in
                          int32_t* sel, void* stream);
 
 /* ---- the step's tail in one launch ------------------------------------------------------------------------------
- * acfm_step_losses_forward: any of acfm_mask_losses_ws, acfm_tex_mse_ws and acfm_bds_loss_ws / acfm_bds_loss_sel_ws on
+ * acfm_step_losses_forward: any of acfm_mask_losses, acfm_tex_mse and acfm_bds_loss (each in its ticket form) on
  * the same N meshes, and optionally acfm_combine_losses over their outputs, as ONE kernel (k_step_tail): the three
  * sums are short launches far below the memory and issue limits, and as roles of one grid their latencies overlap.
  * Every job computes what its own entry point computes, bit for bit (same pixel partition, same order of sums); the
  * fields of a job are that entry point's arguments.  mask / tex / bds: NULL = that term is not computed (at least
- * one must be given).  bds->sel: NULL = acfm_bds_loss_ws (rows and S are ignored), else acfm_bds_loss_sel_ws.
+ * one must be given).  bds->sel: as acfm_bds_loss's sel (NULL: rows and S are ignored).
  * total: NULL, or the arguments of acfm_combine_losses; its terms are usually the outputs of the jobs of this call
  * (the kernel evaluates the total once the last of them is finished), and any other term must have been finished by
  * an earlier launch on the stream.  Same expression in the same order as acfm_combine_losses: the same bits.
@@ -814,8 +787,8 @@ int acfm_edge_rigidity_backward(const float* verts, const int64_t* edges, const 
  *     other cloud has length 0 (then the sum is 0); rows at or past the length are not written.
  *   |.|^2 = (dx dx + dy dy) + dz dz in f32, each operation rounded.  Both directions are one launch; the candidates
  *   stream through a fixed 16 KB of LDS, so P1 and P2 are bounded by int only; N <= 65535.
- *   Scratch as for acfm_mask_losses_ws, but 2 N ticket words (all zero before the first use, zero again after every
- *   launch) and acfm_chamfer_partial_floats(N, P1, P2) floats of any contents, both required: no zero fill of
+ *   Scratch as for the ticket form of acfm_mask_losses, but 2 N ticket words (all zero before the first use, zero again
+ *   after every launch) and acfm_chamfer_partial_floats(N, P1, P2) floats of any contents, both required: no zero fill of
  *   `sums`, no float atomics, the same bits on every run.
  * acfm_chamfer_backward: grad_sums [N,2] (device) -> grad_x [N,P1,3], grad_y [N,P2,3]; EVERY row is written (zeros
  *   at and past the lengths).  A point receives 2 g (p - nn(p)) for its own nearest neighbour and 2 g' (p - r) from

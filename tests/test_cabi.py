@@ -10,10 +10,110 @@ import torch
 from conftest import ROOT
 
 
-def _declared_symbols():
+def _header():
+    """include/acfm_hip.h without its comments."""
     txt = open(os.path.join(ROOT, "include", "acfm_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(acfm_[a-z0-9_]+)\s*\(", txt)))
+    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+
+
+def _declared_symbols():
+    return sorted(set(re.findall(r"\b(acfm_[a-z0-9_]+)\s*\(", _header())))
+
+
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+
+
+def _prototypes():
+    """{name: (restype, [argtypes])} of every `type name(args);` of the header, in ctypes classes: any pointer is
+    c_void_p, int / float / size_t are themselves; a type outside these is a KeyError (extend the test with the ABI)."""
+    out = {}
+    for ret, name, args in re.findall(r"^((?:const\s+)?\w+\s*\*?)\s*(acfm_\w+)\s*\(([^()]*)\)\s*;", _header(), flags=re.M):
+        params = [" ".join(a.split()) for a in args.split(",")]
+        if params == ["void"]:
+            params = []
+        kinds = [ctypes.c_void_p if "*" in p else _SCALARS[p.rsplit(" ", 1)[0]] for p in params]
+        assert name not in out, "%s is declared twice" % name
+        out[name] = (_RETURNS[" ".join(ret.split())], kinds)
+    return out
+
+
+def _struct_fields(name):
+    """Field names, in order, of `typedef struct [tag] { ... } name;` (several fields per statement are split)."""
+    body = re.search(r"typedef\s+struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*%s\s*;" % name, _header()).group(1)
+    pieces = [p.strip() for p in re.split(r"[;,]", body)]
+    return [re.search(r"(\w+)\s*(?:\[\d+\])?$", p).group(1) for p in pieces if p]
+
+
+def _defines():
+    """{NAME: value} of the header's integer #defines and enumerators."""
+    txt = _header()
+    out = {k: int(v, 0) for k, v in re.findall(r"^#define\s+(ACFM_\w+)\s+(-?\w+)\s*$", txt, flags=re.M)}
+    for body in re.findall(r"enum\s*\{([^{}]*)\}", txt):
+        out.update({k: int(v, 0) for k, v in re.findall(r"(ACFM_\w+)\s*=\s*(-?\w+)", body)})
+    return out
+
+
+def test_signature_table_matches_the_header_by_type():
+    """SIGNATURES[name] == the header's prototype: return type and every parameter's class, in order and in number
+    (the names-only comparison below cannot see an argument added to or dropped from one side)."""
+    from acfm_video_3d_reconstruction_amd import _lib
+    protos = _prototypes()
+    assert set(protos) == set(_declared_symbols()), "a prototype the pattern does not parse"
+    assert set(protos) == set(_lib.SIGNATURES)
+    short = lambda sig: "%s(%s)" % (sig[0].__name__, ", ".join(k.__name__ for k in sig[1]))
+    bad = ["%s: header %d parameters %s, table %d parameters %s" % (n, len(h[1]), short(h), len(t[1]), short(t))
+           for n, h in sorted(protos.items()) for t in [_lib.SIGNATURES[n]] if h != (t[0], list(t[1]))]
+    assert not bad, "\n".join(bad)
+
+
+def test_mirrored_structures_match_the_header():
+    from acfm_video_3d_reconstruction_amd import _lib
+    pairs = [(_lib.RasterTuning, "AcfmRasterTuning"), (_lib.SilExtras, "AcfmSilExtras"),
+             (_lib.BlendParams, "AcfmBlendParams"), (_lib.StepMaskJob, "acfm_step_mask_job"),
+             (_lib.StepTexJob, "acfm_step_tex_job"), (_lib.StepBdsJob, "acfm_step_bds_job"),
+             (_lib.StepTotalJob, "acfm_step_total_job")]
+    for cls, name in pairs:
+        assert [f[0] for f in cls._fields_] == _struct_fields(name), name
+
+
+def test_mirrored_constants_match_the_header():
+    from acfm_video_3d_reconstruction_amd import _lib, ops
+    from acfm_video_3d_reconstruction_amd.ops import base
+    d = _defines()
+    assert _lib.PROF_NKERNELS == d["ACFM_PROF_NKERNELS"]
+    assert set(_lib._ERR) == {d["ACFM_E_BADARG"], d["ACFM_E_LAUNCH"], d["ACFM_E_WORKSPACE"]} and d["ACFM_OK"] == 0
+    assert [_lib._ERR[d[k]].split()[0] for k in ("ACFM_E_BADARG", "ACFM_E_LAUNCH", "ACFM_E_WORKSPACE")] == \
+        ["ACFM_E_BADARG", "ACFM_E_LAUNCH", "ACFM_E_WORKSPACE"]
+    assert _lib.raster_tuning(deterministic=True).t.flags == d["ACFM_DETERMINISTIC"] == 1
+    assert _lib.with_f16(None, True).flags == d["ACFM_STORE_F16"] == 2
+    assert _lib.with_cover(None, True).flags == d["ACFM_RECORD_COVER"] == 4
+    assert ops.SOLVE_INFO_HANDOFF == d["ACFM_SOLVE_INFO_HANDOFF"]
+    assert ops.GEODESIC_MAX_STEINER == d["ACFM_GEODESIC_MAX_STEINER"]
+    assert ops.GEODESIC_LDS_MAX == d["ACFM_GEODESIC_LDS_MAX"]
+    assert (base._LOSS_MASK, base._LOSS_TEX_MSE, base._LOSS_BDS) == \
+        (d["ACFM_LOSS_MASK"], d["ACFM_LOSS_TEX_MSE"], d["ACFM_LOSS_BDS"]) == (0, 1, 2)
+
+
+def test_a_library_of_another_version_is_refused_at_load(tmp_path):
+    """ACFM_LIB pointing at a build that reports another acfm_version(): _lib.lib() raises before it binds any other
+    symbol (the 2.x entry points keep 1.x names with other argument lists), naming the file, both versions and the
+    rebuild command.  The stand-in exports acfm_version alone, so reaching any other symbol would be an AttributeError."""
+    import shutil
+    import subprocess
+    import sys
+    from acfm_video_3d_reconstruction_amd import _lib
+    cc = next(c for c in (shutil.which("cc"), shutil.which("gcc"), shutil.which("clang")) if c)
+    src, so = tmp_path / "stale.c", tmp_path / "libacfm_stale.so"
+    src.write_text("int acfm_version(void) { return 1001; }\n")
+    subprocess.check_call([cc, "-shared", "-fPIC", "-o", str(so), str(src)])
+    r = subprocess.run([sys.executable, "-c", "from acfm_video_3d_reconstruction_amd import _lib; _lib.lib()"],
+                       cwd=ROOT, env=dict(os.environ, ACFM_LIB=str(so)), capture_output=True, text=True)
+    assert r.returncode != 0
+    assert _lib.ABI_VERSION == 2000
+    last = r.stderr.strip().splitlines()[-1]
+    assert last.startswith("RuntimeError:") and str(so) in last and "1001" in last and "2000" in last, r.stderr
+    assert "make -C" in last and _lib.CSRC in last, r.stderr
 
 
 def test_library_exports_every_declared_symbol():

@@ -1,4 +1,4 @@
-"""GPU: the per-mesh loss sums in one launch (acfm_mask_losses_ws, acfm_tex_mse_ws, acfm_bds_loss_ws; behind
+"""GPU: the per-mesh loss sums in one launch (acfm_mask_losses, acfm_tex_mse, acfm_bds_loss given tickets; behind
 ops.mask_losses, ops.tex_mse and ops.bds_loss_per_mesh) -- every workgroup hands its partial sums over in a
 persistent scratch, the one that draws a mesh's last ticket adds them in workgroup order.  Checked here: the same
 bits on every call, values against the float64 references at the tolerances of test_gpu_loss_shapes.py, the ticket
@@ -95,7 +95,7 @@ def test_same_inputs_same_bits_and_float64_values(N, RB, H, W, P, V):
 
 
 def _c_three(lib, t, N, RB, HW, P, V, scratch):
-    """The three losses through the C ABI on caller-owned (tickets, partials) (None: the plain entry points)."""
+    """The three losses through the C ABI on caller-owned (tickets, partials) (None: the zero-fill + atomics form)."""
     from acfm_video_3d_reconstruction_amd import _lib
     d = t["mask"].device
     st = _lib.cur_stream(d)
@@ -104,18 +104,12 @@ def _c_three(lib, t, N, RB, HW, P, V, scratch):
     b = torch.full((N,), 7.0, device=d)
     c = torch.full((N,), 7.0, device=d)
     arg = torch.empty((N, P), dtype=torch.int32, device=d)
-    if scratch is None:
-        _lib.check(lib.acfm_mask_losses(p(t["mask"]), p(t["gt"]), p(t["edt"]), N, HW, RB, p(a), st), "mask")
-        _lib.check(lib.acfm_tex_mse(p(t["tex"]), p(t["img"]), p(t["m"]), N, HW, RB, p(b), st), "tex")
-        _lib.check(lib.acfm_bds_loss(p(t["xy"]), p(t["bds"]), p(t["vis"]), N, V, P, RB, p(c), p(arg), st), "bds")
-    else:
-        tk, part = scratch
-        nf = part.numel()
-        _lib.check(lib.acfm_mask_losses_ws(p(t["mask"]), p(t["gt"]), p(t["edt"]), N, HW, RB, p(a), p(tk), p(part), nf, st),
-                   "mask")
-        _lib.check(lib.acfm_tex_mse_ws(p(t["tex"]), p(t["img"]), p(t["m"]), N, HW, RB, p(b), p(tk), p(part), nf, st), "tex")
-        _lib.check(lib.acfm_bds_loss_ws(p(t["xy"]), p(t["bds"]), p(t["vis"]), N, V, P, RB, p(c), p(arg), p(tk), p(part), nf,
-                                        st), "bds")
+    tk, part = scratch if scratch is not None else (None, None)
+    nf = part.numel() if part is not None else 0
+    _lib.check(lib.acfm_mask_losses(p(t["mask"]), p(t["gt"]), p(t["edt"]), N, HW, RB, p(a), p(tk), p(part), nf, st), "mask")
+    _lib.check(lib.acfm_tex_mse(p(t["tex"]), p(t["img"]), p(t["m"]), N, HW, RB, p(b), p(tk), p(part), nf, st), "tex")
+    _lib.check(lib.acfm_bds_loss(p(t["xy"]), p(t["bds"]), p(t["vis"]), None, N, V, P, RB, 0, 0, p(c), p(arg), p(tk), p(part),
+                                 nf, st), "bds")
     return a, b, c, arg
 
 
@@ -155,9 +149,9 @@ def test_tickets_reset_themselves_on_one_scratch():
     t, N, RB, HW, P, V = data[0]
     o = torch.empty((N, 4), device=d)
     args = (_lib.ptr(t["mask"]), _lib.ptr(t["gt"]), _lib.ptr(t["edt"]), N, HW, RB, _lib.ptr(o))
-    assert lib.acfm_mask_losses_ws(*args, _lib.ptr(tickets), _lib.ptr(partials), 4 * 64 * 8 - 1, _lib.cur_stream(d)) == 3
-    assert lib.acfm_mask_losses_ws(*args, None, _lib.ptr(partials), need, _lib.cur_stream(d)) == 1
-    assert lib.acfm_mask_losses_ws(*args, _lib.ptr(tickets), None, need, _lib.cur_stream(d)) == 1
+    assert lib.acfm_mask_losses(*args, _lib.ptr(tickets), _lib.ptr(partials), 4 * 64 * 8 - 1, _lib.cur_stream(d)) == 3
+    assert lib.acfm_mask_losses(*args, None, _lib.ptr(partials), need, _lib.cur_stream(d)) == 1
+    assert lib.acfm_mask_losses(*args, _lib.ptr(tickets), None, need, _lib.cur_stream(d)) == 1
 
 
 def test_captured_graph_of_the_three_losses_replays_to_the_eager_bits():
@@ -243,8 +237,8 @@ def test_boundary_loss_is_bit_equal_to_the_recorded_parent():
         assert loss.detach().cpu().numpy().tobytes() == g["c%d_loss" % i].tobytes(), i
         l2 = torch.full((N,), -1.0, device=d)
         a2 = torch.empty((N, P), dtype=torch.int32, device=d)
-        _lib.call("acfm_bds_loss", d, _lib.ptr(txy.detach()), _lib.ptr(tb), _lib.ptr(tvis), N, V, P, RB, _lib.ptr(l2),
-                  _lib.ptr(a2))
+        _lib.call("acfm_bds_loss", d, _lib.ptr(txy.detach()), _lib.ptr(tb), _lib.ptr(tvis), None, N, V, P, RB, 0, 0,
+                  _lib.ptr(l2), _lib.ptr(a2), None, None, 0)
         np.testing.assert_array_equal(a2.cpu().numpy(), g["c%d_argmin" % i])
         assert l2.cpu().numpy().tobytes() == g["c%d_loss" % i].tobytes(), i
         assert np.all(g["c%d_argmin" % i][N - 1] == -1)

@@ -1,4 +1,4 @@
-"""GPU: k_tex_mse reads the mask first and the colour planes only where the mask is not zero (acfm_tex_mse_ws behind
+"""GPU: k_tex_mse reads the mask first and the colour planes only where the mask is not zero (acfm_tex_mse behind
 ops.tex_mse / loss_utils.masked_texture_mse).  The result is what it was for finite inputs: against the float64 torch
 expression at the tolerance of tests/test_gpu_losses.py::test_masked_texture_mse, bit for bit against itself when the
 colours under a zero mask change, and exactly 0 for an all-zero mask.  Masks put single pixels on both sides of a

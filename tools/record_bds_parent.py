@@ -1,11 +1,12 @@
-"""Record tests/golden/bds_parent.npz: what a given build of libacfm_hip.so answers to acfm_bds_loss (the plain
-entry point) on inputs made to pin its tie rule -- the fixture tests/test_gpu_loss_reductions.py compares later
-builds with, bit for bit.
+"""Record tests/golden/bds_parent.npz: what a given build of libacfm_hip.so answers to acfm_bds_loss (every point,
+the zero-fill + atomics finish) on inputs made to pin its tie rule -- the fixture
+tests/test_gpu_loss_reductions.py compares later builds with, bit for bit.
 
     python tools/record_bds_parent.py --lib PATH/libacfm_hip.so [--out tests/golden/bds_parent.npz]
 
 Run it with the library of the commit BEFORE a change to k_bds_loss.  It loads the library by itself (ctypes, no
-package import), so any build that exports acfm_bds_loss will do.
+package import), so any build of the 2.x ABI will do; a library that reports another acfm_version() has other argument
+lists behind the same names and is refused.
 
 The inputs: vertices and boundary points on the grid k / 16, k in [-16, 16] -- many vertices coincide and many
 points are equally far from several vertices, so the answer depends on the tie rule (first nearest vertex in
@@ -21,6 +22,7 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ABI_VERSION = 2000   # acfm_version() of the header the signature below is taken from
 # (N, ref_batch, V, P)
 CASES = [(3, 3, 37, 70), (4, 2, 642, 800), (3, 1, 2562, 1537), (2, 2, 3, 1), (3, 3, 65, 64)]
 
@@ -52,8 +54,13 @@ def main():
     a = ap.parse_args()
     lib = ctypes.CDLL(os.path.abspath(a.lib))
     vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.acfm_version.restype, lib.acfm_version.argtypes = ci, []
+    if lib.acfm_version() != ABI_VERSION:
+        raise SystemExit("%s reports acfm_version() = %d, this tool binds version %d of include/acfm_hip.h: record with "
+                         "the tool of the library's own commit, or rebuild the library (make -C "
+                         "acfm_video_3d_reconstruction_amd/csrc)" % (a.lib, lib.acfm_version(), ABI_VERSION))
     lib.acfm_bds_loss.restype = ci
-    lib.acfm_bds_loss.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]
+    lib.acfm_bds_loss.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ctypes.c_size_t, vp]
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(20240)
     out = {}
@@ -63,8 +70,8 @@ def main():
         tv, tb, tvis = torch.from_numpy(v).to(dev), torch.from_numpy(b).to(dev), torch.from_numpy(vis).to(dev)
         loss = torch.empty(N, dtype=torch.float32, device=dev)
         arg = torch.empty((N, P), dtype=torch.int32, device=dev)
-        rc = lib.acfm_bds_loss(tv.data_ptr(), tb.data_ptr(), tvis.data_ptr(), N, V, P, RB, loss.data_ptr(),
-                               arg.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        rc = lib.acfm_bds_loss(tv.data_ptr(), tb.data_ptr(), tvis.data_ptr(), None, N, V, P, RB, 0, 0, loss.data_ptr(),
+                               arg.data_ptr(), None, None, 0, torch.cuda.current_stream().cuda_stream)
         assert rc == 0, rc
         torch.cuda.synchronize()
         for k, x in (("xy", xy), ("bd", bd), ("flag", flag), ("vis", vis), ("loss", loss.cpu().numpy()),

@@ -1,6 +1,6 @@
 """Record tests/golden/loss_sums_parent.npz: what a given build of libacfm_hip.so answers to the one-launch forms of the
-masked texture MSE and the silhouette losses (ops.tex_mse, ops.mask_losses: acfm_tex_mse_ws, acfm_mask_losses_ws, whose
-sums are added in a fixed order) on seeded inputs -- the fixture tests/test_gpu_loss_bits_parent.py compares later
+masked texture MSE and the silhouette losses (ops.tex_mse, ops.mask_losses: acfm_tex_mse, acfm_mask_losses given tickets,
+whose sums are added in a fixed order) on seeded inputs -- the fixture tests/test_gpu_loss_bits_parent.py compares later
 builds with, bit for bit.
 
     ACFM_LIB=PATH/libacfm_hip.so python tools/record_loss_parent.py [--out tests/golden/loss_sums_parent.npz]
