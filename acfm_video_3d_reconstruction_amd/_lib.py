@@ -16,144 +16,151 @@ CSRC = os.path.join(_HERE, "csrc")
 ABI_VERSION = 2000  # acfm_version() of the header these signatures mirror; lib() refuses any other build
 
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+# Device pointers with the header's element type: ctypes binds them as c_void_p, call() checks a tensor's dtype against
+# them (size and float-versus-integer; signedness is not told apart).  _vp takes a tensor of any dtype: void*, the
+# mirrored structures, pointer tables and host out-parameters.
+_pf, _pd, _p1, _p4, _p8 = "float*", "double*", "int8*", "int32*", "int64*"
+_ELEMENTS = {_pf: (torch.float32,), _pd: (torch.float64,), _p1: (torch.uint8, torch.int8, torch.bool),
+             _p4: (torch.int32, torch.uint32), _p8: (torch.int64, torch.uint64)}
 
-# name -> (restype, argtypes); must list every symbol of include/acfm_hip.h
+# name -> (restype, parameters); must list every symbol of include/acfm_hip.h
 SIGNATURES = {
     "acfm_version": (_i, []),
     "acfm_arch": (ctypes.c_char_p, []),
     "acfm_prof_enable": (_i, [_i]),
     "acfm_prof_collect": (_i, [_vp, _vp, _i]),
     "acfm_prof_name": (ctypes.c_char_p, [_i]),
-    "acfm_project": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp]),
-    "acfm_project_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
-    "acfm_project_xy": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp]),
-    "acfm_project_xy_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
-    "acfm_deform_apply": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "acfm_deform_apply_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "acfm_deform_presolve_sums_f64": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "acfm_correlation_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_correlation_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "acfm_deform_conv2d_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_project": (_i, [_pf, _pf, _i, _i, _f, _pf, _vp]),
+    "acfm_project_backward": (_i, [_pf, _pf, _pf, _i, _i, _pf, _pf, _vp]),
+    "acfm_project_xy": (_i, [_pf, _pf, _i, _i, _f, _pf, _vp]),
+    "acfm_project_xy_backward": (_i, [_pf, _pf, _pf, _i, _i, _pf, _pf, _vp]),
+    "acfm_deform_apply": (_i, [_pf, _pf, _pf, _i, _i, _i, _pf, _vp]),
+    "acfm_deform_apply_backward": (_i, [_pf, _pf, _pf, _i, _i, _i, _pf, _pf, _pf, _vp]),
+    "acfm_deform_presolve_sums_f64": (_i, [_pf, _pf, _i, _i, _i, _pd, _pd, _pf, _vp]),
+    "acfm_correlation_forward": (_i, [_pf, _pf, _i, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_correlation_backward": (_i, [_pf, _pf, _pf, _i, _i, _i, _i, _i, _pf, _pf, _vp]),
+    "acfm_deform_conv2d_forward": (_i, [_pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _pf, _vp]),
     "acfm_deform_conv2d_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "acfm_deform_conv2d_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "acfm_of_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "acfm_of_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_camera_pipeline": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
-    "acfm_camera_pipeline_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
-    "acfm_camera_mirror": (_i, [_vp, _i, _vp, _vp]),
-    "acfm_camera_pipeline_tables": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
-    "acfm_camera_pipeline_tables_backward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
-    "acfm_camera_pipeline_azel": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp]),
-    "acfm_camera_pipeline_azel_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp]),
-    "acfm_camera_pipeline_azel_tables": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp]),
-    "acfm_camera_pipeline_azel_tables_backward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f,
+    "acfm_deform_conv2d_backward": (_i, [_pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _pf, _pf, _pf, _pf, _vp, _sz, _vp]),
+    "acfm_of_loss": (_i, [_pf, _pf, _pf, _p1, _i, _i, _i, _i, _i, _i, _i, _pf, _pf, _vp]),
+    "acfm_of_loss_backward": (_i, [_pf, _pf, _pf, _p1, _pf, _pf, _i, _i, _i, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_camera_pipeline": (_i, [_pf, _p8, _pf, _i, _i, _f, _pf, _vp]),
+    "acfm_camera_pipeline_backward": (_i, [_pf, _p8, _pf, _pf, _i, _i, _f, _pf, _vp]),
+    "acfm_camera_mirror": (_i, [_pf, _i, _pf, _vp]),
+    "acfm_camera_pipeline_tables": (_i, [_vp, _i, _i, _p8, _p8, _p8, _pf, _i, _i, _f, _pf, _vp]),
+    "acfm_camera_pipeline_tables_backward": (_i, [_vp, _i, _i, _p8, _p8, _p8, _pf, _pf, _i, _i, _f, _vp, _vp]),
+    "acfm_camera_pipeline_azel": (_i, [_pf, _p8, _pf, _i, _i, _f, _f, _f, _f, _f, _pf, _vp]),
+    "acfm_camera_pipeline_azel_backward": (_i, [_pf, _p8, _pf, _pf, _i, _i, _f, _f, _f, _f, _f, _pf, _vp]),
+    "acfm_camera_pipeline_azel_tables": (_i, [_vp, _i, _i, _p8, _p8, _p8, _pf, _i, _i, _f, _f, _f, _f, _f, _pf, _vp]),
+    "acfm_camera_pipeline_azel_tables_backward": (_i, [_vp, _i, _i, _p8, _p8, _p8, _pf, _pf, _i, _i, _f, _f, _f, _f, _f,
                                                        _vp, _vp]),
-    "acfm_camera_normalize": (_i, [_vp, _i, _vp, _vp]),
-    "acfm_camera_normalize_backward": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "acfm_camera_normalize": (_i, [_pf, _i, _pf, _vp]),
+    "acfm_camera_normalize_backward": (_i, [_pf, _pf, _i, _pf, _vp]),
     "acfm_deform_solve_workspace_bytes": (_sz, [_i, _i]),
-    "acfm_deform_solve": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
-    "acfm_deform_solve_backward": (_i, [_vp, _i, _i, _vp, _sz, _vp, _vp]),
+    "acfm_deform_solve": (_i, [_pf, _pf, _i, _i, _pf, _vp, _sz, _vp]),
+    "acfm_deform_solve_backward": (_i, [_pf, _i, _i, _vp, _sz, _pf, _vp]),
     "acfm_deform_solve_info": (_i, [_vp, _sz, _i, _vp, _vp]),
     "acfm_deform_solve_info_offset": (_sz, [_i]),
     "acfm_raster_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "acfm_stream_capture_id": (_i, [_vp, _vp]),
-    "acfm_sil_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp,
+    "acfm_sil_forward": (_i, [_pf, _p8, _pf, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _p8, _p1, _vp,
                               _sz, _vp, _vp, _vp]),
-    "acfm_sil_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp,
+    "acfm_sil_backward": (_i, [_pf, _p8, _pf, _vp, _p8, _pf, _i, _i, _i, _i, _f, _f, _f, _pf, _pf, _vp,
                                _sz, _i, _vp, _vp, _vp]),
-    "acfm_sil_loss_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp,
-                                   _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
-    "acfm_sil_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _f, _f, _vp,
-                                    _vp, _vp, _sz, _i, _vp, _vp, _vp]),
-    "acfm_hard_raster": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "acfm_sil_loss_forward": (_i, [_pf, _p8, _pf, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _p8,
+                                   _p1, _pf, _vp, _sz, _vp, _vp, _vp]),
+    "acfm_sil_loss_backward": (_i, [_pf, _p8, _pf, _vp, _p8, _vp, _vp, _i, _pf, _i, _i, _i, _i, _f, _f, _f, _pf,
+                                    _pf, _vp, _sz, _i, _vp, _vp, _vp]),
+    "acfm_hard_raster": (_i, [_pf, _p8, _i, _i, _i, _i, _p8, _p1, _vp, _sz, _vp, _vp]),
     "acfm_rasterize_fragments_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "acfm_rasterize_fragments": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "acfm_rasterize_fragments_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp,
+    "acfm_rasterize_fragments": (_i, [_pf, _p8, _i, _i, _i, _i, _i, _f, _i, _p8, _pf, _pf, _pf, _vp, _sz, _vp, _vp]),
+    "acfm_rasterize_fragments_backward": (_i, [_pf, _p8, _p8, _pf, _pf, _pf, _i, _i, _i, _i, _i, _f, _i, _pf, _vp,
                                                _sz, _i, _vp, _vp]),
-    "acfm_sigmoid_alpha_blend": (_i, [_vp, _vp, _vp, _sz, _i, _f, _vp, _vp, _vp]),
-    "acfm_sigmoid_alpha_blend_backward": (_i, [_vp, _vp, _vp, _sz, _i, _f, _vp, _vp, _vp, _vp]),
-    "acfm_softmax_rgb_blend": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp]),
-    "acfm_softmax_rgb_blend_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i, _vp, _vp, _vp,
-                                             _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "acfm_interpolate_face_attributes": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _vp, _vp, _vp]),
-    "acfm_interpolate_face_attributes_backward": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp, _vp, _vp, _sz, _vp,
+    "acfm_sigmoid_alpha_blend": (_i, [_p8, _pf, _pf, _sz, _i, _f, _pf, _vp, _vp]),
+    "acfm_sigmoid_alpha_blend_backward": (_i, [_p8, _pf, _pf, _sz, _i, _f, _pf, _pf, _vp, _vp]),
+    "acfm_softmax_rgb_blend": (_i, [_p8, _pf, _pf, _pf, _pf, _pf, _i, _i, _pf, _sz, _i, _i, _vp, _pf, _vp, _vp]),
+    "acfm_softmax_rgb_blend_backward": (_i, [_p8, _pf, _pf, _pf, _pf, _pf, _i, _i, _pf, _sz, _i, _i, _vp, _pf, _pf,
+                                             _pf, _pf, _pf, _vp, _sz, _vp, _vp]),
+    "acfm_interpolate_face_attributes": (_i, [_p8, _pf, _pf, _sz, _i, _i, _i, _pf, _vp, _vp]),
+    "acfm_interpolate_face_attributes_backward": (_i, [_p8, _pf, _pf, _pf, _sz, _i, _i, _i, _pf, _pf, _vp, _sz, _vp,
                                                        _vp]),
-    "acfm_uv_texels": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "acfm_uv_texels_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+    "acfm_uv_texels": (_i, [_p8, _pf, _pf, _pf, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _pf, _vp, _vp]),
+    "acfm_uv_texels_backward": (_i, [_p8, _pf, _pf, _pf, _pf, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _pf, _pf, _pf, _vp,
                                      _sz, _vp, _vp]),
-    "acfm_tex_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp,
+    "acfm_tex_forward": (_i, [_pf, _p8, _pf, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _p4,
                               _vp, _sz, _i, _f, _i, _vp, _vp]),
-    "acfm_vertex_color_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz,
+    "acfm_vertex_color_forward": (_i, [_pf, _p8, _pf, _pf, _i, _i, _i, _i, _f, _f, _f, _pf, _pf, _p8, _vp, _sz,
                                        _i, _f, _vp, _vp]),
-    "acfm_tex_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_tex_backward_faces": (_i, [_vp, _vp, _vp, _sz, _f, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_tex_mse_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp,
-                                  _vp, _vp, _sz, _i, _f, _i, _vp, _vp]),
-    "acfm_tex_mse_backward_faces": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _f, _i, _i, _i, _i, _i, _i, _vp, _vp,
+    "acfm_tex_backward": (_i, [_pf, _p4, _i, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_tex_backward_faces": (_i, [_pf, _p4, _vp, _sz, _f, _i, _i, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_tex_mse_forward": (_i, [_pf, _p8, _pf, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _p4,
+                                  _pf, _vp, _sz, _i, _f, _i, _vp, _vp]),
+    "acfm_tex_mse_backward_faces": (_i, [_vp, _vp, _vp, _i, _pf, _p4, _vp, _sz, _f, _i, _i, _i, _i, _i, _i, _pf, _vp,
                                          _vp]),
-    "acfm_combine_losses": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "acfm_combine_losses_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "acfm_hypothesis_total": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "acfm_hypothesis_total_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "acfm_combine_losses": (_i, [_vp, _p4, _pf, _i, _i, _pf, _vp]),
+    "acfm_combine_losses_backward": (_i, [_pf, _vp, _p4, _pf, _i, _i, _vp]),
+    "acfm_hypothesis_total": (_i, [_vp, _pf, _p4, _pf, _i, _i, _i, _pf, _pf, _pf, _pf, _pf, _vp]),
+    "acfm_hypothesis_total_backward": (_i, [_pf, _pf, _pf, _i, _i, _i, _vp, _vp]),
     "acfm_texture_cycle_scratch_floats": (_sz, [_i, _i, _i, _i]),
-    "acfm_texture_cycle": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "acfm_texture_cycle_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_texture_cycle": (_i, [_pf, _i, _i, _i, _i, _pf, _pf, _vp]),
+    "acfm_texture_cycle_backward": (_i, [_pf, _pf, _pf, _i, _i, _i, _i, _pf, _vp]),
     "acfm_loss_partial_floats": (_sz, [_i, _i, _i]),
-    "acfm_mask_losses": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "acfm_mask_losses": (_i, [_pf, _pf, _pf, _i, _i, _i, _pf, _p4, _pf, _sz, _vp]),
     "acfm_step_losses_ws": (_sz, [_i, _i, _i, _i, _vp]),
-    "acfm_step_losses_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
-    "acfm_mask_losses_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "acfm_tex_mse": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "acfm_tex_mse_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "acfm_cot_laplacian": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "acfm_step_losses_forward": (_i, [_vp, _vp, _vp, _vp, _i, _p4, _pf, _sz, _vp]),
+    "acfm_mask_losses_backward": (_i, [_pf, _pf, _pf, _pf, _i, _i, _i, _pf, _vp]),
+    "acfm_tex_mse": (_i, [_pf, _pf, _pf, _i, _i, _i, _pf, _p4, _pf, _sz, _vp]),
+    "acfm_tex_mse_backward": (_i, [_pf, _pf, _pf, _pf, _i, _i, _i, _pf, _vp]),
+    "acfm_cot_laplacian": (_i, [_pf, _p8, _i, _i, _pf, _vp]),
     "acfm_laplacian_smoothing_state_floats": (_sz, [_i, _i]),
-    "acfm_laplacian_smoothing": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "acfm_laplacian_smoothing_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_edge_rigidity": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "acfm_edge_rigidity_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "acfm_laplacian_smoothing": (_i, [_pf, _p8, _pf, _i, _i, _i, _i, _i, _pf, _pf, _vp]),
+    "acfm_laplacian_smoothing_backward": (_i, [_p8, _pf, _pf, _i, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_edge_rigidity": (_i, [_pf, _p8, _pf, _p8, _i, _pf, _vp]),
+    "acfm_edge_rigidity_backward": (_i, [_pf, _p8, _pf, _p8, _i, _i, _i, _i, _pf, _pf, _pf, _vp]),
     "acfm_edt_workspace_bytes": (_sz, [_i, _i, _i]),
-    "acfm_edt": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "acfm_boundaries": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "acfm_visible_vertices": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_bds_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "acfm_bds_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_boundary_subset": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_edt": (_i, [_pf, _i, _i, _i, _i, _pf, _vp, _sz, _vp]),
+    "acfm_boundaries": (_i, [_pf, _i, _i, _i, _i, _pf, _p4, _vp]),
+    "acfm_visible_vertices": (_i, [_p8, _p8, _i, _i, _i, _i, _i, _p1, _vp]),
+    "acfm_bds_loss": (_i, [_pf, _pf, _p1, _p4, _i, _i, _i, _i, _i, _i, _pf, _p4, _p4, _pf, _sz, _vp]),
+    "acfm_bds_loss_backward": (_i, [_pf, _pf, _p4, _p4, _pf, _i, _i, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_boundary_subset": (_i, [_p8, _p4, _i, _i, _i, _i, _p4, _vp]),
     "acfm_chamfer_partial_floats": (_sz, [_i, _i, _i]),
-    "acfm_chamfer": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "acfm_chamfer_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "acfm_chamfer": (_i, [_pf, _pf, _p8, _p8, _i, _i, _i, _pf, _p4, _p4, _p4, _pf, _sz, _vp]),
+    "acfm_chamfer_backward": (_i, [_pf, _pf, _p8, _p8, _p4, _p4, _pf, _i, _i, _i, _pf, _pf, _vp]),
     "acfm_mesh_term_partial_floats": (_sz, [_i]),
-    "acfm_edge_length_loss": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
-    "acfm_edge_length_loss_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
-    "acfm_normal_consistency": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "acfm_normal_consistency_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "acfm_uv_atlas_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_uv_atlas_taps": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "acfm_uv_atlas_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "acfm_edge_length_loss": (_i, [_pf, _p8, _pf, _i, _i, _f, _pf, _p4, _pf, _sz, _vp]),
+    "acfm_edge_length_loss_backward": (_i, [_pf, _p8, _pf, _pf, _i, _i, _f, _pf, _vp]),
+    "acfm_normal_consistency": (_i, [_pf, _p8, _pf, _i, _i, _pf, _p4, _pf, _sz, _vp]),
+    "acfm_normal_consistency_backward": (_i, [_pf, _p8, _pf, _pf, _i, _i, _pf, _vp]),
+    "acfm_uv_atlas_forward": (_i, [_pf, _pf, _i, _i, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_uv_atlas_taps": (_i, [_pf, _i, _i, _i, _p4, _vp]),
+    "acfm_uv_atlas_backward": (_i, [_pf, _pf, _pf, _p4, _p4, _i, _i, _i, _i, _i, _i, _i, _pf, _vp]),
     "acfm_geodesic_lds_bytes": (_sz, [_i, _i, _i]),
-    "acfm_geodesic_distances": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "acfm_geodesic_distances": (_i, [_pf, _p4, _p4, _p4, _i, _i, _i, _i, _i, _p4, _i, _pf, _p4, _vp]),
     "acfm_geodesic_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
-    "acfm_geodesic_distances_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
-    "acfm_lpips_input_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_lpips_input_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_lpips_layer_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "acfm_lpips_layer_backward": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp]),
-    "acfm_lpips_mask_weights": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "acfm_lpips_masked_mean_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "acfm_lpips_masked_mean_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "acfm_kp_weights_forward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
-    "acfm_kp_weights_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "acfm_kp_head_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "acfm_geodesic_distances_dev": (_i, [_pf, _p4, _p4, _p4, _i, _i, _i, _i, _i, _p4, _i, _pf, _p4, _i, _vp, _sz, _vp]),
+    "acfm_lpips_input_forward": (_i, [_pf, _pf, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_lpips_input_backward": (_i, [_pf, _pf, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_lpips_layer_forward": (_i, [_pf, _pf, _pf, _i, _i, _i, _i, _pf, _sz, _vp]),
+    "acfm_lpips_layer_backward": (_i, [_pf, _pf, _pf, _pf, _sz, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_lpips_mask_weights": (_i, [_pf, _i, _i, _i, _p4, _i, _pf, _vp]),
+    "acfm_lpips_masked_mean_forward": (_i, [_pf, _pf, _i, _i, _i, _pf, _vp]),
+    "acfm_lpips_masked_mean_backward": (_i, [_pf, _pf, _i, _i, _i, _pf, _vp]),
+    "acfm_kp_weights_forward": (_i, [_pf, _i, _i, _pf, _pf, _pf, _vp]),
+    "acfm_kp_weights_backward": (_i, [_pf, _pf, _pf, _pf, _pf, _i, _i, _pf, _vp]),
+    "acfm_kp_head_forward": (_i, [_pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _f, _pf, _pf, _pf, _pf, _vp]),
     "acfm_kp_head_workspace_bytes": (_sz, [_i, _i]),
-    "acfm_kp_head_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+    "acfm_kp_head_backward": (_i, [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _pf, _pf, _pf, _vp,
                                    _sz, _vp]),
-    "acfm_camera_loss_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
-    "acfm_camera_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]),
+    "acfm_camera_loss_forward": (_i, [_pf, _pf, _pf, _pf, _i, _i, _f, _pf, _p8, _vp]),
+    "acfm_camera_loss_backward": (_i, [_pf, _pf, _pf, _p8, _pf, _i, _f, _pf, _vp]),
 }
 
 _ERR = {1: "ACFM_E_BADARG (shape/parameter outside what the kernels support)",
         2: "ACFM_E_LAUNCH (HIP launch failed)", 3: "ACFM_E_WORKSPACE (workspace too small)"}
 
 _LIB = None
+_BOUND = {}   # name -> (bound function, pointer_kinds of its parameters), filled by lib()
 
 
 def build(verbose=False):
@@ -180,7 +187,8 @@ def lib():
                 "a build of another tree. Rebuild it with `make -C %s`." % (SO_PATH, found, ABI_VERSION, CSRC))
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
-            fn.restype, fn.argtypes = res, args
+            fn.restype, fn.argtypes = res, [_vp if type(a) is str else a for a in args]
+            _BOUND[name] = (fn, pointer_kinds(args))
         _LIB = handle
     return _LIB
 
@@ -209,11 +217,52 @@ def check(rc, what):
         raise RuntimeError("%s failed: %s" % (what, _ERR.get(rc, "error %d" % rc)))
 
 
+def pointer_kinds(params):
+    """What marshal() needs of a SIGNATURES entry's parameters: (their number, ((position, label, dtypes), ...) of the
+    pointers in front of the last parameter, the stream; dtypes None where any element type will do)."""
+    return len(params), tuple((i, "void*", None) if a is _vp else (i, a, _ELEMENTS[a])
+                              for i, a in enumerate(params[:-1]) if a is _vp or type(a) is str)
+
+
+def marshal(name, kinds, device, args):
+    """`args` of entry point `name` (all but the stream) as ctypes takes them: a tensor in a pointer position becomes
+    its address if it is on `device`, contiguous and of the element type the header declares (kinds = pointer_kinds of
+    the entry); None, ctypes values and numbers pass as they are.  Nothing is copied or converted.  Of a tensor only
+    get_device / is_contiguous / dtype / data_ptr / numel are asked, which a PendingTerm answers without its values."""
+    count, pointers = kinds
+    if len(args) + 1 != count:
+        raise TypeError("%s takes %d arguments, the stream included; got %d and the stream" % (name, count, len(args)))
+    out = list(args)
+    index = device.index if device.type == "cuda" else -1
+    for i, label, dtypes in pointers:
+        a = out[i]
+        if a is None or not isinstance(a, torch.Tensor):
+            continue
+        what = None
+        if a.get_device() != index:          # (-1 for a CPU tensor)
+            what = ValueError, "a tensor on %s in a call on %s" % (a.device, device)
+        elif not a.is_contiguous():
+            what = ValueError, "a non-contiguous tensor, shape %s strides %s" % (tuple(a.shape), a.stride())
+        elif dtypes is not None and a.dtype not in dtypes:
+            what = TypeError, "a %s tensor" % a.dtype
+        else:
+            out[i] = a.data_ptr()
+            if not out[i] and a.numel():   # a LazyGrad / LazyPixToFace: the caller was to form it, or not to pass it
+                what = ValueError, "a %s without storage" % type(a).__name__
+        if what:
+            raise what[0]("%s, parameter %d: the header declares %s, got %s" % (name, i, label, what[1]))
+    return out
+
+
 def call(name, device, *args):
-    """Entry point `name` on `device`, ordered on its current stream (appended as the last argument); raises on a
-    nonzero return code."""
+    """Entry point `name` on `device`, ordered on its current stream (appended as the last argument); tensors are
+    passed as they are and checked by marshal(); raises on a nonzero return code."""
+    if _LIB is None:
+        lib()
+    fn, kinds = _BOUND[name]
+    args = marshal(name, kinds, device, args)
     with torch.cuda.device(device):
-        check(getattr(lib(), name)(*args, cur_stream(device)), name)
+        check(fn(*args, cur_stream(device)), name)
 
 
 def require_gpu(*tensors):

@@ -23,7 +23,7 @@ def compute_dt(mask, norm=True):
     nb = _lib.lib().acfm_edt_workspace_bytes(N, H, W)
     ws = torch.empty(nb, dtype=torch.uint8, device=m.device)
     divisor = max(H, W) if norm else 1
-    _lib.call("acfm_edt", m.device, _lib.ptr(m), N, H, W, int(divisor), _lib.ptr(out), _lib.ptr(ws), nb)
+    _lib.call("acfm_edt", m.device, m, N, H, W, int(divisor), out, ws, nb)
     return out[0] if mask.dim() == 2 else out
 
 
@@ -53,7 +53,7 @@ def compute_boundaries(masks, cap=None, return_counts=False):
         raise ValueError("compute_boundaries: cap must be positive")
     out = torch.empty((N, cap, 3), dtype=torch.float32, device=m.device)
     counts = torch.empty((N,), dtype=torch.int32, device=m.device)
-    _lib.call("acfm_boundaries", m.device, _lib.ptr(m), N, H, W, cap, _lib.ptr(out), _lib.ptr(counts))
+    _lib.call("acfm_boundaries", m.device, m, N, H, W, cap, out, counts)
     if not fixed:
         max_bd = int(counts.max().item())
         out = out[:, :max_bd].contiguous()

@@ -23,8 +23,7 @@ class _OFLoss(torch.autograd.Function):
                                 None if mk is None else tuple(mk.shape), B, T))
         loss = torch.empty((B, T - 1), dtype=torch.float32, device=p.device)
         cnt = torch.empty((B, T - 1), dtype=torch.float32, device=p.device)
-        _lib.call("acfm_of_loss", p.device, _lib.ptr(p), _lib.ptr(fl), _lib.ptr(mk), _lib.ptr(vi), B, T, V, H, W,
-                  clips, int(bool(flip_t)), _lib.ptr(loss), _lib.ptr(cnt))
+        _lib.call("acfm_of_loss", p.device, p, fl, mk, vi, B, T, V, H, W, clips, int(bool(flip_t)), loss, cnt)
         ctx.save_for_backward(p, fl, vi, cnt) if mk is None else ctx.save_for_backward(p, fl, vi, cnt, mk)
         ctx.dims = (B, T, V, H, W, clips, int(bool(flip_t)), mk is not None)
         return loss
@@ -36,8 +35,7 @@ class _OFLoss(torch.autograd.Function):
         mk = ctx.saved_tensors[4] if has_m else None
         g = _f32c(g)
         gp = torch.empty_like(p)
-        _lib.call("acfm_of_loss_backward", p.device, _lib.ptr(p), _lib.ptr(fl), _lib.ptr(mk), _lib.ptr(vi),
-                  _lib.ptr(cnt), _lib.ptr(g), B, T, V, H, W, clips, flip_t, _lib.ptr(gp))
+        _lib.call("acfm_of_loss_backward", p.device, p, fl, mk, vi, cnt, g, B, T, V, H, W, clips, flip_t, gp)
         return gp, None, None, None, None, None, None
 
 
@@ -75,7 +73,7 @@ def _correlation_args(f1, f2, max_displacement):
 def _correlation_forward(a, b, md):
     N, C, H, W = a.shape
     out = torch.empty((N, (2 * md + 1) ** 2, H, W), dtype=torch.float32, device=a.device)
-    _lib.call("acfm_correlation_forward", a.device, _lib.ptr(a), _lib.ptr(b), N, C, H, W, md, _lib.ptr(out))
+    _lib.call("acfm_correlation_forward", a.device, a, b, N, C, H, W, md, out)
     return out
 
 
@@ -97,8 +95,7 @@ class _Correlation(torch.autograd.Function):
         go = _f32c(g)
         g1 = torch.empty_like(a) if ctx.needs_input_grad[0] else None
         g2 = torch.empty_like(b) if ctx.needs_input_grad[1] else None
-        _lib.call("acfm_correlation_backward", a.device, _lib.ptr(go), _lib.ptr(a), _lib.ptr(b), N, C, H, W, ctx.md,
-                  _lib.ptr(g1), _lib.ptr(g2))
+        _lib.call("acfm_correlation_backward", a.device, go, a, b, N, C, H, W, ctx.md, g1, g2)
         return (None if g1 is None else g1.to(ctx.dtypes[0]), None if g2 is None else g2.to(ctx.dtypes[1]), None)
 
 
@@ -140,8 +137,7 @@ def _dconv_args(input, offset, weight, bias, shared_offset):
 def _dconv_forward(x, o, w, b, shared_offset):
     (N, Cin, H, W), Cout = x.shape, w.shape[0]
     out = torch.empty((N, Cout, H, W), dtype=torch.float32, device=x.device)
-    _lib.call("acfm_deform_conv2d_forward", x.device, _lib.ptr(x), _lib.ptr(o), _lib.ptr(w), _lib.ptr(b), N, Cin, H, W,
-              Cout, 1 if shared_offset else 0, _lib.ptr(out))
+    _lib.call("acfm_deform_conv2d_forward", x.device, x, o, w, b, N, Cin, H, W, Cout, 1 if shared_offset else 0, out)
     return out
 
 
@@ -170,9 +166,8 @@ class _DeformConv2d(torch.autograd.Function):
         if gw is not None:
             nbytes = int(_lib.lib().acfm_deform_conv2d_backward_workspace_bytes(N, Cin, H, W, Cout))
             ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device)
-        _lib.call("acfm_deform_conv2d_backward", x.device, _lib.ptr(go), _lib.ptr(x), _lib.ptr(o), _lib.ptr(w), N, Cin, H,
-                  W, Cout, 1 if ctx.shared else 0, _lib.ptr(gx), _lib.ptr(goff), _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(ws),
-                  nbytes)
+        _lib.call("acfm_deform_conv2d_backward", x.device, go, x, o, w, N, Cin, H, W, Cout, 1 if ctx.shared else 0, gx,
+                  goff, gw, gb, ws, nbytes)
         return tuple(None if t is None else t.to(dt) for t, dt in zip((gx, goff, gw, gb), ctx.dtypes)) + (None,)
 
 

@@ -30,9 +30,8 @@ class _Fragments(torch.autograd.Function):
         nb = _lib.lib().acfm_rasterize_fragments_workspace_bytes(N, V, F, H)
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)
         tune = _lib.tuning()[1]
-        P = _lib.ptr
-        _lib.call("acfm_rasterize_fragments", dev, P(v), P(f), N, V, F, H, K, float(blur), int(clip), P(p2f), P(zbuf),
-                  P(bary), P(dists), P(ws), nb, _lib.tuning_ptr(tune))
+        _lib.call("acfm_rasterize_fragments", dev, v, f, N, V, F, H, K, float(blur), int(clip), p2f, zbuf, bary, dists,
+                  ws, nb, _lib.tuning_ptr(tune))
         ctx.save_for_backward(v, f, p2f)
         ctx.cfg = (H, K, float(blur), int(clip))
         ctx.ws = (ws, nb, tune)   # face records of the forward: the backward sets nothing up again
@@ -51,9 +50,8 @@ class _Fragments(torch.autograd.Function):
         N, V, _ = v.shape
         gz, gb, gd = (_f32c(g) if g is not None else None for g in (gzbuf, gbary, gdists))
         gv = torch.empty_like(v)
-        P = _lib.ptr
-        _lib.call("acfm_rasterize_fragments_backward", v.device, P(v), P(f), P(p2f), P(gz), P(gb), P(gd), N, V,
-                  f.shape[1], H, K, blur, clip, P(gv), P(ws), nb, 1, _lib.tuning_ptr(tune))
+        _lib.call("acfm_rasterize_fragments_backward", v.device, v, f, p2f, gz, gb, gd, N, V, f.shape[1], H, K, blur,
+                  clip, gv, ws, nb, 1, _lib.tuning_ptr(tune))
         return (gv,) + none
 
 
@@ -137,8 +135,7 @@ class _SigmoidBlend(torch.autograd.Function):
         c = _f32c(colors) if colors is not None else None
         rgba = torch.empty(p2f.shape[:-1] + (4,), dtype=torch.float32, device=p2f.device)
         tune = _lib.tuning()[1]
-        _lib.call("acfm_sigmoid_alpha_blend", p2f.device, _lib.ptr(p2f), _lib.ptr(d), _lib.ptr(c), P, K, float(sigma),
-                  _lib.ptr(rgba), _lib.tuning_ptr(tune))
+        _lib.call("acfm_sigmoid_alpha_blend", p2f.device, p2f, d, c, P, K, float(sigma), rgba, _lib.tuning_ptr(tune))
         ctx.save_for_backward(p2f, d)
         ctx.cfg = (P, K, float(sigma), tune)
         ctx.set_materialize_grads(False)
@@ -153,8 +150,8 @@ class _SigmoidBlend(torch.autograd.Function):
         P, K, sigma, tune = ctx.cfg
         gd = torch.empty_like(d) if need_d else None
         gc = torch.empty(p2f.shape + (3,), dtype=torch.float32, device=p2f.device) if need_c else None
-        _lib.call("acfm_sigmoid_alpha_blend_backward", p2f.device, _lib.ptr(p2f), _lib.ptr(d), _lib.ptr(_a16(g)), P, K,
-                  sigma, _lib.ptr(gd), _lib.ptr(gc), _lib.tuning_ptr(tune))
+        _lib.call("acfm_sigmoid_alpha_blend_backward", p2f.device, p2f, d, _a16(g), P, K, sigma, gd, gc,
+                  _lib.tuning_ptr(tune))
         return gc, gd, None, None
 
 
@@ -175,9 +172,8 @@ class _SoftmaxBlend(torch.autograd.Function):
         R, Fp = (a.shape[1], a.shape[0]) if a is not None else (0, 0)
         rgba = torch.empty((N, H, W, 4), dtype=torch.float32, device=p2f.device)
         tune = _lib.tuning()[1]
-        P_ = _lib.ptr
-        _lib.call("acfm_softmax_rgb_blend", p2f.device, P_(p2f), P_(d), P_(z), P_(b), P_(c), P_(a), R, Fp, P_(am), P,
-                  K, H * W, ctypes.byref(params), P_(rgba), _lib.tuning_ptr(tune))
+        _lib.call("acfm_softmax_rgb_blend", p2f.device, p2f, d, z, b, c, a, R, Fp, am, P, K, H * W,
+                  ctypes.byref(params), rgba, _lib.tuning_ptr(tune))
         ctx.save_for_backward(p2f, d, z, b, c, a, am)
         ctx.cfg = (P, K, H * W, R, Fp, params, tune)
         ctx.set_materialize_grads(False)
@@ -195,10 +191,8 @@ class _SoftmaxBlend(torch.autograd.Function):
         gd = torch.empty_like(d) if nig[2] else None
         gz = torch.empty_like(z) if nig[3] else None
         ws, nb = _det_ws(tune, a.numel(), a.device) if ga is not None else (None, 0)
-        P_ = _lib.ptr
-        _lib.call("acfm_softmax_rgb_blend_backward", p2f.device, P_(p2f), P_(d), P_(z), P_(b), P_(c), P_(a), R, Fp,
-                  P_(am), P, K, HW, ctypes.byref(params), P_(_a16(g)), P_(gd), P_(gz), P_(gc), P_(ga), P_(ws), nb,
-                  _lib.tuning_ptr(tune))
+        _lib.call("acfm_softmax_rgb_blend_backward", p2f.device, p2f, d, z, b, c, a, R, Fp, am, P, K, HW,
+                  ctypes.byref(params), _a16(g), gd, gz, gc, ga, ws, nb, _lib.tuning_ptr(tune))
         return gc, ga, gd, gz, None, None, None, None
 
 
@@ -213,8 +207,7 @@ class _Interpolate(torch.autograd.Function):
         Fp, D = fa.shape[0], fa.shape[2]
         out = torch.empty(p2f.shape + (D,), dtype=torch.float32, device=p2f.device)
         tune = _lib.tuning()[1]
-        _lib.call("acfm_interpolate_face_attributes", p2f.device, _lib.ptr(p2f), _lib.ptr(b), _lib.ptr(fa), P, K, Fp, D,
-                  _lib.ptr(out), _lib.tuning_ptr(tune))
+        _lib.call("acfm_interpolate_face_attributes", p2f.device, p2f, b, fa, P, K, Fp, D, out, _lib.tuning_ptr(tune))
         ctx.save_for_backward(p2f, b, fa)
         ctx.cfg = (P, K, Fp, D, tune)
         ctx.set_materialize_grads(False)
@@ -230,8 +223,8 @@ class _Interpolate(torch.autograd.Function):
         gb = torch.empty_like(b) if need_b else None
         ga = torch.empty_like(fa) if need_a else None
         ws, nb = _det_ws(tune, fa.numel(), fa.device) if need_a else (None, 0)
-        _lib.call("acfm_interpolate_face_attributes_backward", p2f.device, _lib.ptr(p2f), _lib.ptr(b), _lib.ptr(fa),
-                  _lib.ptr(_f32c(g)), P, K, Fp, D, _lib.ptr(gb), _lib.ptr(ga), _lib.ptr(ws), nb, _lib.tuning_ptr(tune))
+        _lib.call("acfm_interpolate_face_attributes_backward", p2f.device, p2f, b, fa, _f32c(g), P, K, Fp, D, gb, ga,
+                  ws, nb, _lib.tuning_ptr(tune))
         return gb, ga, None
 
 
@@ -314,9 +307,8 @@ class _UvTexels(torch.autograd.Function):
         Fp, Hm, Wm = fv.shape[0], m.shape[1], m.shape[2]
         out = torch.empty(p2f.shape + (3,), dtype=torch.float32, device=p2f.device)
         tune = _lib.tuning()[1]
-        P_ = _lib.ptr
-        _lib.call("acfm_uv_texels", p2f.device, P_(p2f), P_(b), P_(fv), P_(m), P, K, H * W, Fp, N, Hm, Wm, align, pad,
-                  P_(out), _lib.tuning_ptr(tune))
+        _lib.call("acfm_uv_texels", p2f.device, p2f, b, fv, m, P, K, H * W, Fp, N, Hm, Wm, align, pad, out,
+                  _lib.tuning_ptr(tune))
         ctx.save_for_backward(p2f, b, fv, m)
         ctx.cfg = (P, K, H * W, Fp, N, Hm, Wm, align, pad, tune)
         ctx.set_materialize_grads(False)
@@ -334,9 +326,8 @@ class _UvTexels(torch.autograd.Function):
         gm = torch.empty_like(m) if need_m else None
         n_acc = (fv.numel() if need_fv else 0) + (m.numel() if need_m else 0)
         ws, nb = _det_ws(tune, n_acc, p2f.device) if n_acc else (None, 0)
-        P_ = _lib.ptr
-        _lib.call("acfm_uv_texels_backward", p2f.device, P_(p2f), P_(b), P_(fv), P_(m), P_(_f32c(g)), P, K, HW, Fp, N,
-                  Hm, Wm, align, pad, P_(gm), P_(gb), P_(gfv), P_(ws), nb, _lib.tuning_ptr(tune))
+        _lib.call("acfm_uv_texels_backward", p2f.device, p2f, b, fv, m, _f32c(g), P, K, HW, Fp, N, Hm, Wm, align, pad,
+                  gm, gb, gfv, ws, nb, _lib.tuning_ptr(tune))
         return gb, gfv, gm, None, None, None
 
 

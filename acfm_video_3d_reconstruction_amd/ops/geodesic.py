@@ -111,8 +111,7 @@ def geodesic_distances(verts, faces, steiner=15, sources=None, memory="lds", max
     out = torch.empty((N, S, V), dtype=torch.float32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     if memory == "lds" or (memory == "auto" and fits):
-        _lib.call("acfm_geodesic_distances", dev, _lib.ptr(v3), _lib.ptr(f32), _lib.ptr(e32), _lib.ptr(fe32), N, V, F_, E,
-                  m, _lib.ptr(src), S, _lib.ptr(out), _lib.ptr(status))
+        _lib.call("acfm_geodesic_distances", dev, v3, f32, e32, fe32, N, V, F_, E, m, src, S, out, status)
     else:
         cap = int(max_workgroups or 0)
         with torch.cuda.device(dev):
@@ -121,8 +120,8 @@ def geodesic_distances(verts, faces, steiner=15, sources=None, memory="lds", max
             raise ValueError("geodesic_distances: no workspace size for N = %d, V = %d, E = %d, steiner = %d, S = %d"
                              % (N, V, E, m, S))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _lib.call("acfm_geodesic_distances_dev", dev, _lib.ptr(v3), _lib.ptr(f32), _lib.ptr(e32), _lib.ptr(fe32), N, V,
-                  F_, E, m, _lib.ptr(src), S, _lib.ptr(out), _lib.ptr(status), cap, _lib.ptr(ws), ws_bytes)
+        _lib.call("acfm_geodesic_distances_dev", dev, v3, f32, e32, fe32, N, V, F_, E, m, src, S, out, status, cap, ws,
+                  ws_bytes)
     if not capturing:       # (a captured call cannot read it: a workgroup that gave up leaves a row of NaN)
         st = int(status.item())
         if st:

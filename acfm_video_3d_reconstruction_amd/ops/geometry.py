@@ -16,7 +16,7 @@ class _Project(torch.autograd.Function):
         v, c = _f32c(verts), _f32c(cams)
         N, V, _ = v.shape
         out = torch.empty_like(v)
-        _lib.call("acfm_project", v.device, _lib.ptr(v), _lib.ptr(c), N, V, float(offset_z), _lib.ptr(out))
+        _lib.call("acfm_project", v.device, v, c, N, V, float(offset_z), out)
         ctx.save_for_backward(v, c)
         return out
 
@@ -27,8 +27,7 @@ class _Project(torch.autograd.Function):
         g = _f32c(g)
         gv = torch.empty_like(v) if ctx.needs_input_grad[0] else None
         gc = torch.empty_like(c) if ctx.needs_input_grad[1] else None
-        _lib.call("acfm_project_backward", v.device, _lib.ptr(v), _lib.ptr(c), _lib.ptr(g), N, V, _lib.ptr(gv),
-                  _lib.ptr(gc))
+        _lib.call("acfm_project_backward", v.device, v, c, g, N, V, gv, gc)
         return gv, gc, None
 
 
@@ -39,7 +38,7 @@ class _ProjectXY(torch.autograd.Function):
         v, c = _f32c(verts), _f32c(cams)
         N, V, _ = v.shape
         out = torch.empty((N, V, 2), dtype=torch.float32, device=v.device)
-        _lib.call("acfm_project_xy", v.device, _lib.ptr(v), _lib.ptr(c), N, V, float(offset_z), _lib.ptr(out))
+        _lib.call("acfm_project_xy", v.device, v, c, N, V, float(offset_z), out)
         ctx.save_for_backward(v, c)
         return out
 
@@ -50,8 +49,7 @@ class _ProjectXY(torch.autograd.Function):
         g = _f32c(g)
         gv = torch.empty_like(v) if ctx.needs_input_grad[0] else None
         gc = torch.empty_like(c) if ctx.needs_input_grad[1] else None
-        _lib.call("acfm_project_xy_backward", v.device, _lib.ptr(v), _lib.ptr(c), _lib.ptr(g), N, V, _lib.ptr(gv),
-                  _lib.ptr(gc))
+        _lib.call("acfm_project_xy_backward", v.device, v, c, g, N, V, gv, gc)
         return gv, gc, None
 
 
@@ -77,7 +75,7 @@ class _DeformApply(torch.autograd.Function):
         if p.shape != (V, Kh):
             raise ValueError("P must be [V,K_h] = [%d,%d], got %s" % (V, Kh, tuple(p.shape)))
         out = torch.empty((N, V, 3), dtype=torch.float32, device=m.device)
-        _lib.call("acfm_deform_apply", m.device, _lib.ptr(m), _lib.ptr(p), _lib.ptr(d), N, V, Kh, _lib.ptr(out))
+        _lib.call("acfm_deform_apply", m.device, m, p, d, N, V, Kh, out)
         ctx.save_for_backward(p, d)
         return out
 
@@ -90,8 +88,7 @@ class _DeformApply(torch.autograd.Function):
         gm = torch.empty((V, 3), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
         gp = torch.empty_like(p) if ctx.needs_input_grad[1] else None
         gd = torch.empty_like(d) if ctx.needs_input_grad[2] else None
-        _lib.call("acfm_deform_apply_backward", g.device, _lib.ptr(p), _lib.ptr(d), _lib.ptr(g), N, V, Kh, _lib.ptr(gd),
-                  _lib.ptr(gm), None)
+        _lib.call("acfm_deform_apply_backward", g.device, p, d, g, N, V, Kh, gd, gm, None)
         if gp is not None:
             # dL/dP = sum_n g_n delta_n^T feeds the solve's backward, which amplifies its rounding by the conditioning
             # of the system: summed in double and rounded once (acfm_deform_presolve_sums_f64), so that the value does
@@ -102,8 +99,7 @@ class _DeformApply(torch.autograd.Function):
                 g64, m64 = sink.presolve_buffer(V, Kh, g.device)
             else:
                 g64, m64 = torch.empty((V, Kh), dtype=torch.float64, device=g.device), None
-            _lib.call("acfm_deform_presolve_sums_f64", g.device, _lib.ptr(d), _lib.ptr(g), N, V, Kh, _lib.ptr(g64),
-                      _lib.ptr(m64), _lib.ptr(gp))
+            _lib.call("acfm_deform_presolve_sums_f64", g.device, d, g, N, V, Kh, g64, m64, gp)
         return gm, gp, gd
 
 
@@ -191,10 +187,10 @@ class _DeformSolve(torch.autograd.Function):
         nbytes = lib.acfm_deform_solve_workspace_bytes(V, Kh)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
         P = torch.empty((V, Kh), dtype=torch.float32, device=b.device)
-        _lib.call("acfm_deform_solve", b.device, _lib.ptr(l), _lib.ptr(b), V, Kh, _lib.ptr(P), _lib.ptr(ws), nbytes)
+        _lib.call("acfm_deform_solve", b.device, l, b, V, Kh, P, ws, nbytes)
         if check:
             info = ctypes.c_int(0)
-            _lib.call("acfm_deform_solve_info", b.device, _lib.ptr(ws), nbytes, V, ctypes.byref(info))
+            _lib.call("acfm_deform_solve_info", b.device, ws, nbytes, V, ctypes.byref(info))
             msg = decode_solve_info(info.value)
             if msg:
                 raise RuntimeError(msg)
@@ -218,8 +214,7 @@ class _DeformSolve(torch.autograd.Function):
             return None, None, None
         g = _f32c(g)
         gl = torch.empty((V, Kh), dtype=torch.float32, device=g.device)
-        _lib.call("acfm_deform_solve_backward", g.device, _lib.ptr(g), V, Kh, _lib.ptr(ctx.ws), ctx.ws.numel(),
-                  _lib.ptr(gl))
+        _lib.call("acfm_deform_solve_backward", g.device, g, V, Kh, ctx.ws, ctx.ws.numel(), gl)
         return None, gl, None
 
 
@@ -252,7 +247,7 @@ class _CameraPipeline(torch.autograd.Function):
             raise ValueError("camera rows %d must be a multiple of the %d frames (transforms %s)"
                              % (R, N, tuple(tr.shape)))
         out = torch.empty((R, 7), dtype=torch.float32, device=e.device)
-        _lib.call(entry, e.device, _lib.ptr(e), _lib.ptr(mf), _lib.ptr(tr), R, N, *params, _lib.ptr(out))
+        _lib.call(entry, e.device, e, mf, tr, R, N, *params, out)
         ctx.save_for_backward(e, mf, tr)
         ctx.cfg = (entry, W, params)
         return out
@@ -264,8 +259,7 @@ class _CameraPipeline(torch.autograd.Function):
         R, N = e.numel() // W, mf.numel()
         g = _f32c(g)
         ge = torch.empty_like(e)
-        _lib.call(entry + "_backward", e.device, _lib.ptr(e), _lib.ptr(mf), _lib.ptr(tr), _lib.ptr(g), R, N, *params,
-                  _lib.ptr(ge))
+        _lib.call(entry + "_backward", e.device, e, mf, tr, g, R, N, *params, ge)
         return ge, None, None, None, None, None
 
 
@@ -315,8 +309,7 @@ class _CameraPipelineTables(torch.autograd.Function):
                              % (what, N, mf.numel(), tuple(tr.shape), G, len(ts)))
         out = torch.empty((R, 7), dtype=torch.float32, device=ts[0].device)
         ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        _lib.call(entry, out.device, ptrs, len(ts), F, _lib.ptr(fi), _lib.ptr(sel), _lib.ptr(mf), _lib.ptr(tr), R, N,
-                  *params, _lib.ptr(out))
+        _lib.call(entry, out.device, ptrs, len(ts), F, fi, sel, mf, tr, R, N, *params, out)
         ctx.save_for_backward(fi, mf, tr, *ts) if sel is None else ctx.save_for_backward(fi, mf, tr, sel, *ts)
         ctx.cfg = (entry, W, params, R, N, F, len(ts), sel is not None)
         return out
@@ -333,8 +326,7 @@ class _CameraPipelineTables(torch.autograd.Function):
         outs = [torch.empty((F, W), dtype=torch.float32, device=g.device) if need[i] else None for i in range(nt)]
         ptrs = (ctypes.c_void_p * nt)(*[t.data_ptr() for t in ts])
         gptrs = (ctypes.c_void_p * nt)(*[(o.data_ptr() if o is not None else None) for o in outs])
-        _lib.call(entry + "_backward", g.device, ptrs, nt, F, _lib.ptr(fi), _lib.ptr(sel), _lib.ptr(mf), _lib.ptr(tr),
-                  _lib.ptr(g), R, N, *params, gptrs)
+        _lib.call(entry + "_backward", g.device, ptrs, nt, F, fi, sel, mf, tr, g, R, N, *params, gptrs)
         return (None,) * 8 + tuple(outs)
 
 
@@ -383,7 +375,7 @@ def camera_mirror(cams):
     _lib.require_gpu(cams)
     c = _f32c(cams.detach()).reshape(-1, 7)
     out = torch.empty_like(c)
-    _lib.call("acfm_camera_mirror", c.device, _lib.ptr(c), c.shape[0], _lib.ptr(out))
+    _lib.call("acfm_camera_mirror", c.device, c, c.shape[0], out)
     return out
 
 
@@ -394,7 +386,7 @@ class _CameraNormalize(torch.autograd.Function):
         r = _f32c(raw)
         N = r.numel() // 7
         out = torch.empty_like(r)
-        _lib.call("acfm_camera_normalize", r.device, _lib.ptr(r), N, _lib.ptr(out))
+        _lib.call("acfm_camera_normalize", r.device, r, N, out)
         ctx.save_for_backward(r)
         return out
 
@@ -403,7 +395,7 @@ class _CameraNormalize(torch.autograd.Function):
         (r,) = ctx.saved_tensors
         g = _f32c(g)
         gr = torch.empty_like(r)
-        _lib.call("acfm_camera_normalize_backward", r.device, _lib.ptr(r), _lib.ptr(g), r.numel() // 7, _lib.ptr(gr))
+        _lib.call("acfm_camera_normalize_backward", r.device, r, g, r.numel() // 7, gr)
         return gr
 
 

@@ -24,8 +24,7 @@ class _HypTotal(torch.autograd.Function):
         ag = (ctypes.c_int * nt)(*[int(x) for x in aux_group])
         aw = (ctypes.c_float * nt)(*[float(x) for x in aux_weights])
         ptrs = (ctypes.c_void_p * nt)(*[t.data_ptr() for t in ts])
-        _lib.call("acfm_hypothesis_total", dev, ptrs, w, ag, aw, nt, G, N, _lib.ptr(total), _lib.ptr(probs),
-                  _lib.ptr(aux[0]), _lib.ptr(aux[1]), _lib.ptr(out))
+        _lib.call("acfm_hypothesis_total", dev, ptrs, w, ag, aw, nt, G, N, total, probs, aux[0], aux[1], out)
         ctx.args = (w, nt, G, N, [t.shape for t in terms])
         ctx.save_for_backward(probs)
         ctx.mark_non_differentiable(total, probs, aux, out)
@@ -39,7 +38,7 @@ class _HypTotal(torch.autograd.Function):
         need = ctx.needs_input_grad[5:]
         outs = [torch.empty((G, N), dtype=torch.float32, device=g.device) if need[i] else None for i in range(nt)]
         ptrs = (ctypes.c_void_p * nt)(*[(o.data_ptr() if o is not None else None) for o in outs])
-        _lib.call("acfm_hypothesis_total_backward", g.device, _lib.ptr(g), _lib.ptr(probs), w, nt, G, N, ptrs)
+        _lib.call("acfm_hypothesis_total_backward", g.device, g, probs, w, nt, G, N, ptrs)
         return (None,) * 5 + tuple(o.reshape(shapes[i]) if o is not None else None for i, o in enumerate(outs))
 
 
@@ -67,7 +66,7 @@ class _TexCycle(torch.autograd.Function):
         scratch = torch.empty(_lib.lib().acfm_texture_cycle_scratch_floats(B, int(T), F, R), dtype=torch.float32,
                               device=x.device)
         loss = torch.empty((), dtype=torch.float32, device=x.device)
-        _lib.call("acfm_texture_cycle", x.device, _lib.ptr(x), B, int(T), F, R, _lib.ptr(scratch), _lib.ptr(loss))
+        _lib.call("acfm_texture_cycle", x.device, x, B, int(T), F, R, scratch, loss)
         ctx.save_for_backward(x, scratch)
         ctx.cfg = (B, int(T), F, R, textures.dtype)
         return loss
@@ -78,8 +77,7 @@ class _TexCycle(torch.autograd.Function):
         B, T, F, R, dt = ctx.cfg
         g = _f32c(go).reshape(1)
         gx = torch.empty_like(x)
-        _lib.call("acfm_texture_cycle_backward", x.device, _lib.ptr(x), _lib.ptr(scratch), _lib.ptr(g), B, T, F, R,
-                  _lib.ptr(gx))
+        _lib.call("acfm_texture_cycle_backward", x.device, x, scratch, g, B, T, F, R, gx)
         return (gx if dt == torch.float32 else gx.to(dt)), None
 
 

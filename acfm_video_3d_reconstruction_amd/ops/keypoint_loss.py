@@ -38,7 +38,7 @@ class _KpWeights(torch.autograd.Function):
         A = torch.empty_like(x)
         entropy = torch.empty((), dtype=torch.float32, device=x.device)
         stats = torch.empty((K, 2), dtype=torch.float32, device=x.device)
-        _lib.call("acfm_kp_weights_forward", x.device, _lib.ptr(x), K, V, _lib.ptr(A), _lib.ptr(entropy), _lib.ptr(stats))
+        _lib.call("acfm_kp_weights_forward", x.device, x, K, V, A, entropy, stats)
         ctx.save_for_backward(x, A, stats)
         return A, entropy
 
@@ -51,8 +51,7 @@ class _KpWeights(torch.autograd.Function):
         gA = None if gA is None else _f32c(gA)
         ge = None if ge is None else _f32c(ge)
         gx = torch.empty_like(x)
-        _lib.call("acfm_kp_weights_backward", x.device, _lib.ptr(x), _lib.ptr(A), _lib.ptr(stats), _lib.ptr(gA),
-                  _lib.ptr(ge), K, V, _lib.ptr(gx))
+        _lib.call("acfm_kp_weights_backward", x.device, x, A, stats, gA, ge, K, V, gx)
         return gx
 
 
@@ -81,8 +80,8 @@ class _KpHead(torch.autograd.Function):
         kp_pred = torch.empty((N, K, 2), dtype=torch.float32, device=dev)
         loss = None if g is None else torch.empty((N,), dtype=torch.float32, device=dev)
         err = torch.empty((N, K), dtype=torch.float32, device=dev) if want_err else None
-        _lib.call("acfm_kp_head_forward", dev, _lib.ptr(a), _lib.ptr(v), _lib.ptr(c), _lib.ptr(g), K, V, N, Nv, Ng,
-                  float(img_size or 0.0), _lib.ptr(kp_verts), _lib.ptr(kp_pred), _lib.ptr(loss), _lib.ptr(err))
+        _lib.call("acfm_kp_head_forward", dev, a, v, c, g, K, V, N, Nv, Ng, float(img_size or 0.0), kp_verts, kp_pred,
+                  loss, err)
         ctx.save_for_backward(a, v, c, g, kp_verts, kp_pred)
         if err is not None:
             ctx.mark_non_differentiable(err)
@@ -103,9 +102,8 @@ class _KpHead(torch.autograd.Function):
         gc = torch.empty_like(c) if need[2] else None
         nb = int(_lib.lib().acfm_kp_head_workspace_bytes(K, Nv))
         ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
-        _lib.call("acfm_kp_head_backward", dev, _lib.ptr(a), _lib.ptr(v), _lib.ptr(c), _lib.ptr(gt), _lib.ptr(kp_verts),
-                  _lib.ptr(kp_pred), _lib.ptr(g_loss), _lib.ptr(g_pred), _lib.ptr(g_kpv), K, V, N, Nv, Ng, _lib.ptr(gA),
-                  _lib.ptr(gv), _lib.ptr(gc), _lib.ptr(ws), nb)
+        _lib.call("acfm_kp_head_backward", dev, a, v, c, gt, kp_verts, kp_pred, g_loss, g_pred, g_kpv, K, V, N, Nv, Ng,
+                  gA, gv, gc, ws, nb)
         return gA, gv, gc, None, None, None
 
 
@@ -143,8 +141,7 @@ class _CameraLoss(torch.autograd.Function):
         G = 0 if w is None else w.shape[0]
         loss = torch.empty((), dtype=torch.float32, device=dev)
         best = None if w is None else torch.empty((N,), dtype=torch.int64, device=dev)
-        _lib.call("acfm_camera_loss_forward", dev, _lib.ptr(p), _lib.ptr(r), _lib.ptr(c), _lib.ptr(w), N, G,
-                  float(margin), _lib.ptr(loss), _lib.ptr(best))
+        _lib.call("acfm_camera_loss_forward", dev, p, r, c, w, N, G, float(margin), loss, best)
         ctx.save_for_backward(p, r, c, best)
         ctx.margin = float(margin)
         if best is not None:
@@ -158,8 +155,7 @@ class _CameraLoss(torch.autograd.Function):
         p, r, c, best = ctx.saved_tensors
         g = _f32c(g)
         gp = torch.empty_like(p)
-        _lib.call("acfm_camera_loss_backward", p.device, _lib.ptr(p), _lib.ptr(r), _lib.ptr(c), _lib.ptr(best),
-                  _lib.ptr(g), p.shape[0], ctx.margin, _lib.ptr(gp))
+        _lib.call("acfm_camera_loss_backward", p.device, p, r, c, best, g, p.shape[0], ctx.margin, gp)
         return gp, None, None, None, None
 
 

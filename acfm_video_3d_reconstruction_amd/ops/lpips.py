@@ -23,7 +23,7 @@ class _LpipsInput(torch.autograd.Function):
         i, m = _f32c(img), _f32c(mask)
         N, _, H, W = i.shape
         x = torch.empty_like(i)
-        _lib.call("acfm_lpips_input_forward", i.device, _lib.ptr(i), _lib.ptr(m), N, m.shape[0], H, W, _lib.ptr(x))
+        _lib.call("acfm_lpips_input_forward", i.device, i, m, N, m.shape[0], H, W, x)
         ctx.save_for_backward(m)
         return x
 
@@ -33,7 +33,7 @@ class _LpipsInput(torch.autograd.Function):
         g = _f32c(gx)
         N, _, H, W = g.shape
         gi = torch.empty_like(g)
-        _lib.call("acfm_lpips_input_backward", g.device, _lib.ptr(g), _lib.ptr(m), N, m.shape[0], H, W, _lib.ptr(gi))
+        _lib.call("acfm_lpips_input_backward", g.device, g, m, N, m.shape[0], H, W, gi)
         return gi, None
 
 
@@ -72,8 +72,7 @@ class _LpipsLayers(torch.autograd.Function):
         d = torch.empty((N, P), dtype=torch.float32, device=fas[0].device)
         off = 0
         for a, b, w, hw in zip(fas, fbs, lins, hws):
-            _lib.call("acfm_lpips_layer_forward", a.device, _lib.ptr(a), _lib.ptr(b), _lib.ptr(w), N, Nr, a.shape[1], hw,
-                      _ptr_at(d, off), P)
+            _lib.call("acfm_lpips_layer_forward", a.device, a, b, w, N, Nr, a.shape[1], hw, _ptr_at(d, off), P)
             off += hw
         ctx.save_for_backward(*fas, *fbs, *[w for w in lins if w is not None])
         ctx.cfg = (L, [w is not None for w in lins], hws, P)
@@ -93,12 +92,12 @@ class _LpipsLayers(torch.autograd.Function):
         for l, (a, b, w, hw) in enumerate(zip(fas, fbs, lins, hws)):
             if need_a[l]:
                 ga[l] = torch.empty_like(a)
-                _lib.call("acfm_lpips_layer_backward", a.device, _lib.ptr(a), _lib.ptr(b), _lib.ptr(w), _ptr_at(g, off), P,
-                          N, Nr, a.shape[1], hw, _lib.ptr(ga[l]))
+                _lib.call("acfm_lpips_layer_backward", a.device, a, b, w, _ptr_at(g, off), P, N, Nr, a.shape[1], hw,
+                          ga[l])
             if need_b[l]:   # Nr == N (checked by lpips_layers): d is symmetric, the same kernel with the roles exchanged
                 gb[l] = torch.empty_like(b)
-                _lib.call("acfm_lpips_layer_backward", a.device, _lib.ptr(b), _lib.ptr(a), _lib.ptr(w), _ptr_at(g, off), P,
-                          N, N, a.shape[1], hw, _lib.ptr(gb[l]))
+                _lib.call("acfm_lpips_layer_backward", a.device, b, a, w, _ptr_at(g, off), P, N, N, a.shape[1], hw,
+                          gb[l])
             off += hw
         return (None, *ga, *gb, *([None] * L))
 
@@ -184,7 +183,7 @@ def lpips_mask_weights(mask, sizes):
     P = sum(h * w for h, w in sizes)
     M = torch.empty((Nr, P), dtype=torch.float32, device=m.device)
     hw = (ctypes.c_int32 * (2 * len(sizes)))(*[v for s in sizes for v in s])
-    _lib.call("acfm_lpips_mask_weights", m.device, _lib.ptr(m), Nr, H, W, hw, len(sizes), _lib.ptr(M))
+    _lib.call("acfm_lpips_mask_weights", m.device, m, Nr, H, W, hw, len(sizes), M)
     return M
 
 
@@ -194,8 +193,7 @@ class _LpipsMaskedMean(torch.autograd.Function):
         dd, mm = _f32c(d), _f32c(M)
         N, P = dd.shape
         loss = torch.empty((N,), dtype=torch.float32, device=dd.device)
-        _lib.call("acfm_lpips_masked_mean_forward", dd.device, _lib.ptr(dd), _lib.ptr(mm), N, mm.shape[0], P,
-                  _lib.ptr(loss))
+        _lib.call("acfm_lpips_masked_mean_forward", dd.device, dd, mm, N, mm.shape[0], P, loss)
         ctx.save_for_backward(mm)
         return loss
 
@@ -205,7 +203,7 @@ class _LpipsMaskedMean(torch.autograd.Function):
         g = _f32c(gl)
         N, P = g.shape[0], mm.shape[1]
         gd = torch.empty((N, P), dtype=torch.float32, device=g.device)
-        _lib.call("acfm_lpips_masked_mean_backward", g.device, _lib.ptr(g), _lib.ptr(mm), N, mm.shape[0], P, _lib.ptr(gd))
+        _lib.call("acfm_lpips_masked_mean_backward", g.device, g, mm, N, mm.shape[0], P, gd)
         return gd, None
 
 

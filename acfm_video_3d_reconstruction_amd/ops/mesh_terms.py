@@ -13,7 +13,7 @@ def cot_laplacian(verts, faces):
     f = faces.detach().to(torch.int64).contiguous()
     V, F = v.shape[0], f.shape[0]
     L = torch.empty((V, V), dtype=torch.float32, device=v.device)
-    _lib.call("acfm_cot_laplacian", v.device, _lib.ptr(v), _lib.ptr(f), V, F, _lib.ptr(L))
+    _lib.call("acfm_cot_laplacian", v.device, v, f, V, F, L)
     return L
 
 
@@ -27,8 +27,7 @@ class _LaplacianSmoothing(torch.autograd.Function):
         n = _lib.lib().acfm_laplacian_smoothing_state_floats(P, F)
         state = torch.empty(n, dtype=torch.float32, device=v.device)
         loss = torch.empty((), dtype=torch.float32, device=v.device)
-        _lib.call("acfm_laplacian_smoothing", v.device, _lib.ptr(v), _lib.ptr(c), _lib.ptr(w), P, F, int(method),
-                  int(vpm), int(fpm), _lib.ptr(loss), _lib.ptr(state))
+        _lib.call("acfm_laplacian_smoothing", v.device, v, c, w, P, F, int(method), int(vpm), int(fpm), loss, state)
         ctx.save_for_backward(c, state)
         ctx.cfg = (P, F, int(method), int(vpm), int(fpm))
         return loss
@@ -39,8 +38,7 @@ class _LaplacianSmoothing(torch.autograd.Function):
         P, F, method, vpm, fpm = ctx.cfg
         g = _f32c(go).reshape(1)
         gv = torch.empty((P, 3), dtype=torch.float32, device=g.device)
-        _lib.call("acfm_laplacian_smoothing_backward", g.device, _lib.ptr(c), _lib.ptr(state), _lib.ptr(g), P, F,
-                  method, vpm, fpm, _lib.ptr(gv))
+        _lib.call("acfm_laplacian_smoothing_backward", g.device, c, state, g, P, F, method, vpm, fpm, gv)
         return gv, None, None, None, None, None
 
 
@@ -61,8 +59,7 @@ class _EdgeRigidity(torch.autograd.Function):
         if e.shape != et.shape:
             raise ValueError("meshes and template must have the same number of edges")
         loss = torch.empty((), dtype=torch.float32, device=v.device)
-        _lib.call("acfm_edge_rigidity", v.device, _lib.ptr(v), _lib.ptr(e), _lib.ptr(vt), _lib.ptr(et), e.shape[0],
-                  _lib.ptr(loss))
+        _lib.call("acfm_edge_rigidity", v.device, v, e, vt, et, e.shape[0], loss)
         ctx.save_for_backward(v, e, vt, et)
         ctx.vpm = int(vpm)
         return loss
@@ -73,8 +70,8 @@ class _EdgeRigidity(torch.autograd.Function):
         g = _f32c(go).reshape(1)
         gv = torch.empty_like(v) if ctx.needs_input_grad[0] else None
         gvt = torch.empty_like(vt) if ctx.needs_input_grad[2] else None
-        _lib.call("acfm_edge_rigidity_backward", g.device, _lib.ptr(v), _lib.ptr(e), _lib.ptr(vt), _lib.ptr(et),
-                  e.shape[0], v.shape[0], vt.shape[0], ctx.vpm, _lib.ptr(g), _lib.ptr(gv), _lib.ptr(gvt))
+        _lib.call("acfm_edge_rigidity_backward", g.device, v, e, vt, et, e.shape[0], v.shape[0], vt.shape[0], ctx.vpm,
+                  g, gv, gvt)
         return gv, None, gvt, None, None
 
 
@@ -109,8 +106,7 @@ class _Chamfer(torch.autograd.Function):
         with torch.cuda.device(a.device):
             need = int(_lib.lib().acfm_chamfer_partial_floats(N, P1, P2))
             tk, part, nf = _row_scratch(a.device, _LOSS_CHAMFER, 2 * N, need)
-        _lib.call("acfm_chamfer", a.device, _lib.ptr(a), _lib.ptr(b), _lib.ptr(xl), _lib.ptr(yl), N, P1, P2,
-                  _lib.ptr(sums), _lib.ptr(ix), _lib.ptr(iy), _lib.ptr(tk), _lib.ptr(part), nf)
+        _lib.call("acfm_chamfer", a.device, a, b, xl, yl, N, P1, P2, sums, ix, iy, tk, part, nf)
         ctx.save_for_backward(a, b, ix, iy)
         ctx.lens = (xl, yl)
         ctx.mark_non_differentiable(ix, iy)
@@ -124,8 +120,7 @@ class _Chamfer(torch.autograd.Function):
         P2 = b.shape[1]
         g = _f32c(gs)
         ga, gb = torch.empty_like(a), torch.empty_like(b)
-        _lib.call("acfm_chamfer_backward", a.device, _lib.ptr(a), _lib.ptr(b), _lib.ptr(xl), _lib.ptr(yl), _lib.ptr(ix),
-                  _lib.ptr(iy), _lib.ptr(g), N, P1, P2, _lib.ptr(ga), _lib.ptr(gb))
+        _lib.call("acfm_chamfer_backward", a.device, a, b, xl, yl, ix, iy, g, N, P1, P2, ga, gb)
         return ga, gb, None, None
 
 
@@ -155,8 +150,7 @@ class _EdgeLength(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=v.device)
         with torch.cuda.device(v.device):
             tk, part, nf = _row_scratch(v.device, _LOSS_EDGE_LEN, 1, int(_lib.lib().acfm_mesh_term_partial_floats(E)))
-        _lib.call("acfm_edge_length_loss", v.device, _lib.ptr(v), _lib.ptr(e), _lib.ptr(w), P, E, float(target),
-                  _lib.ptr(loss), _lib.ptr(tk), _lib.ptr(part), nf)
+        _lib.call("acfm_edge_length_loss", v.device, v, e, w, P, E, float(target), loss, tk, part, nf)
         ctx.save_for_backward(v, e, w)
         ctx.target = float(target)
         return loss
@@ -166,8 +160,7 @@ class _EdgeLength(torch.autograd.Function):
         v, e, w = ctx.saved_tensors
         g = _f32c(go).reshape(1)
         gv = torch.empty_like(v)
-        _lib.call("acfm_edge_length_loss_backward", v.device, _lib.ptr(v), _lib.ptr(e), _lib.ptr(w), _lib.ptr(g),
-                  v.shape[0], e.shape[0], ctx.target, _lib.ptr(gv))
+        _lib.call("acfm_edge_length_loss_backward", v.device, v, e, w, g, v.shape[0], e.shape[0], ctx.target, gv)
         return gv, None, None, None
 
 
@@ -186,8 +179,7 @@ class _NormalConsistency(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=v.device)
         with torch.cuda.device(v.device):
             tk, part, nf = _row_scratch(v.device, _LOSS_NORMAL, 1, int(_lib.lib().acfm_mesh_term_partial_floats(Q)))
-        _lib.call("acfm_normal_consistency", v.device, _lib.ptr(v), _lib.ptr(q), _lib.ptr(w), P, Q, _lib.ptr(loss),
-                  _lib.ptr(tk), _lib.ptr(part), nf)
+        _lib.call("acfm_normal_consistency", v.device, v, q, w, P, Q, loss, tk, part, nf)
         ctx.save_for_backward(v, q, w)
         return loss
 
@@ -196,8 +188,7 @@ class _NormalConsistency(torch.autograd.Function):
         v, q, w = ctx.saved_tensors
         g = _f32c(go).reshape(1)
         gv = torch.empty_like(v)
-        _lib.call("acfm_normal_consistency_backward", v.device, _lib.ptr(v), _lib.ptr(q), _lib.ptr(w), _lib.ptr(g),
-                  v.shape[0], q.shape[0], _lib.ptr(gv))
+        _lib.call("acfm_normal_consistency_backward", v.device, v, q, w, g, v.shape[0], q.shape[0], gv)
         return gv, None, None
 
 

@@ -229,7 +229,7 @@ def _launch_step_tail(jobs, total):
         j.done = True
     try:
         _lib.call("acfm_step_losses_forward", dev, ref(structs.get("mask")), ref(structs.get("tex")),
-                  ref(structs.get("bds")), ref(tot), N, _lib.ptr(tk), _lib.ptr(part), nf)
+                  ref(structs.get("bds")), ref(tot), N, tk, part, nf)
     finally:
         for j in jobs:
             j.taken(fused=True)

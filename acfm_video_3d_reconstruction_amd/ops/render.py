@@ -252,9 +252,8 @@ def _lazy_pix_to_face(plane0, vis, v, f, c, H, K, blur, sigma, offset_z):
         kth = torch.empty((N, H, H), dtype=torch.int64, device=v.device)
         vis2 = torch.empty((N, V), dtype=torch.uint8, device=v.device)
         ws, nb = _workspace(N, V, F, H, v.device)          # its own workspace: the render's is still the backward's
-        _lib.call("acfm_sil_forward", v.device, _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), N, V, F, H, K, K, float(blur),
-                  float(sigma), float(offset_z), _lib.ptr(mask), _lib.ptr(full), _lib.ptr(kth), _lib.ptr(vis2),
-                  _lib.ptr(ws), nb, _lib.tuning_ptr(tune), None)
+        _lib.call("acfm_sil_forward", v.device, v, f, c, N, V, F, H, K, K, float(blur), float(sigma), float(offset_z),
+                  mask, full, kth, vis2, ws, nb, _lib.tuning_ptr(tune), None)
         return full
 
     return LazyPixToFace(plane0, K, make_full, vis)
@@ -308,14 +307,12 @@ class _SilRender(torch.autograd.Function):
         # gradients afterwards (k_project, k_project_bwd and two torch adds less per step)
         proj = torch.empty((N, V, 2), dtype=torch.float32, device=v.device)
         exp, _ex_keep = _lib.sil_extras(proj_xy=proj, prefill=prefill)
-        P = _lib.ptr
         if fused:
-            _lib.call("acfm_sil_loss_forward", v.device, P(v), P(f), P(c), P(g), P(e), RB, N, V, F, H, K, int(k_out),
-                      float(blur), float(sigma), float(offset_z), P(mask), P(p2f), P(kth), P(vis), P(losses), P(ws), nb,
-                      tp, exp)
+            _lib.call("acfm_sil_loss_forward", v.device, v, f, c, g, e, RB, N, V, F, H, K, int(k_out), float(blur),
+                      float(sigma), float(offset_z), mask, p2f, kth, vis, losses, ws, nb, tp, exp)
         else:
-            _lib.call("acfm_sil_forward", v.device, P(v), P(f), P(c), N, V, F, H, K, int(k_out), float(blur),
-                      float(sigma), float(offset_z), P(mask), P(p2f), P(kth), P(vis), P(ws), nb, tp, exp)
+            _lib.call("acfm_sil_forward", v.device, v, f, c, N, V, F, H, K, int(k_out), float(blur), float(sigma),
+                      float(offset_z), mask, p2f, kth, vis, ws, nb, tp, exp)
         _remember_setup(v, c, f, H, offset_z, ws, nb, blur, tune, prefill)
         ctx.save_for_backward(v, f, c, mask, kth, g, e)
         ctx.cfg = (H, float(blur), float(sigma), float(offset_z), RB)
@@ -336,9 +333,8 @@ class _SilRender(torch.autograd.Function):
         gv = torch.empty_like(v) if ctx.needs_input_grad[0] else None
         gc = torch.empty_like(c) if ctx.needs_input_grad[2] else None
         gp = _f32c(gproj) if gproj is not None else None
-        P = _lib.ptr
         if glosses is None and gmask is None:      # only the projection was used: its own backward
-            _lib.call("acfm_project_xy_backward", v.device, P(v), P(c), P(gp), N, V, P(gv), P(gc))
+            _lib.call("acfm_project_xy_backward", v.device, v, c, gp, N, V, gv, gc)
             return (gv, None, gc) + none[3:]
         ws, nb, tune = ctx.ws
         exp, _ex_keep = _lib.sil_extras(grad_proj_xy=gp)
@@ -348,12 +344,12 @@ class _SilRender(torch.autograd.Function):
             pay = gmask.take("mask_losses", mask) if type(gmask) is LazyGrad else None
         if pay is not None:
             _m, lg, le, rb, go = pay
-            _lib.call("acfm_sil_loss_backward", v.device, P(v), P(f), P(c), P(mask), P(kth), P(lg), P(le), rb, P(go),
-                      N, V, F, H, blur, sigma, offset_z, P(gv), P(gc), P(ws), nb, 1, _lib.tuning_ptr(tune), exp)
+            _lib.call("acfm_sil_loss_backward", v.device, v, f, c, mask, kth, lg, le, rb, go, N, V, F, H, blur, sigma,
+                      offset_z, gv, gc, ws, nb, 1, _lib.tuning_ptr(tune), exp)
         else:
             gm = _f32c(gmask)
-            _lib.call("acfm_sil_backward", v.device, P(v), P(f), P(c), P(mask), P(kth), P(gm), N, V, F, H, blur,
-                      sigma, offset_z, P(gv), P(gc), P(ws), nb, 1, _lib.tuning_ptr(tune), exp)
+            _lib.call("acfm_sil_backward", v.device, v, f, c, mask, kth, gm, N, V, F, H, blur, sigma, offset_z, gv, gc,
+                      ws, nb, 1, _lib.tuning_ptr(tune), exp)
         return (gv, None, gc) + none[3:]
 
 
@@ -416,8 +412,7 @@ def hard_raster(verts_proj, faces, img_size):
     p2f = torch.empty((N, H, H, 1), dtype=torch.int64, device=v.device)
     vis = torch.empty((N, V), dtype=torch.uint8, device=v.device)
     ws, nb = _workspace(N, V, F, H, v.device)
-    _lib.call("acfm_hard_raster", v.device, _lib.ptr(v), _lib.ptr(f), N, V, F, H, _lib.ptr(p2f), _lib.ptr(vis),
-              _lib.ptr(ws), nb, _lib.tuning()[0])
+    _lib.call("acfm_hard_raster", v.device, v, f, N, V, F, H, p2f, vis, ws, nb, _lib.tuning()[0])
     p2f._acfm_vis = vis
     return p2f
 
@@ -474,14 +469,13 @@ class _TexRender(torch.autograd.Function):
             p2f = torch.empty((N, H, H, 1), dtype=torch.int32 if f16 else torch.int64, device=v.device)
             tidx = torch.empty((N, H, H), dtype=torch.int32, device=v.device)
         tune = _lib.with_f16(tune, f16)
-        P = _lib.ptr
         if fused:
-            _lib.call("acfm_tex_mse_forward", v.device, P(v), P(f), P(c), P(a), P(ri), P(rm), RB, N, V, F, H, R,
-                      float(sigma), float(gamma), float(offset_z), P(imgs), P(sil), P(p2f), P(tidx), P(loss), P(ws), nb,
-                      ws_ready, float(ws_blur), NA, _lib.tuning_ptr(tune))
+            _lib.call("acfm_tex_mse_forward", v.device, v, f, c, a, ri, rm, RB, N, V, F, H, R, float(sigma),
+                      float(gamma), float(offset_z), imgs, sil, p2f, tidx, loss, ws, nb, ws_ready, float(ws_blur), NA,
+                      _lib.tuning_ptr(tune))
         else:
-            _lib.call("acfm_tex_forward", v.device, P(v), P(f), P(c), P(a), N, V, F, H, R, float(sigma), float(gamma),
-                      float(offset_z), P(imgs), P(sil), P(p2f), P(tidx), P(ws), nb, ws_ready, float(ws_blur), NA,
+            _lib.call("acfm_tex_forward", v.device, v, f, c, a, N, V, F, H, R, float(sigma), float(gamma),
+                      float(offset_z), imgs, sil, p2f, tidx, ws, nb, ws_ready, float(ws_blur), NA,
                       _lib.tuning_ptr(tune))
         ctx.save_for_backward(tidx, imgs, ri, rm)   # (imgs: to recognise a LazyGrad of this very image, at this version)
         ctx.cfg = (N, F, H, R, NA, V, RB)
@@ -505,20 +499,19 @@ class _TexRender(torch.autograd.Function):
         else:
             pay = None
         ws, nb, ws_blur = ctx.ws
-        P = _lib.ptr
         ga = None
         if pay is not None:      # the texture MSE's gradient (a LazyGrad still unformed): the kernel forms it per pixel
             t0, ri, rm, rb, go = pay
             ga = torch.empty((NA, F, R, R, 3), dtype=torch.float32, device=t0.device)
-            _lib.call("acfm_tex_mse_backward_faces", t0.device, P(t0), P(ri), P(rm), rb, P(go), P(tidx), P(ws), nb,
-                      ws_blur, N, V, F, H, R, NA, P(ga), _lib.tuning_ptr(ctx.tune))
+            _lib.call("acfm_tex_mse_backward_faces", t0.device, t0, ri, rm, rb, go, tidx, ws, nb, ws_blur, N, V, F, H,
+                      R, NA, ga, _lib.tuning_ptr(ctx.tune))
         elif gimgs is not None:
             g = _f32c(gimgs)
             ga = torch.empty((NA, F, R, R, 3), dtype=torch.float32, device=g.device)
             if TEX_BWD_GATHER[0] and R <= 8:
-                _lib.call("acfm_tex_backward_faces", g.device, P(g), P(tidx), P(ws), nb, ws_blur, N, V, F, H, R, NA, P(ga))
+                _lib.call("acfm_tex_backward_faces", g.device, g, tidx, ws, nb, ws_blur, N, V, F, H, R, NA, ga)
             else:
-                _lib.call("acfm_tex_backward", g.device, P(g), P(tidx), N, F, H, R, NA, P(ga))
+                _lib.call("acfm_tex_backward", g.device, g, tidx, N, F, H, R, NA, ga)
         # geometry / camera: integer texel lookup and K=1 blending send (numerically) no
         # gradient -- |d rgb / d dist| <= 1e-6 |texel| from the delta=1e-10 term.
         if ga is not None and ctx.adt != torch.float32:
@@ -559,9 +552,8 @@ def vertex_color_render(verts, faces, cams, verts_rgb, img_size, sigma=1e-4, gam
     p2f = torch.empty((N, H, H, 1), dtype=torch.int64, device=v.device)
     nb = _lib.lib().acfm_raster_workspace_bytes(N, V, F, H) + 4 * N * H * H
     ws = torch.empty(nb, dtype=torch.uint8, device=v.device)
-    _lib.call("acfm_vertex_color_forward", v.device, _lib.ptr(v), _lib.ptr(f), _lib.ptr(c), _lib.ptr(col), N, V, F, H,
-              float(sigma), float(gamma), float(offset_z), _lib.ptr(imgs), _lib.ptr(sil), _lib.ptr(p2f), _lib.ptr(ws),
-              nb, 0, 0.0, _lib.tuning()[0])
+    _lib.call("acfm_vertex_color_forward", v.device, v, f, c, col, N, V, F, H, float(sigma), float(gamma),
+              float(offset_z), imgs, sil, p2f, ws, nb, 0, 0.0, _lib.tuning()[0])
     return imgs, sil, p2f
 
 
@@ -581,5 +573,5 @@ def visible_vertices(pix_to_face, faces, nv):
     HW = p[0].numel() // K
     f = expand_faces(faces, N)
     vis = torch.empty((N, nv), dtype=torch.uint8, device=p.device)
-    _lib.call("acfm_visible_vertices", p.device, _lib.ptr(p), _lib.ptr(f), N, nv, f.shape[1], HW, K, _lib.ptr(vis))
+    _lib.call("acfm_visible_vertices", p.device, p, f, N, nv, f.shape[1], HW, K, vis)
     return vis

@@ -30,8 +30,7 @@ class _MaskLosses(torch.autograd.Function):
         def launch():
             with torch.cuda.device(m.device):
                 tk, part, nf = _loss_scratch(m.device, _LOSS_MASK, N, HW)
-            _lib.call("acfm_mask_losses", m.device, _lib.ptr(m), _lib.ptr(g), _lib.ptr(e), N, HW, RB, _lib.ptr(out),
-                      _lib.ptr(tk), _lib.ptr(part), nf)
+            _lib.call("acfm_mask_losses", m.device, m, g, e, N, HW, RB, out, tk, part, nf)
         ctx.save_for_backward(m, g, e)
         ctx.rb = RB
         ctx.job = None
@@ -56,8 +55,7 @@ class _MaskLosses(torch.autograd.Function):
 
         def make():
             gm = torch.empty_like(m)
-            _lib.call("acfm_mask_losses_backward", m.device, _lib.ptr(m), _lib.ptr(g), _lib.ptr(e), _lib.ptr(go), N, HW,
-                      rb, _lib.ptr(gm))
+            _lib.call("acfm_mask_losses_backward", m.device, m, g, e, go, N, HW, rb, gm)
             return gm
         if LAZY_GRADS[0] and m.dim() >= 2:
             return LazyGrad(m, "mask_losses", (m, g, e, rb, go), make), None, None
@@ -85,8 +83,7 @@ class _TexMSE(torch.autograd.Function):
         def launch():
             with torch.cuda.device(t.device):
                 tk, part, nf = _loss_scratch(t.device, _LOSS_TEX_MSE, N, HW)
-            _lib.call("acfm_tex_mse", t.device, _lib.ptr(t), _lib.ptr(i), _lib.ptr(m), N, HW, RB, _lib.ptr(out),
-                      _lib.ptr(tk), _lib.ptr(part), nf)
+            _lib.call("acfm_tex_mse", t.device, t, i, m, N, HW, RB, out, tk, part, nf)
         ctx.save_for_backward(t, i, m)
         ctx.rb = RB
         ctx.job = None
@@ -110,8 +107,7 @@ class _TexMSE(torch.autograd.Function):
 
         def make():
             gt = torch.empty_like(t)
-            _lib.call("acfm_tex_mse_backward", t.device, _lib.ptr(t), _lib.ptr(i), _lib.ptr(m), _lib.ptr(g), N, HW, rb,
-                      _lib.ptr(gt))
+            _lib.call("acfm_tex_mse_backward", t.device, t, i, m, g, N, HW, rb, gt)
             return gt
         if LAZY_GRADS[0]:
             return LazyGrad(t, "tex_mse", (t, i, m, rb, g), make), None, None
@@ -157,7 +153,7 @@ class _Combine(torch.autograd.Function):
             _launch_step_tail(jobs, (ts, ctx.args[0], ctx.args[1], total))
             return total
         ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        _lib.call("acfm_combine_losses", total.device, ptrs, ctx.args[0], ctx.args[1], len(ts), N, _lib.ptr(total))
+        _lib.call("acfm_combine_losses", total.device, ptrs, ctx.args[0], ctx.args[1], len(ts), N, total)
         return total
 
     @staticmethod
@@ -168,7 +164,7 @@ class _Combine(torch.autograd.Function):
         outs = [torch.empty((N, cols[i]), dtype=torch.float32, device=g.device) if need[i] else None
                 for i in range(nt)]
         ptrs = (ctypes.c_void_p * nt)(*[(o.data_ptr() if o is not None else None) for o in outs])
-        _lib.call("acfm_combine_losses_backward", g.device, _lib.ptr(g), ptrs, cols, w, nt, N)
+        _lib.call("acfm_combine_losses_backward", g.device, g, ptrs, cols, w, nt, N)
         return (None,) + tuple(o.reshape(shapes[i]) if o is not None else None for i, o in enumerate(outs))
 
 
@@ -196,8 +192,7 @@ class _BdsLoss(torch.autograd.Function):
         def launch():
             with torch.cuda.device(v.device):
                 tk, part, nf = _loss_scratch(v.device, _LOSS_BDS, N, P)
-            _lib.call("acfm_bds_loss", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vz), None, N, V, P, RB, 0, 0,
-                      _lib.ptr(loss), _lib.ptr(arg), _lib.ptr(tk), _lib.ptr(part), nf)
+            _lib.call("acfm_bds_loss", v.device, v, b, vz, None, N, V, P, RB, 0, 0, loss, arg, tk, part, nf)
         ctx.rb = RB
         ctx.job = None
         if not _deferring(v.device, "bds") or 12 * V > 150 * 1024:     # (a V the kernel refuses is refused here, by its own launch)
@@ -219,8 +214,7 @@ class _BdsLoss(torch.autograd.Function):
         P = b.shape[1]
         g = _f32c(gl)
         gv = torch.empty_like(v)
-        _lib.call("acfm_bds_loss_backward", v.device, _lib.ptr(v), _lib.ptr(b), None, _lib.ptr(arg), _lib.ptr(g), N, V, P,
-                  ctx.rb, 0, 0, _lib.ptr(gv))
+        _lib.call("acfm_bds_loss_backward", v.device, v, b, None, arg, g, N, V, P, ctx.rb, 0, 0, gv)
         return gv, None, None
 
 
@@ -246,8 +240,7 @@ class _BdsLossSel(torch.autograd.Function):
         def launch():
             with torch.cuda.device(v.device):
                 tk, part, nf = _loss_scratch(v.device, _LOSS_BDS, N, S)
-            _lib.call("acfm_bds_loss", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(vz), _lib.ptr(s),
-                      N, V, P, RB, rows, S, _lib.ptr(loss), _lib.ptr(arg), _lib.ptr(tk), _lib.ptr(part), nf)
+            _lib.call("acfm_bds_loss", v.device, v, b, vz, s, N, V, P, RB, rows, S, loss, arg, tk, part, nf)
         ctx.rb = RB
         ctx.job = None
         if not _deferring(v.device, "bds") or 12 * V > 150 * 1024:
@@ -270,8 +263,7 @@ class _BdsLossSel(torch.autograd.Function):
         rows, S = s.shape
         g = _f32c(gl)
         gv = torch.empty_like(v)
-        _lib.call("acfm_bds_loss_backward", v.device, _lib.ptr(v), _lib.ptr(b), _lib.ptr(s), _lib.ptr(arg),
-                  _lib.ptr(g), N, V, P, ctx.rb, rows, S, _lib.ptr(gv))
+        _lib.call("acfm_bds_loss_backward", v.device, v, b, s, arg, g, N, V, P, ctx.rb, rows, S, gv)
         return gv, None, None, None
 
 
@@ -306,6 +298,5 @@ def boundary_subset(state, P, n_samples, counts=None, per_mesh=False):
         nc = counts.shape[0]
     rows = nc if per_mesh else 1
     sel = torch.empty((rows, int(n_samples)), dtype=torch.int32, device=state.device)
-    _lib.call("acfm_boundary_subset", state.device, _lib.ptr(state), _lib.ptr(counts), nc, rows, int(P),
-              int(n_samples), _lib.ptr(sel))
+    _lib.call("acfm_boundary_subset", state.device, state, counts, nc, rows, int(P), int(n_samples), sel)
     return sel

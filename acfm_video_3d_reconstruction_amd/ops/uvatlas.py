@@ -59,7 +59,7 @@ def uv_atlas_table(uv_sampler, Hu, Wu):
         return UVAtlasTable(s, Hu, Wu)
     n = s.shape[0] * s.shape[1] * s.shape[2]
     taps = torch.empty((n, 4), dtype=torch.int32, device=s.device)
-    _lib.call("acfm_uv_atlas_taps", s.device, _lib.ptr(s), n, Hu, Wu, _lib.ptr(taps))
+    _lib.call("acfm_uv_atlas_taps", s.device, s, n, Hu, Wu, taps)
     return UVAtlasTable(s, Hu, Wu, *_uv_table_from_taps(taps, Hu * Wu))
 
 
@@ -69,8 +69,8 @@ class _UVAtlas(torch.autograd.Function):
         x = uvimage.detach().contiguous()
         B = x.shape[0]
         atlas = torch.empty((B, table.Fp + nsym, table.T, table.T, 3), dtype=torch.float32, device=x.device)
-        _lib.call("acfm_uv_atlas_forward", x.device, _lib.ptr(x), _lib.ptr(table.sampler), B, table.Hu, table.Wu,
-                  table.Fp, table.T, nsym, _lib.ptr(atlas))
+        _lib.call("acfm_uv_atlas_forward", x.device, x, table.sampler, B, table.Hu, table.Wu, table.Fp, table.T, nsym,
+                  atlas)
         ctx.save_for_backward(atlas)
         ctx.cfg = (table, nsym)
         return atlas
@@ -82,9 +82,8 @@ class _UVAtlas(torch.autograd.Function):
         g = _f32c(go)
         B = atlas.shape[0]
         gx = torch.empty((B, 3, table.Hu, table.Wu), dtype=torch.float32, device=atlas.device)
-        _lib.call("acfm_uv_atlas_backward", atlas.device, _lib.ptr(g), _lib.ptr(atlas), _lib.ptr(table.sampler),
-                  _lib.ptr(table.pix_start), _lib.ptr(table.pix_taps), table.n_entries, B, table.Hu, table.Wu, table.Fp,
-                  table.T, nsym, _lib.ptr(gx))
+        _lib.call("acfm_uv_atlas_backward", atlas.device, g, atlas, table.sampler, table.pix_start, table.pix_taps,
+                  table.n_entries, B, table.Hu, table.Wu, table.Fp, table.T, nsym, gx)
         return gx, None, None
 
 

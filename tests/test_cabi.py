@@ -22,17 +22,33 @@ def _declared_symbols():
 
 _RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
 _SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+# what a device pointer points to, as _lib.SIGNATURES names it: element size and float-versus-integer, not signedness
+_ELEMENTS = {"float": "float*", "double": "double*", "uint8_t": "int8*", "int": "int32*", "int32_t": "int32*",
+             "uint32_t": "int32*", "int64_t": "int64*", "uint64_t": "int64*"}
+
+
+def _kind(param):
+    """A parameter `type name` of the header as the table holds it: int / float / size_t are their ctypes classes (a
+    scalar type outside these is a KeyError: extend the test with the ABI); a pointer to float, double or a 1-, 4- or
+    8-byte integer on the device is its element kind; void*, a mirrored structure, a pointer table and a host
+    out-parameter (`*_host`, size_t*) are c_void_p; a pointer to anything else is a KeyError as well."""
+    base, name = param.rsplit(" ", 1)
+    if "*" not in param:
+        return _SCALARS[base]
+    base = base.replace("const ", "").rstrip("* ")
+    if param.count("*") > 1 or name.endswith("_host") or base in ("void", "size_t") or base.lower().startswith("acfm"):
+        return ctypes.c_void_p
+    return _ELEMENTS[base]
 
 
 def _prototypes():
-    """{name: (restype, [argtypes])} of every `type name(args);` of the header, in ctypes classes: any pointer is
-    c_void_p, int / float / size_t are themselves; a type outside these is a KeyError (extend the test with the ABI)."""
+    """{name: (restype, [parameter kinds])} of every `type name(args);` of the header (see _kind)."""
     out = {}
     for ret, name, args in re.findall(r"^((?:const\s+)?\w+\s*\*?)\s*(acfm_\w+)\s*\(([^()]*)\)\s*;", _header(), flags=re.M):
         params = [" ".join(a.split()) for a in args.split(",")]
         if params == ["void"]:
             params = []
-        kinds = [ctypes.c_void_p if "*" in p else _SCALARS[p.rsplit(" ", 1)[0]] for p in params]
+        kinds = [_kind(p) for p in params]
         assert name not in out, "%s is declared twice" % name
         out[name] = (_RETURNS[" ".join(ret.split())], kinds)
     return out
@@ -55,13 +71,14 @@ def _defines():
 
 
 def test_signature_table_matches_the_header_by_type():
-    """SIGNATURES[name] == the header's prototype: return type and every parameter's class, in order and in number
-    (the names-only comparison below cannot see an argument added to or dropped from one side)."""
+    """SIGNATURES[name] == the header's prototype: return type and every parameter's class -- for a device pointer the
+    element kind it points to -- in order and in number (the names-only comparison below cannot see an argument added
+    to or dropped from one side)."""
     from acfm_video_3d_reconstruction_amd import _lib
     protos = _prototypes()
     assert set(protos) == set(_declared_symbols()), "a prototype the pattern does not parse"
     assert set(protos) == set(_lib.SIGNATURES)
-    short = lambda sig: "%s(%s)" % (sig[0].__name__, ", ".join(k.__name__ for k in sig[1]))
+    short = lambda sig: "%s(%s)" % (sig[0].__name__, ", ".join(getattr(k, "__name__", k) for k in sig[1]))
     bad = ["%s: header %d parameters %s, table %d parameters %s" % (n, len(h[1]), short(h), len(t[1]), short(t))
            for n, h in sorted(protos.items()) for t in [_lib.SIGNATURES[n]] if h != (t[0], list(t[1]))]
     assert not bad, "\n".join(bad)
