@@ -37,6 +37,8 @@ SIGNATURES = {
     "acfm_deform_apply": (_i, [_pf, _pf, _pf, _i, _i, _i, _pf, _vp]),
     "acfm_deform_apply_backward": (_i, [_pf, _pf, _pf, _i, _i, _i, _pf, _pf, _pf, _vp]),
     "acfm_deform_presolve_sums_f64": (_i, [_pf, _pf, _i, _i, _i, _pd, _pd, _pf, _vp]),
+    "acfm_symmetrize": (_i, [_pf, _i, _i, _i, _pf, _vp]),
+    "acfm_symmetrize_backward": (_i, [_pf, _i, _i, _i, _pf, _vp]),
     "acfm_correlation_forward": (_i, [_pf, _pf, _i, _i, _i, _i, _i, _pf, _vp]),
     "acfm_correlation_backward": (_i, [_pf, _pf, _pf, _i, _i, _i, _i, _i, _pf, _pf, _vp]),
     "acfm_deform_conv2d_forward": (_i, [_pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _pf, _vp]),

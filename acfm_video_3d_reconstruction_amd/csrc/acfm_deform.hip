@@ -198,6 +198,43 @@ __global__ __launch_bounds__(256) void k_deform_grad_P_f64(const float* __restri
     }
   }
 }
+
+// Symmetric template (mesh_net.py:573-591): the learned mean shape holds the n_indept centre rows and the n_sym right
+// rows; the full shape appends the right rows once more with x negated.  One thread per output float each way, every
+// element written exactly once, no atomics: the fold is ONE float addition per element of the right rows, so both
+// kernels are bit-reproducible and equal the torch lines (ones, index write, slice, multiply, cat and their
+// backwards) bit for bit: -1 * x and -x are the same float, and so are a + b and b + a.
+//   full[b][v][c] = half[b][v][c]                            v <  n_half = n_indept + n_sym
+//                 = (c == 0 ? -1 : 1) half[b][v - n_sym][c]  v >= n_half
+__global__ __launch_bounds__(256) void k_symmetrize(const float* __restrict__ half, int n_half, int n_sym, int total,
+                                                    float* __restrict__ full) {
+  const unsigned u = blockIdx.x * 256u + threadIdx.x;   // (compared unsigned: the last block may pass 2^31)
+  if (u >= (unsigned)total) return;
+  const int i = (int)u;
+  const int row3 = 3 * (n_half + n_sym);
+  const int b = i / row3, r = i - b * row3;
+  const float* hb = half + (size_t)b * 3 * n_half;
+  if (r < 3 * n_half) { full[i] = hb[r]; return; }
+  const int s = r - 3 * n_sym;           // the same coordinate of the right twin: rows n_half - n_sym .. n_half - 1
+  const float x = hb[s];
+  full[i] = (s % 3 == 0) ? -x : x;
+}
+
+//   ghalf[b][v][c] = g[b][v][c]                                         v <  n_indept
+//                  = g[b][v][c] + (c == 0 ? -1 : 1) g[b][v + n_sym][c]  v >= n_indept
+__global__ __launch_bounds__(256) void k_symmetrize_fold(const float* __restrict__ g, int n_indept, int n_sym, int total,
+                                                         float* __restrict__ ghalf) {
+  const unsigned u = blockIdx.x * 256u + threadIdx.x;   // (compared unsigned: the last block may pass 2^31)
+  if (u >= (unsigned)total) return;
+  const int i = (int)u;
+  const int half3 = 3 * (n_indept + n_sym);
+  const int b = i / half3, r = i - b * half3;
+  const float* gb = g + (size_t)b * (half3 + 3 * n_sym);
+  const float own = gb[r];
+  if (r < 3 * n_indept) { ghalf[i] = own; return; }
+  const float twin = gb[r + 3 * n_sym];
+  ghalf[i] = own + ((r % 3 == 0) ? -twin : twin);
+}
 }  // namespace acfm
 
 using namespace acfm;
@@ -223,6 +260,31 @@ int acfm_deform_apply(const float* mean_v, const float* P, const float* delta, i
   ProfScope ps(ACFM_PROF_DEFORM, st);
   hipLaunchKernelGGL(k_deform_apply, dim3((V + 15) / 16, (3 * N + 63) / 64), dim3(256), 0, st, mean_v, P,
                      delta, N, V, Kh, verts);
+  ACFM_CHECK_LAUNCH();
+  return ACFM_OK;
+}
+
+// (both: the element index is an int, so B rows of the FULL shape must stay below 2^31 floats)
+static bool symmetrize_args_ok(const void* in, const void* out, int B, int n_indept, int n_sym) {
+  if (!in || !out || B < 1 || n_indept < 0 || n_sym < 0) return false;
+  const long long n_half = (long long)n_indept + n_sym;
+  return n_half > 0 && (long long)B * 3 * (n_half + n_sym) <= 0x7fffffffll;
+}
+
+int acfm_symmetrize(const float* half, int B, int n_indept, int n_sym, float* full, void* stream) {
+  if (!symmetrize_args_ok(half, full, B, n_indept, n_sym)) return ACFM_E_BADARG;
+  const int n_half = n_indept + n_sym, total = B * 3 * (n_half + n_sym);
+  hipLaunchKernelGGL(k_symmetrize, dim3((unsigned)(((size_t)total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, half, n_half, n_sym,
+                     total, full);
+  ACFM_CHECK_LAUNCH();
+  return ACFM_OK;
+}
+
+int acfm_symmetrize_backward(const float* grad_full, int B, int n_indept, int n_sym, float* grad_half, void* stream) {
+  if (!symmetrize_args_ok(grad_full, grad_half, B, n_indept, n_sym)) return ACFM_E_BADARG;
+  const int total = B * 3 * (n_indept + n_sym);
+  hipLaunchKernelGGL(k_symmetrize_fold, dim3((unsigned)(((size_t)total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, grad_full,
+                     n_indept, n_sym, total, grad_half);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
 }

@@ -57,11 +57,24 @@ def _solve(L, lbs_logits):
 
 
 class DeformSolver(nn.Module):
-    """mean_v / lbs_logits may be nn.Parameters (learned, as in the reference) or plain tensors."""
+    """mean_v / lbs_logits may be nn.Parameters (learned, as in the reference) or plain tensors.
+    symmetry=(num_indept, num_sym): the reference's symmetric template (mesh_net.py:462-484).  mean_v then holds the
+    num_indept + num_sym rows on the mirror plane and right of it, as the reference's parameter does, and every reader
+    of the geometry goes through mean_shape(), which appends the mirrored right rows (template.symmetrize)."""
 
-    def __init__(self, mean_v, faces, lbs_logits, method="cot"):
+    def __init__(self, mean_v, faces, lbs_logits, method="cot", symmetry=None):
         super().__init__()
         self.method = method
+        self.symmetry = None
+        if symmetry is not None:
+            n_indept, n_sym = int(symmetry[0]), int(symmetry[1])
+            if n_indept < 0 or n_sym < 0 or mean_v.shape[0] != n_indept + n_sym:
+                raise ValueError("symmetry = (%d, %d): mean_v must have num_indept + num_sym = %d rows, got %d"
+                                 % (n_indept, n_sym, n_indept + n_sym, mean_v.shape[0]))
+            if int(faces.max()) + 1 != n_indept + 2 * n_sym:
+                raise ValueError("symmetry = (%d, %d): the faces index %d vertices, not num_indept + 2 num_sym = %d"
+                                 % (n_indept, n_sym, int(faces.max()) + 1, n_indept + 2 * n_sym))
+            self.symmetry = (n_indept, n_sym)
         if isinstance(mean_v, nn.Parameter):
             self.mean_v = mean_v
         else:
@@ -74,13 +87,22 @@ class DeformSolver(nn.Module):
         self._P = None
         self._L = None
 
+    def mean_shape(self):
+        """The full [V,3] mean shape (MeshNet.get_mean_shape, mesh_net.py:593-595): mean_v itself without symmetry, else
+        its rows followed by the mirrored right rows, with the autograd path back to the half parameter."""
+        if self.symmetry is None:
+            return self.mean_v
+        from . import template
+        return template.symmetrize(self.mean_v, self.symmetry[1])
+
     def laplacian(self, mean_v=None):
-        v = (self.mean_v if mean_v is None else mean_v).detach()
+        v = (self.mean_shape() if mean_v is None else mean_v).detach()
         return geom_utils.mesh_laplacian(_OneMesh(v, self.faces), self.method)
 
     def refresh(self, mean_v=None):
         """Call after lbs or the mean shape (which defines L) changed, i.e. once per optimiser
-        step: the next solve_matrix() rebuilds L and re-factorises."""
+        step: the next solve_matrix() rebuilds L and re-factorises.  mean_v: the FULL shape, where the caller has
+        formed it already."""
         self._P = None
         self._L = self.laplacian(mean_v)
 
@@ -100,7 +122,7 @@ class DeformSolver(nn.Module):
 
     def forward(self, delta, mean_override=None):
         """delta [N,K_h,3] handle offsets -> deformed verts [N,V,3] (delta = 0: the mean shape)."""
-        mean = self.mean_v if mean_override is None else mean_override
+        mean = self.mean_shape() if mean_override is None else mean_override
         P = self.solve_matrix()
         if delta.is_cuda:
             from . import ops

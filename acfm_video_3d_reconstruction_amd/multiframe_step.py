@@ -53,7 +53,12 @@ def _y_rotation_quats(num_guesses):
 
 class MultiframeStep(nn.Module):
     def __init__(self, mean_v, faces, lbs_logits, num_training_frames, img_size=256, vert2kp=None, prior_stream=False,
-                 boundary_sampler=None, supervision_kernels=False, **opts):
+                 boundary_sampler=None, supervision_kernels=False, symmetric=None, **opts):
+        """symmetric=(num_indept, num_sym): the reference's default template (--symmetric True, mesh_net.py:462-484;
+        template.make_symmetric gives the counts and the face order).  The learned `mean_v` then holds the first
+        num_indept + num_sym rows, as the reference's parameter does -- its checkpoints load --, and every step
+        renders and deforms solver.mean_shape().  mean_v may be given full (its left rows must mirror its right rows
+        exactly) or half."""
         super().__init__()
         # supervision_kernels=True (GPU tensors only): the keypoint term comes from keypoints.KeypointHead and the camera
         # head's loss from ops.camera_loss (csrc/acfm_keypoints.hip) instead of the chains of torch ops below
@@ -95,9 +100,24 @@ class MultiframeStep(nn.Module):
         self.deform_emb.weight.data.zero_()                     # mesh_net.py:448-451
         self.deform_mirror_emb.weight.data.zero_()
         self.lbs = nn.Parameter(lbs_logits.detach().clone())    # mesh_net.py:543-544
-        self.mean_v = nn.Parameter(mean_v.detach().clone())     # mesh_net.py:480 (symmetrisation: identity here)
+        if symmetric is not None:                               # mesh_net.py:462-480
+            n_indept, n_sym = int(symmetric[0]), int(symmetric[1])
+            n_half = n_indept + n_sym
+            if mean_v.shape[0] == n_half + n_sym and n_sym > 0:
+                flip = torch.tensor([[-1.0, 1.0, 1.0]], dtype=mean_v.dtype, device=mean_v.device)
+                bad = ((flip * mean_v[n_indept:n_half]) != mean_v[n_half:]).any(dim=1).nonzero()
+                if bad.numel():
+                    i = n_half + int(bad[0])
+                    raise ValueError("symmetric = (%d, %d): row %d of mean_v is not (-x, y, z) of row %d"
+                                     % (n_indept, n_sym, i, i - n_sym))
+                mean_v = mean_v[:n_half]
+            elif mean_v.shape[0] != n_half:
+                raise ValueError("symmetric = (%d, %d): mean_v must have %d (half) or %d (full) rows, got %d"
+                                 % (n_indept, n_sym, n_half, n_half + n_sym, mean_v.shape[0]))
+            symmetric = (n_indept, n_sym)
+        self.mean_v = nn.Parameter(mean_v.detach().clone())     # mesh_net.py:480
         self.register_buffer("faces1", faces.detach().clone().long())
-        self.solver = DeformSolver(self.mean_v, faces, self.lbs)
+        self.solver = DeformSolver(self.mean_v, faces, self.lbs, symmetry=symmetric)
         self.vert2kp = vert2kp
         self.renderer = NeuralRenderer(img_size)
         self.tex_renderer = NeuralRenderer(img_size)
@@ -201,14 +221,15 @@ class MultiframeStep(nn.Module):
         G = o.num_guesses
         N = batch["masks"].shape[0]
         cam = self.hypothesis_cameras(batch["frames_idx"], batch["mirror_flag"], batch["transforms"])
-        mean_v = self.solver.mean_v[None].repeat(G * N, 1, 1)
+        mean = self.solver.mean_shape()          # (symmetric: the one mirror launch of this call)
+        mean_v = mean[None].repeat(G * N, 1, 1)
         faces = self.faces1[None].expand(G * N, -1, -1)
         _, mask_loss, sil_cons = self._silhouette_terms(mean_v, faces, cam, batch, G)
         total = o.mask_loss_wt * mask_loss.reshape(G, N) + o.of_loss_wt * self._flow_term(mean_v, cam, batch, G) \
             + o.boundaries_reg_wt * sil_cons.reshape(G, N)
         if o.kp_loss_wt > 0 and self.vert2kp is not None and self.supervision_kernels and cam.is_cuda:
             # the mean shape once, the frames' keypoints once: hypothesis g*N + n reads row 0 / row n of them
-            kp = self._keypoint_head()(self.solver.mean_v[None], cam, batch["kps"]).loss
+            kp = self._keypoint_head()(mean[None], cam, batch["kps"]).loss
             total = total + o.kp_loss_wt * kp.reshape(G, N)
         elif o.kp_loss_wt > 0 and self.vert2kp is not None:
             kp_v = torch.matmul(torch.softmax(self.vert2kp, dim=1), mean_v)
@@ -249,14 +270,15 @@ class MultiframeStep(nn.Module):
             delta = deforms
         else:
             delta = delta_v_res
+        mean = self.solver.mean_shape()          # mesh_net.py:593-595, once per step (symmetric: one launch each way)
         if exchange is not None:
             # frame-sharded step (sharding.SharedShapeExchange over self.solver; `batch` holds this rank's clips,
             # sharding.frame_shard): the local backward stops at the (P, mean) leaves, exchange.finish() after
             # loss.backward() all-reduces the pre-solve sums and finishes d lbs identically on every rank
             pred_v1 = exchange.apply(delta)
         else:
-            self.solver.refresh()   # lbs / mean shape moved in the last optimiser step: one factorisation
-            pred_v1 = self.solver(delta)                         # [N,V,3]
+            self.solver.refresh(mean)   # lbs / mean shape moved in the last optimiser step: one factorisation
+            pred_v1 = self.solver(delta, mean_override=mean)     # [N,V,3]
         pred_v = pred_v1.repeat(G, 1, 1)
         faces = self.faces1[None].expand(G * N, -1, -1)
         terms = {}
@@ -276,7 +298,7 @@ class MultiframeStep(nn.Module):
             pred_v.record_stream(side_s)
         with (torch.cuda.stream(side_s) if side_s is not None else contextlib.nullcontext()):
             mesh_3d = Meshes(verts=pred_v, faces=faces_n)
-            mesh_t = Meshes(verts=self.solver.mean_v[None].repeat(G * N, 1, 1), faces=faces_n)
+            mesh_t = Meshes(verts=mean[None].repeat(G * N, 1, 1), faces=faces_n)
             triangle = mesh_laplacian_smoothing(mesh_3d, method="cot")
             rigid = loss_utils.locally_rigid_fn(mesh_3d, mesh_t)
         # The per-hypothesis total (main.py:716-734: weight * term + ...) and its weighting over the hypotheses

@@ -139,7 +139,16 @@ class SharedShapeExchange:
         scalars = ex.finish(extra_scalars=loss_local.detach()[None])   # the collective + the solve backward
         # now solver.lbs.grad / solver.mean_v.grad / extra_params' grads hold the full-batch gradients
 
-    average=True divides the reduced gradients by the world size (per-rank losses are means over equal shards)."""
+    average=True divides the reduced gradients by the world size (per-rank losses are means over equal shards).
+
+    A symmetric solver (DeformSolver(symmetry=...)): the leaves and the [V,3] block stay full-size, so the deformation
+    backward's double sums land where they always did; a direct term on the half parameter (a prior on the template:
+    it depends on the rank's own frames, so it has to pass the collective too) rides behind that block,
+
+        [ G (V x K_h)  |  sum_n g_n  (V x 3)  |  direct term (n_half x 3)  |  extra shared grads  |  loss scalars ]
+
+    and unpack() folds the reduced block into solver.mean_v.grad [n_half,3] (template.fold) and adds the direct term
+    after the fold."""
 
     def __init__(self, solver, extra_params=(), group=None, average=False, deterministic=False):
         self.solver = solver
@@ -166,10 +175,15 @@ class SharedShapeExchange:
     def presolve_buffer(self, V, Kh, device):
         """(called by ops._DeformApply.backward) where this step's local sums go: float64 views [V,K_h] and [V,3] at the
         head of the exchange buffer -- the backward's kernel writes the packed layout itself."""
-        tail = sum(p.numel() for p in self.extra) + max(self._n_sc, 8)
+        tail = self._n_direct() + sum(p.numel() for p in self.extra) + max(self._n_sc, 8)
         st = self._room(V * Kh + 3 * V + tail, device)
         self._filled = True
         return st[:V * Kh].view(V, Kh), st[V * Kh:V * Kh + 3 * V].view(V, 3)
+
+    def _n_direct(self):
+        """Doubles kept behind the [V,3] block for the direct term on a symmetric solver's half parameter."""
+        s = self.solver
+        return s.mean_v.numel() if getattr(s, "symmetry", None) is not None and s.mean_v.requires_grad else 0
 
     def __del__(self):
         try:
@@ -182,10 +196,11 @@ class SharedShapeExchange:
     def apply(self, delta):
         """delta [n_local,K_h,3] -> pred_v [n_local,V,3]; one factorisation per call (lbs / mean shape may have moved)."""
         s = self.solver
-        s.refresh()
+        mean = s.mean_shape().detach()                               # (the full shape: one mirror launch when symmetric)
+        s.refresh(mean)
         self._P = s.solve_matrix()                                   # carries the autograd path to lbs when it is learned
         self._P_leaf = self._P.detach().requires_grad_(True)
-        self._mean_leaf = s.mean_v.detach().requires_grad_(True)
+        self._mean_leaf = mean.requires_grad_(True)
         self._filled = False
         if delta.is_cuda:
             from . import ops
@@ -208,11 +223,21 @@ class SharedShapeExchange:
             gmean = self._mean_leaf.grad if self._mean_leaf.grad is not None else torch.zeros_like(self._mean_leaf)
         direct = s.mean_v.grad if (s.mean_v.requires_grad and s.mean_v.grad is not None) else None   # priors on the template
         self._n_sc = 0 if extra_scalars is None else extra_scalars.numel()
-        nP, nm = gP.numel(), gmean.numel()
-        n = nP + nm + sum(p.numel() for p in self.extra) + self._n_sc
+        nP, nm, nd = gP.numel(), gmean.numel(), self._n_direct()
+        n = nP + nm + nd + sum(p.numel() for p in self.extra) + self._n_sc
         filled = self._filled and self._store is not None and self._store.device == gP.device
         flat = self._room(n, gP.device)[:n]
-        if filled:
+        if nd:
+            # symmetric: the direct term has the half parameter's shape; it gets its own segment and joins the folded
+            # block in unpack()
+            if not filled:
+                flat[:nP].copy_(gP.reshape(-1))
+                flat[nP:nP + nm].copy_(gmean.reshape(-1))
+            if direct is None:
+                flat[nP + nm:nP + nm + nd].zero_()
+            else:
+                flat[nP + nm:nP + nm + nd].copy_(direct.reshape(-1))
+        elif filled:
             # the deformation apply's backward wrote G and sum g in double at the head of the buffer already (GPU); only a
             # direct term on the mean shape (a prior on the template) is still to be added
             if direct is not None:
@@ -220,7 +245,7 @@ class SharedShapeExchange:
         else:
             flat[:nP].copy_(gP.reshape(-1))
             flat[nP:nP + nm].copy_((gmean if direct is None else gmean + direct).reshape(-1))
-        o = nP + nm
+        o = nP + nm + nd
         for p in self.extra:
             flat[o:o + p.numel()].copy_((p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1))
             o += p.numel()
@@ -271,9 +296,14 @@ class SharedShapeExchange:
         nm = 1
         for d in mshape:
             nm *= d
-        if s.mean_v.requires_grad:
+        nd = self._n_direct()
+        if nd:
+            from . import template
+            g = template.fold(flat[o:o + nm].view(mshape).to(s.mean_v.dtype, copy=True), s.symmetry[1])
+            s.mean_v.grad = g + flat[o + nm:o + nm + nd].view_as(s.mean_v).to(s.mean_v.dtype)
+        elif s.mean_v.requires_grad:
             s.mean_v.grad = flat[o:o + nm].view(mshape).to(s.mean_v.dtype, copy=True)
-        o += nm
+        o += nm + nd
         for p in self.extra:
             p.grad = flat[o:o + p.numel()].view_as(p).to(p.dtype, copy=True)
             o += p.numel()

@@ -129,6 +129,19 @@ int acfm_deform_apply_backward(const float* P, const float* delta, const float* 
  * longer shows in the handle-weight gradient. */
 int acfm_deform_presolve_sums_f64(const float* delta, const float* grad_verts, int N, int V, int Kh, double* G64,
                                   double* mean64, float* grad_P, void* stream);
+/* The symmetric template (--symmetric True, mesh_net.py:462-484): the learned mean shape holds the n_indept rows on the
+ * mirror plane and the n_sym right-hand rows, the shape that is deformed and rendered appends the right-hand rows once
+ * more, mirrored.
+ * full[b] = [ half[b] ; (-x, y, z) of half[b][n_half - n_sym : n_half] ],  n_half = n_indept + n_sym,
+ * half [B,n_half,3] -> full [B,n_half + n_sym,3]   (mesh_net.py:573-591) */
+int acfm_symmetrize(const float* half, int B, int n_indept, int n_sym, float* full, void* stream);
+/* grad_half[b][i] = g[b][i] for i < n_indept,
+ *                 = g[b][i] + (-1, 1, 1) * g[b][i + n_sym] for i >= n_indept.
+ * One float addition per element, every element written.
+ * Both: one thread per output float, no atomics, no workspace; bit-reproducible and equal, bit for bit, to the torch
+ * lines they replace.  ACFM_E_BADARG for B < 1, a negative count, n_half == 0 or 3 B (n_half + n_sym) > 2^31 - 1;
+ * n_sym == 0 is a plain copy. */
+int acfm_symmetrize_backward(const float* grad_full, int B, int n_indept, int n_sym, float* grad_half, void* stream);
 
 /* ---- correlation cost volume -------------------------------------------------------------
  * replaces correlation_cuda.forward as MaskFlownet calls it (multiframe/data/optical_flow/model/

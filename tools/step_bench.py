@@ -15,17 +15,26 @@ p.add_argument("--img", type=int, default=256); p.add_argument("--iters", type=i
 p.add_argument("--mesh", default="horse"); p.add_argument("--tex", type=int, default=1)
 p.add_argument("--torch-profile", action="store_true"); p.add_argument("--graph", action="store_true"); p.add_argument("--ops", action="store_true", help="eager step under torch.profiler: aten ops by count and shapes")
 p.add_argument("--series", type=int, default=0)
+p.add_argument("--symmetric", action="store_true", help="with --mesh sphereL: the half-size mean shape, mirrored on the GPU")
 a = p.parse_args()
 d = torch.device("cuda:0")
-m = np.load(os.path.join(ROOT, "tests", "golden", "meshes.npz")); v, f = m[a.mesh + "_v"], m[a.mesh + "_f"]
+sym = None
+if a.mesh.startswith("sphere"):          # --mesh sphere3: the reference's symmetric template (template.py), 642 vertices
+    from acfm_video_3d_reconstruction_amd import template
+    v, f, n_indept, n_sym, _, _ = template.make_symmetric(*template.create_sphere(int(a.mesh[6:])))
+    v, sym = v.astype(np.float32), ((n_indept, n_sym) if a.symmetric else None)
+else:
+    assert not a.symmetric, "--symmetric needs --mesh sphereL"
+    m = np.load(os.path.join(ROOT, "tests", "golden", "meshes.npz")); v, f = m[a.mesh + "_v"], m[a.mesh + "_f"]
 rng = np.random.default_rng(0); B, T, G, H, Kh = a.B, 2, a.G, a.img, 15
 N = B * T
 step = MultiframeStep(torch.tensor(v, device=d), torch.tensor(f, device=d), torch.tensor(fps_lbs_logits(v, Kh), device=d),
                       num_training_frames=4 * N, img_size=H, num_guesses=G, num_lbs=Kh, scale_lr_decay=1.0,
-                      prior_stream=os.environ.get("ACFM_PRIOR_STREAM", "0") != "0").to(d)
+                      prior_stream=os.environ.get("ACFM_PRIOR_STREAM", "0") != "0",
+                      **({"symmetric": sym} if sym else {})).to(d)
 gt_cams = torch.tensor(make_cams(N, rng, extent=float(np.abs(v).max())), device=d)
 with torch.no_grad():
-    gt, _ = step.renderer(step.solver.mean_v[None].repeat(N, 1, 1), step.faces1[None].expand(N, -1, -1), gt_cams)
+    gt, _ = step.renderer(torch.tensor(v, device=d)[None].repeat(N, 1, 1), step.faces1[None].expand(N, -1, -1), gt_cams)
     gt = (gt > 0.5).float()
 batch = dict(masks=gt, edts_barrier=IU.compute_dt(gt, norm=False)[:, None].contiguous(),
              boundaries=IU.compute_boundaries(gt)[:, :1000].contiguous(),
@@ -74,8 +83,8 @@ if not a.graph:                          # the hipEvent brackets are not part of
     torch.cuda.synchronize()
     prof = _lib.prof_collect(); lib.acfm_prof_enable(0)
     ks = sum(ms for ms, _ in prof.values()) / a.iters
-print(("hipGraph " if a.graph else "eager ") + "multiframe step B=%d T=2 G=%d (%d meshes) @%d, mesh=%s tex=%d: %.2f ms/step (%.0f clip-frames/s)%s" % (
-    B, G, G * N, H, a.mesh, a.tex, 1e3 * dt, N / dt, "" if a.graph else ", HIP kernels %.2f ms" % ks))
+print(("hipGraph " if a.graph else "eager ") + "multiframe step B=%d T=2 G=%d (%d meshes) @%d, mesh=%s%s tex=%d: %.2f ms/step (%.0f clip-frames/s)%s" % (
+    B, G, G * N, H, a.mesh, " symmetric" if sym else "", a.tex, 1e3 * dt, N / dt, "" if a.graph else ", HIP kernels %.2f ms" % ks))
 for k, (ms, c) in sorted(prof.items(), key=lambda kv: -kv[1][0]):
     print("   %-24s %8.1f us/step  x%.0f" % (k, 1e3 * ms / a.iters, c / a.iters))
 
