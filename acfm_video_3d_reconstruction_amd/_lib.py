@@ -126,6 +126,9 @@ SIGNATURES = {
     "acfm_bds_loss": (_i, [_pf, _pf, _p1, _p4, _i, _i, _i, _i, _i, _i, _pf, _p4, _p4, _pf, _sz, _vp]),
     "acfm_bds_loss_backward": (_i, [_pf, _pf, _p4, _p4, _pf, _i, _i, _i, _i, _i, _i, _pf, _vp]),
     "acfm_boundary_subset": (_i, [_p8, _p4, _i, _i, _i, _i, _p4, _vp]),
+    "acfm_surface_sample_workspace_bytes": (_sz, [_i, _i]),
+    "acfm_surface_sample": (_i, [_p8, _pf, _p8, _p8, _vp, _i, _i, _i, _i, _pf, _p4, _pf, _vp, _sz, _vp]),
+    "acfm_surface_sample_backward": (_i, [_pf, _p4, _pf, _p8, _i, _i, _i, _i, _i, _pf, _vp]),
     "acfm_chamfer_partial_floats": (_sz, [_i, _i, _i]),
     "acfm_chamfer": (_i, [_pf, _pf, _p8, _p8, _i, _i, _i, _pf, _p4, _p4, _p4, _pf, _sz, _vp]),
     "acfm_chamfer_backward": (_i, [_pf, _pf, _p8, _p8, _p4, _p4, _pf, _i, _i, _i, _pf, _pf, _vp]),

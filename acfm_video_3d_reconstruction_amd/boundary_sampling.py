@@ -78,14 +78,12 @@ def draw_host(seed, draw, P, n_samples, counts=None, per_mesh=False):
     return subset_host(seed, draw, 0, P0, n_samples)[None]
 
 
-class BoundarySampler:
-    """Holds the device state (seed, draw) of the boundary-point draw, one int64 [2] tensor per device, created on
-    first use there (create it before capturing a graph: call draw() or state_on(device) once eagerly)."""
+class DrawState:
+    """The device state (seed, draw) of a counter-based draw, one int64 [2] tensor per device, created on first use
+    there (what BoundarySampler and surface_sampling.SurfaceSampler share)."""
 
-    def __init__(self, n_samples=1000, seed=0, per_mesh=False):
-        if int(n_samples) <= 0:
-            raise ValueError("BoundarySampler: n_samples must be positive")
-        self.n_samples, self.seed, self.per_mesh = int(n_samples), int(seed), bool(per_mesh)
+    def __init__(self, seed=0):
+        self.seed = int(seed)
         self._states = {}
 
     def state_on(self, device):
@@ -113,6 +111,17 @@ class BoundarySampler:
         for st in self._states.values():
             st.copy_(torch.tensor([self.seed, int(draw)], dtype=torch.int64))
         return self
+
+
+class BoundarySampler(DrawState):
+    """Holds the device state (seed, draw) of the boundary-point draw, one int64 [2] tensor per device, created on
+    first use there (create it before capturing a graph: call draw() or state_on(device) once eagerly)."""
+
+    def __init__(self, n_samples=1000, seed=0, per_mesh=False):
+        if int(n_samples) <= 0:
+            raise ValueError("BoundarySampler: n_samples must be positive")
+        super().__init__(seed)
+        self.n_samples, self.per_mesh = int(n_samples), bool(per_mesh)
 
     def draw(self, P, counts=None, device=None):
         """-> sel int32 [1, n_samples] (shared) or [RB, n_samples] (per mesh); advances the draw counter."""

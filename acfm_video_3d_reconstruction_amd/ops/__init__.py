@@ -9,7 +9,7 @@ is one or more stream-ordered calls into libacfm_hip.so."""
 #        step_losses  mask_losses, tex_mse, bds_loss_per_mesh, combine_losses        <- base, pending
 #        render       setup / cover / prefill caches, LazyPixToFace, the renders     <- base, pending
 #   3. the leaves, plain "allocate, call, return" bindings, each <- base only:
-#        geometry, flow, fragments, hypotheses, mesh_terms, geodesic, uvatlas, lpips, keypoint_loss, symmetry
+#        geometry, flow, fragments, hypotheses, mesh_terms, geodesic, uvatlas, lpips, keypoint_loss, symmetry, surface
 #      (geodesic_distances alone looks up pytorch3d_shim's Meshes when called: the shim is built on this package)
 # State is reached through containers that are mutated in place (dicts, one-element lists), never rebound: a
 # re-export below copies the binding, so `ops.X = ...` would not reach the module that reads X.
@@ -51,3 +51,4 @@ from .lpips import (LPIPS_EPS, LPIPS_SCALE, LPIPS_SHIFT, _LpipsInput, _LpipsLaye
 from .keypoint_loss import (KP_MAX_K, KP_MAX_N, KP_MAX_V, _CameraLoss, _KpHead, _KpWeights, _kp_f32, _kp_limits,
                             camera_loss, kp_head, kp_weights)
 from .symmetry import _Symmetrize, symmetrize, symmetrize_fold
+from .surface import _SurfaceSample, sample_surface, sample_surface_uv

@@ -1,6 +1,8 @@
 """pytorch3d.ops.SubdivideMeshes (multiframe/main.py:196-199; semantics: SURVEY App-A.8) and
 interpolate_face_attributes (the HIP kernel of ops.interpolate_face_attributes); sample_points_from_meshes as
 utils/geometry.py:111-112 calls it."""
+import contextlib
+
 import torch
 
 from ..ops import interpolate_face_attributes  # noqa: F401  (pytorch3d.ops.interpolate_face_attributes)
@@ -70,14 +72,94 @@ def sample_points_from_faces(verts, faces, face_idx, u, v, return_normals=False)
     return points, n / n.norm(dim=2, p=2, keepdim=True).clamp(min=1e-12)
 
 
-def sample_points_from_meshes(meshes, num_samples: int = 10000, return_normals: bool = False):
+_DEFAULT_SAMPLER = [None]     # what default_sampler() installs: used by calls that pass no sampler
+
+
+@contextlib.contextmanager
+def default_sampler(sampler):
+    """with default_sampler(SurfaceSampler(seed)): ...   -- inside the block sample_points_from_meshes calls that pass
+    no sampler use this one, so code that cannot be edited (the reference's fit_verts_to_mesh) draws on the kernel.
+    Off by default; process-wide while the block runs."""
+    prev = _DEFAULT_SAMPLER[0]
+    _DEFAULT_SAMPLER[0] = sampler
+    try:
+        yield sampler
+    finally:
+        _DEFAULT_SAMPLER[0] = prev
+
+
+class _HostSurfacePoints(torch.autograd.Function):
+    """The definition's own points (numpy, bit for bit) as a function of the vertices: the gradient of vertex k of a
+    sample's face is its weight w_k, as in ops.sample_surface's backward."""
+
+    @staticmethod
+    def forward(ctx, verts, ids, w, points):
+        ctx.save_for_backward(ids, w)
+        ctx.P = verts.shape[0]
+        return points.to(verts.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        ids, w = ctx.saved_tensors                                   # [N,S,3] each
+        gv = g.new_zeros((ctx.P, 3))
+        gv.index_add_(0, ids.reshape(-1), (w[..., None].to(g.dtype) * g[:, :, None, :]).reshape(-1, 3))
+        return gv, None, None, None
+
+
+def _sample_with(sampler, meshes, num_samples, return_normals):
+    """The counter-based draw of surface_sampling: the kernel for GPU tensors, the numpy definition for host tensors;
+    the point (host) and the normals are the torch lines of sample_points_from_faces on the drawn faces."""
+    verts, faces = meshes.verts_packed(), meshes.faces_packed()
+    counts = [f.shape[0] for f in meshes.faces_list()]
+    first = [0]
+    for n in counts:
+        first.append(first[-1] + n)
+    N, S = len(meshes), int(num_samples)
+    if verts.is_cuda:
+        from .. import ops
+        sizes = {v.shape[0] for v in meshes.verts_list()}
+        vpm = sizes.pop() if len(sizes) == 1 else 0
+        points, fidx = ops.sample_surface(sampler.state_on(verts.device), verts, faces,
+                                          torch.tensor(first, dtype=torch.int64), S, verts_per_mesh=vpm)
+        if not return_normals:
+            return points
+        live = fidx >= 0
+    else:
+        pts, fi, uv = sampler.draw_host(verts.detach().numpy(), faces.numpy(), first, S)
+        fidx, uv = torch.from_numpy(fi), torch.from_numpy(uv)
+        live = fidx >= 0
+        if faces.shape[0] == 0:
+            points = verts.new_zeros((N, S, 3))
+        else:
+            su = uv[..., 0].sqrt()
+            w = torch.stack([1.0 - su, su * (1.0 - uv[..., 1]), su * uv[..., 1]], -1) * live[..., None]
+            points = _HostSurfacePoints.apply(verts, faces.long()[fidx.long().clamp(min=0)], w, torch.from_numpy(pts))
+        if not return_normals:
+            return points
+    if faces.shape[0] == 0:
+        return points, torch.zeros_like(points)
+    tri = verts[faces.long()[fidx.long().clamp(min=0)]]
+    a, b, c = tri[:, :, 0], tri[:, :, 1], tri[:, :, 2]
+    n = torch.cross(b - a, c - a, dim=2)
+    n = n / n.norm(dim=2, p=2, keepdim=True).clamp(min=1e-12)
+    return points, torch.where(live[..., None], n, torch.zeros_like(n))
+
+
+def sample_points_from_meshes(meshes, num_samples: int = 10000, return_normals: bool = False, sampler=None):
     """PyTorch3D 0.3.0's sampling: per mesh, num_samples faces drawn with replacement with probability proportional to
     their area (0.5 |(v1 - v0) x (v2 - v0)|, no gradient), then a uniform point of each (sample_points_from_faces).
     -> [N, num_samples, 3] (and the faces' unit normals); a mesh without faces yields zeros.  The draws are
     torch.multinomial and torch.rand on the meshes' device: the same distribution as PyTorch3D's, not its random
-    stream."""
+    stream.
+    sampler (a surface_sampling.SurfaceSampler, or the one default_sampler() installed): the draws are that module's
+    counter-based ones instead -- ops.sample_surface on the GPU, its numpy definition on host tensors -- which a
+    hipGraph can contain and a test can predict; areas are then quantised to 24 bits of the mesh's largest face."""
     if meshes.isempty():
         raise ValueError("Meshes are empty.")
+    if sampler is None:
+        sampler = _DEFAULT_SAMPLER[0]
+    if sampler is not None:
+        return _sample_with(sampler, meshes, num_samples, return_normals)
     verts, faces = meshes.verts_packed(), meshes.faces_packed()
     N, dev = len(meshes), verts.device
     with torch.no_grad():

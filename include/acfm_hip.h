@@ -717,6 +717,46 @@ int acfm_bds_loss_backward(const float* verts_xy, const float* bds, const int32_
  * sized by P. */
 int acfm_boundary_subset(int64_t* state, const int32_t* counts, int n_counts, int rows, int P, int n_samples,
                          int32_t* sel, void* stream);
+/* acfm_surface_sample: pytorch3d.ops.sample_points_from_meshes (utils/geometry.py:110-111) on the device: per mesh, S
+ * faces drawn with replacement in proportion to their area, and a uniform point of each.  Packed meshes: verts_packed
+ * [P,3] f32, faces_packed [F,3] i64 (packed vertex ids), faces_first_idx [N+1] i64 ON THE DEVICE (mesh m = faces
+ * [first[m], first[m+1])).  -> points [N,S,3] f32, face_idx [N,S] i32 (row of faces_packed, or -1), uv [N,S,2] f32.
+ *   state  int64[2] = (seed, draw) on the device, used and advanced exactly as by acfm_boundary_subset.
+ * Definition (surface_sampling.surface_sample_host restates it in numpy and is the specification; the kernels equal
+ * it bit for bit, the library being compiled without contraction and with correctly rounded division and sqrt):
+ *   n_f = sqrt((cx cx + cy cy) + cz cz), (cx, cy, cz) = (b - a) x (c - a), in f32 with every operation rounded; 0 when
+ *         not finite or when the face names a vertex outside [0, P);
+ *   q_f = floor((n_f / n_max) 2^24) with n_max the mesh's largest n_f; cdf = the inclusive prefix sum of q in 64-bit
+ *         integers.  A face below 2^-24 of its mesh's largest face is therefore never drawn, and the probabilities of
+ *         the others are those of their areas to within 2^-24 of the largest.
+ *   sample s of mesh m in draw t: (x0, x1, x2, x3) = Philox4x32-10, key (seed lo, seed hi), counter (s, m, t lo, t hi);
+ *         target = ((x0 << 32 | x1) total) >> 64 with total = cdf[last]; the face is the first f with cdf_f > target
+ *         (faces of weight 0 are skipped wherever they lie); u = (x2 >> 8) 2^-24, v = (x3 >> 8) 2^-24;
+ *         su = sqrt(u), (w0, w1, w2) = (1 - su, su (1 - v), su v), point = (w0 a + w1 b) + w2 c.
+ *   A mesh without faces, or whose faces all have weight 0: points 0, face_idx -1, uv 0.
+ * Three launches on the one stream: the CDF (one workgroup per mesh), the samples (one thread each), the counter.  No
+ * host read, no allocation: capturable, and a captured call draws afresh at every replay.
+ *   workspace: acfm_surface_sample_workspace_bytes(N, F) bytes, 256-byte aligned, any contents (8 B per face); fewer is
+ *   ACFM_E_WORKSPACE.  The query returns 0 for sizes the call refuses.
+ *   faces_first_idx_host: NULL, or the caller's HOST copy of the table, which is then checked: ACFM_E_BADARG unless
+ *   0 <= first[0] <= ... <= first[N] <= F.  The kernels clamp the device table the same way, so a table that does not
+ *   describe the arrays never leads outside them.
+ *   ACFM_E_BADARG also for N < 1, N > 65535, S < 1, P < 1, F < 0, or 3 P, 3 F or 3 N S past 2^31 - 1.  F = 0 is allowed
+ *   (faces_packed may then be NULL).
+ * acfm_surface_sample_backward: grad_points [N,S,3] -> grad_verts [P,3] = sum over the samples of w_k grad_point at the
+ *   three vertices of its face; EVERY row is written.  verts_per_mesh > 0: the packed arrays are N equal-sized meshes
+ *   one after the other (mesh m = vertices [m vpm, (m+1) vpm), and its faces name only those): one workgroup per mesh
+ *   adds in LDS, 12 B per vertex, at most 150 KB: verts_per_mesh <= 12,800.  0, larger meshes and a verts_per_mesh with
+ *   N verts_per_mesh != P: a zero fill and global float atomics, same result.  Either way the order of the float
+ *   additions varies from run to run: the gradient is NOT bit-reproducible. */
+size_t acfm_surface_sample_workspace_bytes(int N, int F);
+int acfm_surface_sample(int64_t* state, const float* verts_packed, const int64_t* faces_packed,
+                        const int64_t* faces_first_idx, const int64_t* faces_first_idx_host, int N, int S, int P, int F,
+                        float* points, int32_t* face_idx, float* uv, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int acfm_surface_sample_backward(const float* grad_points, const int32_t* face_idx, const float* uv,
+                                 const int64_t* faces_packed, int N, int S, int P, int F, int verts_per_mesh,
+                                 float* grad_verts, void* stream);
 
 /* ---- the step's tail in one launch ------------------------------------------------------------------------------
  * acfm_step_losses_forward: any of acfm_mask_losses, acfm_tex_mse and acfm_bds_loss (each in its ticket form) on
