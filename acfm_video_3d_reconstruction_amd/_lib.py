@@ -132,6 +132,10 @@ SIGNATURES = {
     "acfm_chamfer_partial_floats": (_sz, [_i, _i, _i]),
     "acfm_chamfer": (_i, [_pf, _pf, _p8, _p8, _i, _i, _i, _pf, _p4, _p4, _p4, _pf, _sz, _vp]),
     "acfm_chamfer_backward": (_i, [_pf, _pf, _p8, _p8, _p4, _p4, _pf, _i, _i, _i, _pf, _pf, _vp]),
+    "acfm_knn_points": (_i, [_pf, _pf, _p8, _p8, _i, _i, _i, _i, _pf, _p8, _vp]),
+    "acfm_knn_points_backward": (_i, [_pf, _pf, _p8, _p8, _p8, _pf, _i, _i, _i, _i, _pf, _pf, _vp]),
+    "acfm_knn_gather": (_i, [_pf, _vp, _i, _p8, _i, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_knn_gather_backward": (_i, [_pf, _vp, _i, _p8, _i, _i, _i, _i, _i, _pf, _vp]),
     "acfm_mesh_term_partial_floats": (_sz, [_i]),
     "acfm_edge_length_loss": (_i, [_pf, _p8, _pf, _i, _i, _f, _pf, _p4, _pf, _sz, _vp]),
     "acfm_edge_length_loss_backward": (_i, [_pf, _p8, _pf, _pf, _i, _i, _f, _pf, _vp]),

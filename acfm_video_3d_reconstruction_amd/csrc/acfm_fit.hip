@@ -6,6 +6,7 @@
 // the same bits on every run.  The backward kernels add with float atomics (LDS or global): their sums can differ
 // in the last bits from run to run.
 #include "acfm_common.h"
+#include "acfm_points.h"
 #include "acfm_row_finish.h"
 
 namespace acfm {
@@ -21,17 +22,7 @@ namespace acfm {
 constexpr int CH_TPB = 256;
 constexpr int CH_TILE = 256;   // candidates per wave and round: four per lane
 constexpr int CH_Q = 64;       // query points per workgroup
-
-__device__ __forceinline__ int clamped_len(const int64_t* __restrict__ len, int n, int P) {
-  if (!len) return P;
-  const int64_t l = len[n];
-  return l < 0 ? 0 : (l > (int64_t)P ? P : (int)l);
-}
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// (clamped_len, wave_lds_sync and CH_BWD_LDS_MAX_P: acfm_points.h, shared with acfm_knn.hip)
 
 __global__ __launch_bounds__(CH_TPB) void k_chamfer(const float* __restrict__ x, const float* __restrict__ y,
                                                     const int64_t* __restrict__ x_len, const int64_t* __restrict__ y_len,
@@ -108,7 +99,6 @@ __global__ __launch_bounds__(CH_TPB) void k_chamfer(const float* __restrict__ x,
 // CH_BWD_LDS_MAX_P points on the larger side.  Past that k_chamfer_bwd_own / k_chamfer_bwd_scatter do the same with
 // global atomics.  The order of the float additions varies: gradients are not bit-reproducible.
 constexpr int CHB_TPB = 512;
-constexpr int CH_BWD_LDS_MAX_P = 12800;
 
 struct ChSide {
   const float* own; const float* other;

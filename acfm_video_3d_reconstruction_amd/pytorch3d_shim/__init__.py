@@ -3,6 +3,7 @@
 `structures.Meshes`, `loss.mesh_laplacian_smoothing`, `ops.SubdivideMeshes`, `io.load_obj`, and what
 utils/geometry.py:63-72 imports for the template fit (`io.save_obj`, `utils.ico_sphere`,
 `ops.sample_points_from_meshes`, `loss.{chamfer_distance, mesh_edge_loss, mesh_normal_consistency}`),
+PyTorch3D 0.3.0's point-set pair `ops.{knn_points, knn_gather}`,
 `transforms.{standardize_quaternion, quaternion_multiply, matrix_to_quaternion, ...}`.
 
 It is a shape-compatible shim (same names, arguments, return types), not PyTorch3D.  Of the

@@ -68,8 +68,9 @@ def _zero(meshes):
 
 
 def _chamfer_sums_host(x, y, xl, yl):
-    """[N,2] as ops.chamfer_sums, with torch ops: the nearest index is chosen under no_grad (first occurrence of the
-    minimum), the distance to it is differentiable."""
+    """(sums [N,2], idx_x [N,P1], idx_y [N,P2]) as ops.chamfer_nearest, with torch ops: the nearest index is chosen
+    under no_grad (first occurrence of the minimum; 0 where the other cloud is empty), the distance to it is
+    differentiable."""
     N, P1, _ = x.shape
     P2 = y.shape[1]
     with torch.no_grad():
@@ -90,18 +91,24 @@ def _chamfer_sums_host(x, y, xl, yl):
     ey = torch.where(vy[:, :, None], y, zero) - torch.where(vy[:, :, None], x.gather(1, iy[:, :, None].expand(-1, -1, 3)), zero)
     cx = ((ex[..., 0] * ex[..., 0] + ex[..., 1] * ex[..., 1]) + ex[..., 2] * ex[..., 2]).sum(1)
     cy = ((ey[..., 0] * ey[..., 0] + ey[..., 1] * ey[..., 1]) + ey[..., 2] * ey[..., 2]).sum(1)
-    return torch.stack([cx, cy], 1)
+    return torch.stack([cx, cy], 1), ix, iy
 
 
 def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
                      batch_reduction="mean", point_reduction="mean"):
-    """-> (loss, None).  x [N,P1,3], y [N,P2,3] float32 tensors (Pointclouds are not supported); cham_x[n] =
+    """-> (loss, loss_normals).  x [N,P1,3], y [N,P2,3] float32 tensors (Pointclouds are not supported); cham_x[n] =
     sum_{i < x_lengths[n]} min_{j < y_lengths[n]} |x_i - y_j|^2 and cham_y its mirror image, times weights[n]; divided by
     the lengths for point_reduction "mean"; summed over the batch for batch_reduction "sum", and divided by N (by
     weights.sum() with weights) for "mean"; loss = cham_x + cham_y.  A length of 0 gives a sum of 0 (and 0 / 0 under
-    "mean").  Among equal distances the lowest index is the nearest neighbour."""
-    if x_normals is not None or y_normals is not None:
-        raise ValueError("chamfer_distance: x_normals / y_normals are not supported (the reference passes none)")
+    "mean").  Among equal distances the lowest index is the nearest neighbour.
+    loss_normals is None unless x_normals [N,P1,3] and y_normals [N,P2,3] are both given; then it is formed as
+    PyTorch3D forms it: per point 1 - |cosine_similarity(own normal, the nearest point's normal, eps=1e-6)| (knn_gather
+    of the other cloud's normals by the nearest-neighbour indices; the normal of a point without a neighbour is 0, its
+    term 1), rows at or past a length removed, then the weights and reductions of the distance term.  Gradients reach
+    the normals; the points get none from this term (the index is an integer).  One of the two alone is refused."""
+    if (x_normals is None) != (y_normals is None):
+        raise ValueError("chamfer_distance: x_normals and y_normals must be given together (got only %s)"
+                         % ("x_normals" if y_normals is None else "y_normals"))
     if batch_reduction is not None and batch_reduction not in ("mean", "sum"):
         raise ValueError('batch_reduction must be one of ["mean", "sum"] or None')
     if point_reduction not in ("mean", "sum"):
@@ -116,25 +123,51 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
     for name, t in (("x_lengths", x_lengths), ("y_lengths", y_lengths), ("weights", weights)):
         if t is not None and tuple(t.shape) != (N,):
             raise ValueError("chamfer_distance: %s must have shape (N,) = (%d,)" % (name, N))
+    if x_normals is not None:
+        if tuple(x_normals.shape) != tuple(x.shape) or tuple(y_normals.shape) != tuple(y.shape):
+            raise ValueError("chamfer_distance: x_normals / y_normals must have the shapes of x / y, got %s and %s"
+                             % (tuple(x_normals.shape), tuple(y_normals.shape)))
     if x.is_cuda:
         from .. import ops
-        sums = ops.chamfer_sums(x, y, x_lengths, y_lengths)
+        sums, ix, iy = ops.chamfer_nearest(x, y, x_lengths, y_lengths)
     else:
         xl = torch.full((N,), P1, dtype=torch.int64) if x_lengths is None else x_lengths.long().clamp(0, P1)
         yl = torch.full((N,), P2, dtype=torch.int64) if y_lengths is None else y_lengths.long().clamp(0, P2)
-        sums = _chamfer_sums_host(x.float(), y.float(), xl, yl)
-    cham_x, cham_y = sums[:, 0], sums[:, 1]
-    if weights is not None:
-        cham_x, cham_y = cham_x * weights, cham_y * weights
-    if point_reduction == "mean":
-        cham_x = cham_x / (float(P1) if x_lengths is None else x_lengths.to(cham_x.dtype))
-        cham_y = cham_y / (float(P2) if y_lengths is None else y_lengths.to(cham_y.dtype))
-    if batch_reduction is not None:
-        cham_x, cham_y = cham_x.sum(), cham_y.sum()
-        if batch_reduction == "mean":
-            div = weights.sum() if weights is not None else float(N)
-            cham_x, cham_y = cham_x / div, cham_y / div
-    return cham_x + cham_y, None
+        sums, ix, iy = _chamfer_sums_host(x.float(), y.float(), xl, yl)
+
+    def reduce(cham_x, cham_y):
+        if weights is not None:
+            cham_x, cham_y = cham_x * weights, cham_y * weights
+        if point_reduction == "mean":
+            cham_x = cham_x / (float(P1) if x_lengths is None else x_lengths.to(cham_x.dtype))
+            cham_y = cham_y / (float(P2) if y_lengths is None else y_lengths.to(cham_y.dtype))
+        if batch_reduction is not None:
+            cham_x, cham_y = cham_x.sum(), cham_y.sum()
+            if batch_reduction == "mean":
+                div = weights.sum() if weights is not None else float(N)
+                cham_x, cham_y = cham_x / div, cham_y / div
+        return cham_x + cham_y
+
+    loss = reduce(sums[:, 0], sums[:, 1])
+    if x_normals is None:
+        return loss, None
+    return loss, reduce(_normal_sums(x_normals, y_normals, ix, x_lengths, y_lengths),
+                        _normal_sums(y_normals, x_normals, iy, y_lengths, x_lengths))
+
+
+def _normal_sums(own, other, idx, own_lengths, other_lengths):
+    """[N]: sum over the rows inside own_lengths of 1 - |cos(own normal, other[idx])|.  idx [N,P] are the nearest
+    neighbours' indices; rows at or past a length (which may hold NaN, and an unwritten index) leave through `where`."""
+    from .ops import knn_gather
+    near = knn_gather(other, idx[:, :, None], other_lengths)[:, :, 0]
+    if own_lengths is None:
+        return (1.0 - torch.nn.functional.cosine_similarity(own, near, dim=2, eps=1e-6).abs()).sum(1)
+    # the padded rows leave before the cosine as well: behind it a NaN would come back as 0 x NaN in the backward
+    live = torch.arange(own.shape[1], device=own.device)[None] < own_lengths[:, None]
+    zero = torch.zeros((), dtype=own.dtype, device=own.device)
+    own, near = torch.where(live[:, :, None], own, zero), torch.where(live[:, :, None], near, zero)
+    term = 1.0 - torch.nn.functional.cosine_similarity(own, near, dim=2, eps=1e-6).abs()
+    return torch.where(live, term, zero).sum(1)
 
 
 def mesh_edge_loss(meshes, target_length: float = 0.0):

@@ -1,6 +1,8 @@
 """pytorch3d.ops.SubdivideMeshes (multiframe/main.py:196-199; semantics: SURVEY App-A.8) and
 interpolate_face_attributes (the HIP kernel of ops.interpolate_face_attributes); sample_points_from_meshes as
-utils/geometry.py:111-112 calls it."""
+utils/geometry.py:111-112 calls it; knn_points / knn_gather, PyTorch3D 0.3.0's point-set pair (the kernels of
+csrc/acfm_knn.hip for GPU tensors, the same definition in torch ops for host tensors)."""
+import collections
 import contextlib
 
 import torch
@@ -183,3 +185,89 @@ def sample_points_from_meshes(meshes, num_samples: int = 10000, return_normals: 
     if return_normals:
         return torch.where(live, out[0], torch.zeros_like(out[0])), torch.where(live, out[1], torch.zeros_like(out[1]))
     return torch.where(live, out, torch.zeros_like(out))
+
+
+# ------------------------------------------------------------------------------------------ knn_points, knn_gather
+_KNN = collections.namedtuple("KNN", "dists idx knn")
+
+
+def _sq_dist(e):
+    """Sum of squares over the last dimension, left to right: (dx dx + dy dy) + dz dz for D = 3, as the kernels."""
+    acc = e[..., 0] * e[..., 0]
+    for k in range(1, e.shape[-1]):
+        acc = acc + e[..., k] * e[..., k]
+    return acc
+
+
+def _knn_points_host(p1, p2, l1, l2, K):
+    """The definition of ops.knn_points in torch ops, any D: the K nearest are chosen under no_grad (numpy's stable
+    argsort: the lower index first among equal distances), the distances to them are recomputed differentiably."""
+    N, P1, _ = p1.shape
+    P2 = p2.shape[1]
+    with torch.no_grad():
+        d = _sq_dist(p1[:, :, None, :] - p2[:, None, :, :])                       # [N,P1,P2]
+        v1 = torch.arange(P1)[None] < l1[:, None]                                 # [N,P1] rows that count
+        v2 = torch.arange(P2)[None] < l2[:, None]
+        d = torch.where(v1[:, :, None] & v2[:, None, :], d, torch.full_like(d, float("inf")))   # (padding may hold NaN)
+        order = torch.from_numpy(d.numpy().argsort(axis=2, kind="stable"))[:, :, :K]
+        idx = torch.zeros((N, P1, K), dtype=torch.int64)
+        idx[:, :, :order.shape[2]] = order
+        valid = v1[:, :, None] & (torch.arange(K)[None, None, :] < l2.clamp(max=K)[:, None, None])
+        idx = torch.where(valid, idx, torch.zeros_like(idx))
+    zero = torch.zeros((), dtype=p1.dtype)
+    near = p2[:, :, None, :].expand(N, P2, K, p2.shape[2]).gather(1, idx[..., None].expand(N, P1, K, p2.shape[2]))
+    e = torch.where(valid[..., None], p1[:, :, None, :], zero) - torch.where(valid[..., None], near, zero)
+    return _sq_dist(e), idx
+
+
+def knn_points(p1, p2, lengths1=None, lengths2=None, K: int = 1, version: int = -1, return_nn: bool = False,
+               return_sorted: bool = True):
+    """pytorch3d.ops.knn_points -> the namedtuple (dists [N,P1,K], idx [N,P1,K] int64, knn [N,P1,K,D] or None).  For
+    every point of p1[n, :lengths1[n]] its min(K, lengths2[n]) nearest points of p2[n, :lengths2[n]]: squared distances,
+    ascending, the lower index first among equal distances; every other slot holds 0 / 0 (PyTorch3D's padding).  Rows
+    at or past a length are never used (they may hold NaN).  knn = knn_gather(p2, idx, lengths2) when return_nn.
+    `version` is accepted and ignored; return_sorted=False returns the same sorted lists (PyTorch3D leaves that order
+    open).  GPU tensors run ops.knn_points (float32, D = 3, K <= 32; the gradient of p2 is summed with float atomics
+    and is not bit-reproducible); host tensors run the same definition in torch ops with any D and K."""
+    if not torch.is_tensor(p1) or not torch.is_tensor(p2) or p1.dim() != 3 or p2.dim() != 3:
+        raise ValueError("knn_points: p1 [N,P1,D] and p2 [N,P2,D] tensors expected")
+    if p1.shape[0] != p2.shape[0]:
+        raise ValueError("pts1 and pts2 must have the same batch dimension.")
+    if p1.shape[2] != p2.shape[2]:
+        raise ValueError("pts1 and pts2 must have the same point dimension.")
+    N, P1, P2 = p1.shape[0], p1.shape[1], p2.shape[1]
+    for name, t in (("lengths1", lengths1), ("lengths2", lengths2)):
+        if t is not None and tuple(t.shape) != (N,):
+            raise ValueError("knn_points: %s must have shape (N,) = (%d,)" % (name, N))
+    if p1.is_cuda:
+        from .. import ops
+        dists, idx = ops.knn_points(p1, p2, lengths1, lengths2, K)
+    else:
+        if int(K) != K or K < 1:
+            raise ValueError("knn_points: K must be at least 1, got %r" % (K,))
+        if N == 0 or P1 == 0 or P2 == 0:
+            raise ValueError("knn_points: p1 and p2 must hold at least one cloud of at least one point each")
+        l1 = torch.full((N,), P1, dtype=torch.int64) if lengths1 is None else lengths1.long().clamp(0, P1)
+        l2 = torch.full((N,), P2, dtype=torch.int64) if lengths2 is None else lengths2.long().clamp(0, P2)
+        dists, idx = _knn_points_host(p1, p2, l1, l2, int(K))
+    return _KNN(dists, idx, knn_gather(p2, idx, lengths2) if return_nn else None)
+
+
+def knn_gather(x, idx, lengths=None):
+    """pytorch3d.ops.knn_gather: x [N,M,U], idx [N,L,K], lengths [N] of x's clouds or None -> [N,L,K,U] with
+    out[n,l,k] = x[n, idx[n,l,k]], and zeros where k >= lengths[n].  On the GPU (ops.knn_gather) an index outside
+    [0, M) is not dereferenced and yields zeros; on the host it raises as torch.gather does."""
+    if x.dim() != 3 or idx.dim() != 3 or x.shape[0] != idx.shape[0]:
+        raise ValueError("knn_gather: x [N,M,U] and idx [N,L,K] expected, got %s and %s" % (tuple(x.shape), tuple(idx.shape)))
+    N, M, U = x.shape
+    _, L, K = idx.shape
+    if lengths is not None and tuple(lengths.shape) != (N,):
+        raise ValueError("x and lengths must have same batch dimension.")
+    if x.is_cuda:
+        from .. import ops
+        return ops.knn_gather(x, idx, lengths)
+    out = x[:, :, None, :].expand(N, M, K, U).gather(1, idx.long()[..., None].expand(N, L, K, U))
+    if lengths is None:
+        return out
+    dead = torch.arange(K)[None, :] >= lengths.long()[:, None]                     # [N,K]
+    return torch.where(dead[:, None, :, None], torch.zeros((), dtype=x.dtype), out)

@@ -855,6 +855,34 @@ int acfm_chamfer(const float* x, const float* y, const int64_t* x_len, const int
 int acfm_chamfer_backward(const float* x, const float* y, const int64_t* x_len, const int64_t* y_len,
                           const int32_t* idx_x, const int32_t* idx_y, const float* grad_sums, int N, int P1, int P2,
                           float* grad_x, float* grad_y, void* stream);
+/* ---- point sets (PyTorch3D 0.3.0's pytorch3d.ops.knn) ------------------------------------------
+ * acfm_knn_points: pytorch3d.ops.knn_points.  p1 [N,P1,3], p2 [N,P2,3] f32; lengths1, lengths2 [N] i64 on the device
+ *   or NULL (= P1 / P2; values are clamped to [0, P]); 1 <= K <= 32; N <= 65535.  Rows at or past a length are never
+ *   read.  dists [N,P1,K] f32, idx [N,P1,K] i64: slot (n, i, k) with i < lengths1[n] and k < min(K, lengths2[n]) holds
+ *   the k-th smallest |p1_i - p2_j|^2 = (dx dx + dy dy) + dz dz (f32, each operation rounded, as acfm_chamfer) and
+ *   its j; ascending, the lower index first among equal distances.  EVERY other slot is written with 0 / 0 (PyTorch3D's
+ *   padding), and so is a slot that no finite distance reached.  No workspace, no atomics: the same bits on every run.
+ * acfm_knn_points_backward: grad_dists [N,P1,K] -> grad_p1 [N,P1,3] = sum_k 2 g (p1_i - p2[idx]) over the valid
+ *   slots, and grad_p2 [N,P2,3], which receives the negated terms; EVERY row of both is written (zeros at and past the
+ *   lengths); grad_dists is read at valid slots only, a slot whose index is outside [0, lengths2[n]) sends nothing.
+ *   P2 <= 12,800 and P1 K <= 16,384: one workgroup per cloud sums grad_p2 in LDS (12 B per point, at most 150 KB);
+ *   larger clouds or more slots: global float atomics behind a zero fill, same result.  Either way grad_p2 is NOT
+ *   bit-reproducible (grad_p1 is).
+ * acfm_knn_gather: pytorch3d.ops.knn_gather.  x [N,M,U] f32 (U >= 1), idx [N,L,K] i64 (idx_is_int64 != 0) or i32,
+ *   lengths [N] i64 of x's clouds or NULL (= M; clamped to [0, M]) -> out [N,L,K,U], out[n,l,k] = x[n, idx[n,l,k]].
+ *   Where k >= lengths[n] or the index is outside [0, M) zeros are written and x is not read.
+ * acfm_knn_gather_backward: grad_out [N,L,K,U] -> grad_x [N,M,U], zeroed first, then added into with float atomics
+ *   under the same two tests (NOT bit-reproducible where an index occurs more than once).
+ * All four: ACFM_E_BADARG for K outside its range, non-positive sizes or sizes whose element counts overflow. */
+int acfm_knn_points(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, int N, int P1,
+                    int P2, int K, float* dists, int64_t* idx, void* stream);
+int acfm_knn_points_backward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2,
+                             const int64_t* idx, const float* grad_dists, int N, int P1, int P2, int K, float* grad_p1,
+                             float* grad_p2, void* stream);
+int acfm_knn_gather(const float* x, const void* idx, int idx_is_int64, const int64_t* lengths, int N, int M, int U,
+                    int L, int K, float* out, void* stream);
+int acfm_knn_gather_backward(const float* grad_out, const void* idx, int idx_is_int64, const int64_t* lengths, int N,
+                             int M, int U, int L, int K, float* grad_x, void* stream);
 /* acfm_edge_length_loss: pytorch3d.loss.mesh_edge_loss on packed meshes: loss = sum_e eweight[e] (|v_a - v_b| - target)^2
  *   (eweight = 1 / edges of the edge's mesh; the caller divides by the mesh count).  verts [P,3], edges [E,2] i64,
  *   eweight [E].  An edge with a vertex outside [0, P) is skipped; the subgradient at a zero-length edge is 0.
