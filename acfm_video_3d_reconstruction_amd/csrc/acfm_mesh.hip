@@ -5,8 +5,10 @@
 //   acfm_edge_rigidity{,_backward} <- loss_utils.locally_rigid_fn            (loss_utils.py:150-164)
 // All take PACKED meshes (verts [P,3], faces / edges with packed vertex ids), i.e. any mix of
 // topologies.  The torch-op formulations launch 10-20 small kernels each (index_add, norm, ...);
-// here each is one or two passes with float atomics (results differ from a sequential sum in the
-// last bits only).
+// here each is one or two passes.  The LOSSES of the per-mesh Laplacian path and of the edge rigidity (up to
+// RIGID_ORDERED_MAX edges) are summed in a fixed order and repeat their bits from launch to launch; the gradients, the
+// global-atomic Laplacian path's W v and larger rigidity batches still use float atomics (results differ from a
+// sequential sum, and from call to call, in the last bits only).
 #include "acfm_common.h"
 
 namespace acfm {
@@ -120,10 +122,8 @@ __global__ __launch_bounds__(MTPB) void k_lap_vertex(const float* __restrict__ v
                                                      const float* __restrict__ Wv,
                                                      const float* __restrict__ rowsum,
                                                      const float* __restrict__ vweight, int P,
-                                                     float* __restrict__ glv, float* __restrict__ loss) {
-  __shared__ float s_red[4];
+                                                     float* __restrict__ glv, float* __restrict__ vterm) {
   const int v = blockIdx.x * MTPB + threadIdx.x;
-  float contrib = 0.f;
   if (v < P) {
     const float rs = rowsum[v];
     const float nw = rs > 0.f ? 1.0f / rs : 0.f;
@@ -132,14 +132,35 @@ __global__ __launch_bounds__(MTPB) void k_lap_vertex(const float* __restrict__ v
     const float lz = Wv[3 * v + 2] * nw - verts[3 * v + 2];
     const float nrm = sqrtf(lx * lx + ly * ly + lz * lz);
     const float w = vweight[v];
-    contrib = nrm * w;
+    vterm[v] = nrm * w;                            // summed in a fixed order by k_sum_in_order
     const float inv = nrm > 0.f ? w / nrm : 0.f;   // torch: subgradient 0 at the origin
     glv[3 * v] = lx * inv; glv[3 * v + 1] = ly * inv; glv[3 * v + 2] = lz * inv;
   }
-  contrib = wave_sum(contrib);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = contrib;
+}
+
+// out[0] = sum of term[0..n) in an order that depends on n only: thread t adds term[t], term[t + STB], ... in turn, the
+// wave sums go through the fixed butterfly and thread 0 adds the 16 of them in order.  ONE workgroup, behind a kernel
+// that stored one term per vertex -- in place of a float atomic per workgroup on out[0], whose sum depends on which
+// workgroup arrives first (the loss did not repeat its own last bit from call to call).
+constexpr int STB = 1024;
+__global__ __launch_bounds__(STB) void k_sum_in_order(const float* __restrict__ term, int n, float* __restrict__ out) {
+  __shared__ float s_red[STB / 64];
+  // (four running sums per thread, joined in a fixed order: the loads of four rounds are in flight together)
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  for (int i = threadIdx.x; i < n; i += 4 * STB) {
+    s0 += term[i];
+    if (i + STB < n) s1 += term[i + STB];
+    if (i + 2 * STB < n) s2 += term[i + 2 * STB];
+    if (i + 3 * STB < n) s3 += term[i + 3 * STB];
+  }
+  float s = wave_sum((s0 + s1) + (s2 + s3));
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss, s_red[0] + s_red[1] + s_red[2] + s_red[3]);
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int i = 0; i < STB / 64; ++i) t += s_red[i];
+    out[0] = t;
+  }
 }
 
 // backward: d loss / d v_j = sum_i w_ij nw_i glv_i - glv_j  (weights are constants)
@@ -195,39 +216,60 @@ __global__ __launch_bounds__(LTB) void k_lap_mesh_fwd(const float* __restrict__ 
                                                       const int64_t* __restrict__ faces,
                                                       const float* __restrict__ vweight, int vpm, int fpm,
                                                       float* __restrict__ rowsum_out, float* __restrict__ glv,
-                                                      float* __restrict__ wface, float* __restrict__ loss) {
+                                                      float* __restrict__ wface, float* __restrict__ vterm) {
   extern __shared__ float s_l[];           // Wv [vpm][3], rowsum [vpm]
-  __shared__ float s_red[LTB / 64];
   float* s_wv = s_l;
   float* s_rs = s_l + 3 * (size_t)vpm;
   const int m = blockIdx.x, tid = threadIdx.x;
   const long vb = (long)m * vpm;
   for (int i = tid; i < 4 * vpm; i += LTB) s_l[i] = 0.f;
   __syncthreads();
-  for (int fl = tid; fl < fpm; fl += LTB) {
-    const size_t f = (size_t)m * fpm + fl;
-    const long i0 = faces[3 * f] - vb, i1 = faces[3 * f + 1] - vb, i2 = faces[3 * f + 2] - vb;
-    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= vpm || i1 >= vpm || i2 >= vpm) {
-      wface[3 * f] = 0.f; wface[3 * f + 1] = 0.f; wface[3 * f + 2] = 0.f;
-      continue;
+  // (every thread walks the same number of rounds: the loop holds barriers)
+  for (int base = 0; base < fpm; base += LTB) {
+    const int fl = base + tid;
+    bool ok = false;
+    long vi[3] = {0, 0, 0};
+    float cw[3][4];                              // per corner: its (x, y, z) term and its row-sum weight
+    if (fl < fpm) {
+      const size_t f = (size_t)m * fpm + fl;
+      const long i0 = faces[3 * f] - vb, i1 = faces[3 * f + 1] - vb, i2 = faces[3 * f + 2] - vb;
+      if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= vpm || i1 >= vpm || i2 >= vpm) {
+        wface[3 * f] = 0.f; wface[3 * f + 1] = 0.f; wface[3 * f + 2] = 0.f;
+      } else {
+        ok = true;
+        const FaceCot c = face_cot(verts, i0 + vb, i1 + vb, i2 + vb);
+        wface[3 * f] = c.cota; wface[3 * f + 1] = c.cotb; wface[3 * f + 2] = c.cotc;
+        // edge (i1,i2) carries cota, (i2,i0) cotb, (i0,i1) cotc: a vertex receives the two terms of its two
+        // edges of this face in one go (12 LDS atomics per face instead of 24)
+        vi[0] = i0; vi[1] = i1; vi[2] = i2;
+        const float wa[3] = {c.cotc, c.cota, c.cotb};   // weight towards the next vertex of the face
+        const float wb[3] = {c.cotb, c.cotc, c.cota};   // weight towards the previous one
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const long jn = vi[(k + 1) % 3] + vb, jp = vi[(k + 2) % 3] + vb;
+#pragma unroll
+          for (int d = 0; d < 3; ++d) cw[k][d] = wa[k] * verts[3 * jn + d] + wb[k] * verts[3 * jp + d];
+          cw[k][3] = wa[k] + wb[k];
+        }
+      }
     }
-    const FaceCot c = face_cot(verts, i0 + vb, i1 + vb, i2 + vb);
-    wface[3 * f] = c.cota; wface[3 * f + 1] = c.cotb; wface[3 * f + 2] = c.cotc;
-    // edge (i1,i2) carries cota, (i2,i0) cotb, (i0,i1) cotc: a vertex receives the two terms of its two
-    // edges of this face in one go (12 LDS atomics per face instead of 24)
-    const long vi[3] = {i0, i1, i2};
-    const float wa[3] = {c.cotc, c.cota, c.cotb};   // weight towards the next vertex of the face
-    const float wb[3] = {c.cotb, c.cotc, c.cota};   // weight towards the previous one
+    // The float adds into LDS, one wave at a time and the waves in order: which wave is scheduled first no longer
+    // shows in a vertex's sum (with all waves adding at once the loss differed in its last bit between calls on the
+    // same values).  Between the lanes of ONE wave's atomic instruction that meet on an address the LDS unit decides
+    // the order; it has been the same from launch to launch on gfx950 (tests/test_gpu_mesh_repeatable.py), but the
+    // ISA does not promise it: a sum in face order would need a per-vertex gather over an adjacency list.
+    for (int w = 0; w < LTB / 64; ++w) {
+      if (ok && (tid >> 6) == w) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const long i = vi[k], jn = vi[(k + 1) % 3] + vb, jp = vi[(k + 2) % 3] + vb;
+        for (int k = 0; k < 3; ++k) {
 #pragma unroll
-      for (int d = 0; d < 3; ++d) atomicAdd(&s_wv[3 * i + d], wa[k] * verts[3 * jn + d] + wb[k] * verts[3 * jp + d]);
-      atomicAdd(&s_rs[i], wa[k] + wb[k]);
+          for (int d = 0; d < 3; ++d) atomicAdd(&s_wv[3 * vi[k] + d], cw[k][d]);
+          atomicAdd(&s_rs[vi[k]], cw[k][3]);
+        }
+      }
+      __syncthreads();
     }
   }
-  __syncthreads();
-  float contrib = 0.f;
   for (int vl = tid; vl < vpm; vl += LTB) {
     const size_t v = (size_t)vb + vl;
     const float rs = s_rs[vl];
@@ -238,17 +280,9 @@ __global__ __launch_bounds__(LTB) void k_lap_mesh_fwd(const float* __restrict__ 
     const float lz = s_wv[3 * vl + 2] * nw - verts[3 * v + 2];
     const float nrm = sqrtf(lx * lx + ly * ly + lz * lz);
     const float w = vweight[v];
-    contrib += nrm * w;
+    vterm[v] = nrm * w;                            // summed in a fixed order by k_sum_in_order
     const float inv = nrm > 0.f ? w / nrm : 0.f;   // torch: subgradient 0 at the origin
     glv[3 * v] = lx * inv; glv[3 * v + 1] = ly * inv; glv[3 * v + 2] = lz * inv;
-  }
-  contrib = wave_sum(contrib);
-  if ((tid & 63) == 0) s_red[tid >> 6] = contrib;
-  __syncthreads();
-  if (tid == 0) {
-    float t = 0.f;
-    for (int i = 0; i < LTB / 64; ++i) t += s_red[i];
-    atomicAdd(loss, t);
   }
 }
 
@@ -288,19 +322,52 @@ __global__ __launch_bounds__(LTB) void k_lap_mesh_bwd(const int64_t* __restrict_
 }
 
 // ---- a14: edge rigidity --------------------------------------------------------------------
+__device__ __forceinline__ float rigid_term(const float* __restrict__ v, const int64_t* __restrict__ e,
+                                            const float* __restrict__ vt, const int64_t* __restrict__ et, int i) {
+  const long a = e[2 * i], b = e[2 * i + 1], at = et[2 * i], bt = et[2 * i + 1];
+  const float dx = v[3 * a] - v[3 * b], dy = v[3 * a + 1] - v[3 * b + 1], dz = v[3 * a + 2] - v[3 * b + 2];
+  const float tx = vt[3 * at] - vt[3 * bt], ty = vt[3 * at + 1] - vt[3 * bt + 1], tz = vt[3 * at + 2] - vt[3 * bt + 2];
+  const float d = sqrtf(dx * dx + dy * dy + dz * dz) - sqrtf(tx * tx + ty * ty + tz * tz);
+  return d * d;
+}
+
+// Up to RIGID_ORDERED_MAX edges (a step of 4 frames x 3 camera hypotheses of the 642-vertex template is 23040; one
+// CU walks the edges, which costs more than k_rigid's many workgroups as the batch grows -- 4.6 us against 3.9 at
+// 3840 edges, 25.6 against 5.1 at 32640 before the four running sums -- hence a limit):
+// ONE workgroup, every thread adds its edges i, i + RTB, ... in turn, the wave sums go through the fixed butterfly and
+// thread 0 adds the 16 of them in order and STORES the loss -- the same bits from launch to launch.  k_rigid below adds
+// its workgroups' sums with a float atomic, in the order in which they finish, and did not repeat its own last bit.
+constexpr int RTB = 1024;
+constexpr int RIGID_ORDERED_MAX = 24576;
+__global__ __launch_bounds__(RTB) void k_rigid_ordered(const float* __restrict__ v, const int64_t* __restrict__ e,
+                                                       const float* __restrict__ vt, const int64_t* __restrict__ et,
+                                                       int E, float* __restrict__ loss) {
+  __shared__ float s_red[RTB / 64];
+  // (four running sums per thread, joined in a fixed order: the gathers of four rounds are in flight together)
+  float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f;
+  for (int i = threadIdx.x; i < E; i += 4 * RTB) {
+    c0 += rigid_term(v, e, vt, et, i);
+    if (i + RTB < E) c1 += rigid_term(v, e, vt, et, i + RTB);
+    if (i + 2 * RTB < E) c2 += rigid_term(v, e, vt, et, i + 2 * RTB);
+    if (i + 3 * RTB < E) c3 += rigid_term(v, e, vt, et, i + 3 * RTB);
+  }
+  float c = wave_sum((c0 + c1) + (c2 + c3));
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int i = 0; i < RTB / 64; ++i) t += s_red[i];
+    loss[0] = t;
+  }
+}
+
 __global__ __launch_bounds__(MTPB) void k_rigid(const float* __restrict__ v, const int64_t* __restrict__ e,
                                                 const float* __restrict__ vt, const int64_t* __restrict__ et,
                                                 int E, float* __restrict__ loss) {
   __shared__ float s_red[4];
   const int i = blockIdx.x * MTPB + threadIdx.x;
   float c = 0.f;
-  if (i < E) {
-    const long a = e[2 * i], b = e[2 * i + 1], at = et[2 * i], bt = et[2 * i + 1];
-    const float dx = v[3 * a] - v[3 * b], dy = v[3 * a + 1] - v[3 * b + 1], dz = v[3 * a + 2] - v[3 * b + 2];
-    const float tx = vt[3 * at] - vt[3 * bt], ty = vt[3 * at + 1] - vt[3 * bt + 1], tz = vt[3 * at + 2] - vt[3 * bt + 2];
-    const float d = sqrtf(dx * dx + dy * dy + dz * dz) - sqrtf(tx * tx + ty * ty + tz * tz);
-    c = d * d;
-  }
+  if (i < E) c = rigid_term(v, e, vt, et, i);
   c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = c;
   __syncthreads();
@@ -412,7 +479,7 @@ int acfm_cot_laplacian(const float* verts, const int64_t* faces, int V, int F, f
 
 size_t acfm_laplacian_smoothing_state_floats(int P, int F) {
   if (P <= 0 || F < 0) return 0;
-  return (size_t)7 * P + (size_t)3 * F;  // Wv [P,3] | rowsum [P] | glv [P,3] | wface [F,3]
+  return (size_t)8 * P + (size_t)3 * F;  // Wv [P,3] | rowsum [P] | glv [P,3] | wface [F,3] | vterm [P] (forward only)
 }
 
 // method 0: cot (faces [F,3] packed ids); method 1: uniform (edges [E,2] unique packed edges, F = E).
@@ -429,21 +496,22 @@ int acfm_laplacian_smoothing(const float* verts, const int64_t* conn, const floa
   hipStream_t st = (hipStream_t)stream;
   float* Wv = state; float* rowsum = state + 3 * (size_t)P; float* glv = state + 4 * (size_t)P;
   float* wface = state + 7 * (size_t)P;
+  float* vterm = state + 7 * (size_t)P + 3 * (size_t)F;     // every vertex's term of the loss: k_sum_in_order adds them
   if (lap_blocked(P, F, method, verts_per_mesh, faces_per_mesh)) {
-    if (zero_async(loss, sizeof(float), st) != ACFM_OK) return ACFM_E_LAUNCH;
     hipLaunchKernelGGL(k_lap_mesh_fwd, dim3(P / verts_per_mesh), dim3(LTB), sizeof(float) * 4 * (size_t)verts_per_mesh,
-                       st, verts, conn, vweight, verts_per_mesh, faces_per_mesh, rowsum, glv, wface, loss);
+                       st, verts, conn, vweight, verts_per_mesh, faces_per_mesh, rowsum, glv, wface, vterm);
+    hipLaunchKernelGGL(k_sum_in_order, dim3(1), dim3(STB), 0, st, (const float*)vterm, P, loss);
     ACFM_CHECK_LAUNCH();
     return ACFM_OK;
   }
   if (zero_async(state, sizeof(float) * 4 * (size_t)P, st) != ACFM_OK) return ACFM_E_LAUNCH;
-  if (zero_async(loss, sizeof(float), st) != ACFM_OK) return ACFM_E_LAUNCH;
   if (method == 0)
     hipLaunchKernelGGL(k_lap_accum_faces, dim3(nblk(F, 256)), dim3(256), 0, st, verts, conn, P, F, Wv, rowsum, wface);
   else
     hipLaunchKernelGGL(k_lap_accum_edges, dim3(nblk(F, 256)), dim3(256), 0, st, verts, conn, P, F, Wv, rowsum);
   hipLaunchKernelGGL(k_lap_vertex, dim3(nblk(P, MTPB)), dim3(MTPB), 0, st, verts, (const float*)Wv,
-                     (const float*)rowsum, vweight, P, glv, loss);
+                     (const float*)rowsum, vweight, P, glv, vterm);
+  hipLaunchKernelGGL(k_sum_in_order, dim3(1), dim3(STB), 0, st, (const float*)vterm, P, loss);
   ACFM_CHECK_LAUNCH();
   return ACFM_OK;
 }
@@ -477,6 +545,11 @@ int acfm_edge_rigidity(const float* verts, const int64_t* edges, const float* ve
                        int E, float* loss, void* stream) {
   if (!verts || !edges || !verts_t || !edges_t || !loss || E <= 0) return ACFM_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
+  if (E <= RIGID_ORDERED_MAX) {
+    hipLaunchKernelGGL(k_rigid_ordered, dim3(1), dim3(RTB), 0, st, verts, edges, verts_t, edges_t, E, loss);
+    ACFM_CHECK_LAUNCH();
+    return ACFM_OK;
+  }
   if (zero_async(loss, sizeof(float), st) != ACFM_OK) return ACFM_E_LAUNCH;
   hipLaunchKernelGGL(k_rigid, dim3(nblk(E, MTPB)), dim3(MTPB), 0, st, verts, edges, verts_t, edges_t, E, loss);
   ACFM_CHECK_LAUNCH();

@@ -6,6 +6,7 @@
 ops.kp_weights + ops.kp_head (csrc/acfm_keypoints.hip): two launches forward, three or four back.  On host tensors the
 same reference lines run as torch ops; they are the definition the kernels are tested against."""
 import collections
+import weakref
 
 import torch
 from torch import nn
@@ -32,6 +33,11 @@ def pixel_error(kp_pred, kp_gt, img_size):
     return torch.norm((kp_pred + 1) * img_size / 2 - (kp_gt[..., :2] + 1) * img_size / 2, dim=2)
 
 
+# KeypointHead -> (key, A, entropy) of its last weights() call on the GPU.  Kept beside the module, not in it: A is a
+# non-leaf tensor, which copy.deepcopy / pickling of the module must never meet; a copy starts without an entry.
+_WEIGHTS = weakref.WeakKeyDictionary()
+
+
 class KeypointHead(nn.Module):
     """vert2kp: [K,V] logits, a tensor or an nn.Parameter (mesh_net.py:504-519 builds and learns it)."""
 
@@ -43,10 +49,6 @@ class KeypointHead(nn.Module):
             self.vert2kp = vert2kp
         else:
             self.register_buffer("vert2kp", vert2kp)
-        self._cached = None
-
-    def _drop_cache(self, *_):
-        self._cached = None
 
     def weights(self):
         """(A, entropy): softmax(vert2kp, 1) and entropy_loss(A).  One ops.kp_weights call serves every use until the
@@ -58,12 +60,20 @@ class KeypointHead(nn.Module):
         # (the capture id: tensors made while a hipGraph is captured serve that capture only)
         key = (x.data_ptr(), x._version, tuple(x.shape), torch.is_grad_enabled() and x.requires_grad,
                ops._capture_id(x.device))
-        if self._cached is None or self._cached[0] != key:
+        hit = _WEIGHTS.get(self)
+        if hit is None or hit[0] != key:
             A, ent = ops.kp_weights(x)
             if A.grad_fn is not None:
-                A.grad_fn.register_hook(self._drop_cache)
-            self._cached = (key, A, ent)
-        return self._cached[1], self._cached[2]
+                # (a weak reference: the node must not keep the module -- and with it this very entry -- alive)
+                me = weakref.ref(self)
+
+                def drop(*_):
+                    head = me()
+                    if head is not None:
+                        _WEIGHTS.pop(head, None)
+                A.grad_fn.register_hook(drop)
+            hit = _WEIGHTS[self] = (key, A, ent)
+        return hit[1], hit[2]
 
     def entropy(self):
         return self.weights()[1]

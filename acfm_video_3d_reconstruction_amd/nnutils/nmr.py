@@ -15,7 +15,7 @@ from .. import ops
 from . import geom_utils
 
 
-_LAST_PROJ = weakref.WeakKeyDictionary()   # renderer -> (key, projection of its last silhouette render): see project_points
+_LAST_PROJ = weakref.WeakKeyDictionary()   # renderer -> (key, projection of its last silhouette render, that render's (verts, cams)): see project_points
 
 
 class NeuralRenderer(torch.nn.Module):
@@ -57,10 +57,12 @@ class NeuralRenderer(torch.nn.Module):
             # the silhouette render's face setup produced exactly these (x, y) -- same function, same bits -- as an
             # output of its own autograd node, so the boundary loss's gradient returns through that render's ONE
             # projection backward (no second projection kernel, no sum of two vertex / camera gradients).  Handed out
-            # once, and only for the very tensors of the render (storage, version, shape).
+            # once, and only where it is what project_xy would return, gradient path included (ops._proj_serves): the
+            # very tensors of the render (storage, version, shape), the same inputs requiring grad in the same grad
+            # mode, the same hipGraph capture.  Anything else is projected by the kernel.
             hit = _LAST_PROJ.get(self)
-            if hit is not None and verts.dtype == torch.float32 and hit[0] == ops._proj_key(verts, cams):
-                del _LAST_PROJ[self]
+            if hit is not None and verts.dtype == torch.float32 and ops._proj_serves(hit, verts, cams):
+                _LAST_PROJ.pop(self, None)
                 return hit[1]
             return ops.project_xy(verts, cams, 0.)
         return self.proj_fn(verts, cams)[:, :, :2]

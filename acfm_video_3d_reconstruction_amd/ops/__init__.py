@@ -25,7 +25,7 @@ from .step_losses import (_BdsLoss, _BdsLossSel, _Combine, _MaskLosses, _TexMSE,
                           combine_losses, mask_losses, tex_mse)
 from .render import (LazyPixToFace, PREFILL_TEX, SIL_BLUR, SIL_K, SIL_SIGMA, TEX_BWD_GATHER, _COVER, _EPOCH, _SETUP,
                      _SHARE, _Setup, _SilRender, _TexRender, _cover_taken, _cover_tuning, _lazy_pix_to_face, _proj_key,
-                     _remember_setup, _setup_key, _shared_setup, _sil_apply, _take_prefill, graph_replay, hard_raster,
+                     _proj_serves, _remember_setup, _setup_key, _shared_setup, _sil_apply, _take_prefill, graph_replay, hard_raster,
                      invalidate_setups, share_setup, sil_render, sil_render_losses, tex_render, tex_render_mse,
                      vertex_color_render, visible_vertices)
 from .geometry import (SOLVE_INFO_HANDOFF, _CameraNormalize, _CameraPipeline, _CameraPipelineTables, _DeformApply,

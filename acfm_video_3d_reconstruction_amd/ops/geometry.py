@@ -1,6 +1,7 @@
 """Projection, deformation (apply and solve) and cameras."""
 import ctypes
 import math
+import weakref
 
 import torch
 
@@ -77,6 +78,7 @@ class _DeformApply(torch.autograd.Function):
         out = torch.empty((N, V, 3), dtype=torch.float32, device=m.device)
         _lib.call("acfm_deform_apply", m.device, m, p, d, N, V, Kh, out)
         ctx.save_for_backward(p, d)
+        ctx.sink = _sink_entry(P)      # the registration of this very P object, if any (not of its address)
         return out
 
     @staticmethod
@@ -94,28 +96,48 @@ class _DeformApply(torch.autograd.Function):
             # of the system: summed in double and rounded once (acfm_deform_presolve_sums_f64), so that the value does
             # not depend on how the frames are grouped; a frame-sharded step (sharding.SharedShapeExchange) takes the
             # unrounded doubles for its exchange buffer
-            sink = _PRESOLVE_SINKS.get(p.data_ptr())
+            ent = ctx.sink
+            sink = ent[1]() if (ent is not None and _PRESOLVE_SINKS.get(ent[2]) is ent) else None   # (still registered)
             if sink is not None:       # (G [V,K_h], sum g [V,3]): float64 views INSIDE the exchange buffer
                 g64, m64 = sink.presolve_buffer(V, Kh, g.device)
             else:
                 g64, m64 = torch.empty((V, Kh), dtype=torch.float64, device=g.device), None
             _lib.call("acfm_deform_presolve_sums_f64", g.device, d, g, N, V, Kh, g64, m64, gp)
+            if sink is not None and hasattr(sink, "presolve_rounded"):
+                sink.presolve_rounded(gp, gm)      # (the float32 twins of what the sink now holds in double)
         return gm, gp, gd
 
 
-# P leaf (data_ptr) -> the object that wants the unrounded double sums of its backward (presolve_buffer(V, Kh, device)
-# -> persistent float64 tensors ([V,K_h], [V,3]) it will read after the backward).  One entry per live exchange.
+# id(P leaf) -> (weak reference to that leaf, weak reference to the object that wants the unrounded double sums of its
+# backward, the key): presolve_buffer(V, Kh, device) -> persistent float64 tensors ([V,K_h], [V,3]) it will read after the
+# backward.  One entry per live exchange.  Both references are weak -- the table keeps neither the exchange (its float64
+# store, its factorisation's graph) nor the leaf alive, and an entry goes when either dies -- and a registration is
+# matched on the leaf OBJECT: another tensor on the same address (`P.detach()`, a recycled block) is not routed here.
 _PRESOLVE_SINKS = {}
 
 
+def _forget_sink(key, ref):
+    with _LOCK:
+        ent = _PRESOLVE_SINKS.get(key)
+        if ent is not None and (ent[0] is ref or ent[1] is ref):
+            del _PRESOLVE_SINKS[key]
+
+
+def _sink_entry(P):
+    ent = _PRESOLVE_SINKS.get(id(P))
+    return ent if (ent is not None and ent[0]() is P) else None
+
+
 def register_presolve_sink(P, sink, previous_key=None):
-    """sharding.SharedShapeExchange.apply(): the backward of deform_apply(., P, .) writes sum_n g_n delta_n^T in double
-    into sink.presolve_buffer(...).  -> the key to hand back as previous_key next time (or to drop_presolve_sink)."""
+    """sharding.SharedShapeExchange.apply(): the backward of deform_apply(., P, .) -- of this tensor object P -- writes
+    sum_n g_n delta_n^T in double into sink.presolve_buffer(...).  Neither P nor the sink is kept alive.  -> the key to
+    hand back as previous_key next time (or to drop_presolve_sink)."""
+    key = id(P)
+    gone = lambda ref, key=key: _forget_sink(key, ref)
     with _LOCK:
         if previous_key is not None:
             _PRESOLVE_SINKS.pop(previous_key, None)
-        key = P.data_ptr()
-        _PRESOLVE_SINKS[key] = sink
+        _PRESOLVE_SINKS[key] = (weakref.ref(P, gone), weakref.ref(sink, gone), key)
     return key
 
 

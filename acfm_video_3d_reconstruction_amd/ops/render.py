@@ -354,8 +354,25 @@ class _SilRender(torch.autograd.Function):
 
 
 def _proj_key(verts, cams):
+    """What a projection handed from a silhouette render to NeuralRenderer.project_points must share with the call it
+    answers: the storage (address, version, shape, dtype) AND the autograd identity the result would have -- which
+    input requires grad, whether the graph is being recorded -- and the hipGraph capture (a tensor made inside a capture
+    lives in the graph's pool and is rewritten by every replay: it serves that capture only)."""
     return (verts.data_ptr(), verts._version, tuple(verts.shape), str(verts.dtype), cams.data_ptr(), cams._version,
-            tuple(cams.shape), str(cams.dtype))
+            tuple(cams.shape), str(cams.dtype), bool(verts.requires_grad), bool(cams.requires_grad),
+            torch.is_grad_enabled(), _capture_id(verts.device) if verts.is_cuda else 0)
+
+
+def _proj_serves(entry, verts, cams):
+    """entry = (key, proj, (verts, cams) of the render: kept alive, so that the addresses in the key cannot be
+    recycled -- like _Setup.inputs).  True when `proj` is what project_xy(verts, cams) would return, gradient path
+    included: the key matches, and an input the graph was recorded for is the render's very tensor object (`v.detach()`
+    and a new leaf on the same storage share address and version with `v`, but not its place in the graph)."""
+    key, _proj, inputs = entry
+    if key != _proj_key(verts, cams):
+        return False
+    recorded = torch.is_grad_enabled()
+    return all(a is b or not (recorded and b.requires_grad) for a, b in zip(inputs, (verts, cams)))
 
 
 def _sil_apply(verts, faces, cams, gt, edt, img_size, K, blur, sigma, offset_z, k_out, storage, fused):
@@ -374,7 +391,7 @@ def _sil_apply(verts, faces, cams, gt, edt, img_size, K, blur, sigma, offset_z, 
         p2f._acfm_vis = vis
     # the (x, y) projection of these vertices under these cameras, an output of the render's autograd node: rides on
     # the pix_to_face object like the visibility bitmap (NeuralRenderer.project_points picks it up)
-    p2f._acfm_proj = (_proj_key(verts, cams), proj)
+    p2f._acfm_proj = (_proj_key(verts, cams), proj, (verts, cams))
     return losses, mask, p2f
 
 

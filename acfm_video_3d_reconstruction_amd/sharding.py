@@ -162,6 +162,17 @@ class SharedShapeExchange:
         # d lbs = solve_backward(G) amplifies G's rounding by the conditioning of the system (~1e5), and this way the
         # split of the frames over the ranks no longer shows in it
         self._store, self._filled, self._sink_key = None, False, None
+        self._new_step()
+
+    def _new_step(self):
+        """Per-step bookkeeping, reset by apply().  Like .grad, the exchange ACCUMULATES over the backward passes of one
+        apply(): the first pass writes the head of the buffer, every later one a temporary pair that pack() adds
+        (_more).  pack() and unpack() may be repeated: the direct terms they found on solver.mean_v.grad /
+        solver.lbs.grad the first time are remembered (_direct_*), and the gradients unpack() itself put there (_out_*,
+        recognised by identity) are not taken for direct terms the next time."""
+        self._more, self._rounded = [], []
+        self._direct_mean = self._direct_lbs = self._out_mean = self._out_lbs = None
+        self._direct_added = self._finished = False
 
     def _room(self, n, device):
         """A persistent float64 allocation of at least n elements (the packed buffer is its head)."""
@@ -177,8 +188,20 @@ class SharedShapeExchange:
         head of the exchange buffer -- the backward's kernel writes the packed layout itself."""
         tail = self._n_direct() + sum(p.numel() for p in self.extra) + max(self._n_sc, 8)
         st = self._room(V * Kh + 3 * V + tail, device)
-        self._filled = True
+        if self._filled:
+            # a further backward pass through the same apply() (two losses back-propagated separately, retain_graph):
+            # the kernel writes, it does not add -- its sums go to a pair of their own and pack() adds them to the head
+            pair = (torch.empty((V, Kh), dtype=torch.float64, device=device),
+                    torch.empty((V, 3), dtype=torch.float64, device=device))
+            self._more.append(pair)
+            return pair
+        self._filled, self._direct_added = True, False
         return st[:V * Kh].view(V, Kh), st[V * Kh:V * Kh + 3 * V].view(V, 3)
+
+    def presolve_rounded(self, gP, gmean):
+        """(called by ops._DeformApply.backward behind the kernel) the float32 gradients autograd gets for the (P, mean)
+        leaves from the pass that has just written presolve_buffer(): pack() accepts them back (they say nothing new)."""
+        self._rounded.append((gP, gmean))
 
     def _n_direct(self):
         """Doubles kept behind the [V,3] block for the direct term on a symmetric solver's half parameter."""
@@ -202,6 +225,7 @@ class SharedShapeExchange:
         self._P_leaf = self._P.detach().requires_grad_(True)
         self._mean_leaf = mean.requires_grad_(True)
         self._filled = False
+        self._new_step()
         if delta.is_cuda:
             from . import ops
             self._sink_key = ops.register_presolve_sink(self._P_leaf, self, self._sink_key)
@@ -215,18 +239,38 @@ class SharedShapeExchange:
     def pack(self, gP=None, gmean=None, extra_scalars=None):
         """Complete [G | sum g | extra shared grads | scalars] in the persistent float64 buffer.  On the GPU the first two
         parts are there already (the deformation apply's backward writes its double sums in place: presolve_buffer);
-        otherwise gP / gmean -- by default the .grad of the (P, mean) leaves of the last apply() -- are copied in."""
+        otherwise gP / gmean -- by default the .grad of the (P, mean) leaves of the last apply() -- are copied in.
+        Several backward passes through one apply() have accumulated, like .grad.  Calling pack() again changes nothing
+        (the direct term on the mean shape is counted once).  gP / gmean given while the backward has filled the buffer
+        raise ValueError unless they are that backward's own outputs: anything else would be silently ignored."""
         s = self.solver
+        given = [g for g in (gP, gmean) if g is not None]
         if gP is None:
             gP = self._P_leaf.grad if self._P_leaf.grad is not None else torch.zeros_like(self._P_leaf)
         if gmean is None:
             gmean = self._mean_leaf.grad if self._mean_leaf.grad is not None else torch.zeros_like(self._mean_leaf)
-        direct = s.mean_v.grad if (s.mean_v.requires_grad and s.mean_v.grad is not None) else None   # priors on the template
+        # priors on the template: what the backward left on mean_v.grad -- not what an earlier unpack() of this step put there
+        if s.mean_v.requires_grad and s.mean_v.grad is not None and s.mean_v.grad is self._out_mean:
+            direct = self._direct_mean
+        else:
+            direct = self._direct_mean = s.mean_v.grad if (s.mean_v.requires_grad and s.mean_v.grad is not None) else None
         self._n_sc = 0 if extra_scalars is None else extra_scalars.numel()
         nP, nm, nd = gP.numel(), gmean.numel(), self._n_direct()
         n = nP + nm + nd + sum(p.numel() for p in self.extra) + self._n_sc
         filled = self._filled and self._store is not None and self._store.device == gP.device
+        if filled and given:
+            own = [t for pair in self._rounded for t in pair if t is not None]
+            if not all(any(g.data_ptr() == t.data_ptr() and g.shape == t.shape for t in own) for g in given):
+                raise ValueError("SharedShapeExchange.pack: gP / gmean were given, but the backward of this apply() has "
+                                 "already written its double sums into the exchange buffer -- the two conflict and the "
+                                 "given ones would be ignored.  Pass neither: the buffer is complete")
         flat = self._room(n, gP.device)[:n]
+        if filled and self._more:
+            # the sums of the second and later backward passes of this apply(): added to the first pass's, in double
+            more, self._more = self._more, []
+            for g64, m64 in more:
+                flat[:nP].add_(g64.reshape(-1))
+                flat[nP:nP + nm].add_(m64.reshape(-1))
         if nd:
             # symmetric: the direct term has the half parameter's shape; it gets its own segment and joins the folded
             # block in unpack()
@@ -239,9 +283,10 @@ class SharedShapeExchange:
                 flat[nP + nm:nP + nm + nd].copy_(direct.reshape(-1))
         elif filled:
             # the deformation apply's backward wrote G and sum g in double at the head of the buffer already (GPU); only a
-            # direct term on the mean shape (a prior on the template) is still to be added
-            if direct is not None:
+            # direct term on the mean shape (a prior on the template) is still to be added -- once
+            if direct is not None and not self._direct_added:
                 flat[nP:nP + nm].add_(direct.reshape(-1))
+            self._direct_added = True
         else:
             flat[:nP].copy_(gP.reshape(-1))
             flat[nP:nP + nm].copy_((gmean if direct is None else gmean + direct).reshape(-1))
@@ -288,11 +333,17 @@ class SharedShapeExchange:
             o *= d
         G = flat[:o].view(pshape).to(s.lbs.dtype if s.lbs.is_floating_point() else torch.float32, copy=True)   # the ONE rounding of G
         if s.lbs.requires_grad:
-            direct, s.lbs.grad = s.lbs.grad, None                     # a direct term on lbs (a regulariser: replicated,
-            # identical on every rank) is kept, like mean_v's; d lbs through P = solve_backward(G), on every rank.
+            # a direct term on lbs (a regulariser: replicated, identical on every rank) is kept, like mean_v's -- but what
+            # an earlier unpack() of this step put there is not one: unpack() twice gives the first result
+            if s.lbs.grad is not None and s.lbs.grad is self._out_lbs:
+                direct = self._direct_lbs
+            else:
+                direct = self._direct_lbs = s.lbs.grad
+            s.lbs.grad = None
+            # d lbs through P = solve_backward(G), on every rank.
             # (autograd.grad with retain_graph: the factorisation's node may belong to a captured step that is replayed)
             (g_lbs,) = torch.autograd.grad([self._P], [s.lbs], [G], retain_graph=True)
-            s.lbs.grad = g_lbs if direct is None else direct + g_lbs
+            s.lbs.grad = self._out_lbs = g_lbs if direct is None else direct + g_lbs
         nm = 1
         for d in mshape:
             nm *= d
@@ -300,9 +351,9 @@ class SharedShapeExchange:
         if nd:
             from . import template
             g = template.fold(flat[o:o + nm].view(mshape).to(s.mean_v.dtype, copy=True), s.symmetry[1])
-            s.mean_v.grad = g + flat[o + nm:o + nm + nd].view_as(s.mean_v).to(s.mean_v.dtype)
+            s.mean_v.grad = self._out_mean = g + flat[o + nm:o + nm + nd].view_as(s.mean_v).to(s.mean_v.dtype)
         elif s.mean_v.requires_grad:
-            s.mean_v.grad = flat[o:o + nm].view(mshape).to(s.mean_v.dtype, copy=True)
+            s.mean_v.grad = self._out_mean = flat[o:o + nm].view(mshape).to(s.mean_v.dtype, copy=True)
         o += nm + nd
         for p in self.extra:
             p.grad = flat[o:o + p.numel()].view_as(p).to(p.dtype, copy=True)
@@ -310,8 +361,14 @@ class SharedShapeExchange:
         return flat[flat.numel() - self._n_sc:].to(torch.float32, copy=True) if self._n_sc else None
 
     def finish(self, extra_scalars=None):
+        """pack() -> reduce() -> unpack().  Called again for the same apply() it only unpacks again: the buffer holds the
+        reduced sums already, and a second collective would sum them over the ranks once more (reduce() itself is the
+        collective and is not idempotent: whoever calls the three stages by hand calls it once per step)."""
+        if self._finished and not self._more:
+            return self.unpack()
         self.pack(extra_scalars=extra_scalars)
         self.reduce()
+        self._finished = True
         return self.unpack()
 
     @staticmethod

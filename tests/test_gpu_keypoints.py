@@ -474,6 +474,69 @@ def test_graph_capture():
             assert torch.equal(a, b), (seed, i)
 
 
+# ------------------------------------------------------------------------------------------------ the head's cached weights
+def _head(seed=400, K=15, V=70):
+    from acfm_video_3d_reconstruction_amd.keypoints import KeypointHead
+    return KeypointHead(torch.nn.Parameter(3 * torch.randn(K, V, generator=_gen(seed)))).to(_d())
+
+
+def test_head_copies_and_saves_between_forward_and_backward():
+    """KeypointHead.weights() keeps (A, entropy) for the next call; A is a non-leaf tensor, which copy.deepcopy and
+    torch.save of a module must never meet ("Only Tensors created explicitly by the user ... support the deepcopy
+    protocol").  Between a grad-mode weights() and its backward both succeed; the copy computes its own weights from
+    its own logits and its backward reaches ITS parameter."""
+    import copy
+    import io
+    from acfm_video_3d_reconstruction_amd import ops
+    head = _head()
+    A, ent = head.weights()
+    assert A.grad_fn is not None
+    dup = copy.deepcopy(head)
+    buf = io.BytesIO()
+    torch.save(head, buf)
+    buf.seek(0)
+    loaded = torch.load(buf, weights_only=False)
+    for other in (dup, loaded):
+        assert other.vert2kp is not head.vert2kp and torch.equal(other.vert2kp, head.vert2kp)
+        with torch.no_grad():
+            other.vert2kp.mul_(0.5)                              # its own logits: the original's weights would show
+        A2, ent2 = other.weights()
+        want, want_ent = ops.kp_weights(other.vert2kp)
+        assert torch.equal(A2, want) and torch.equal(ent2, want_ent) and not torch.equal(A2, A)
+        w = torch.randn(A2.shape, generator=_gen(401)).to(_d())
+        ((A2 * w).sum() + ent2).backward()
+        assert other.vert2kp.grad is not None and float(other.vert2kp.grad.abs().max()) > 0
+        assert head.vert2kp.grad is None
+    (A.sum() + ent).backward()                                   # the original's graph is intact
+    assert head.vert2kp.grad is not None
+
+
+def test_head_weights_follow_the_grad_mode():
+    """A no_grad call then a grad call: the second result carries a graph; a grad call then a no_grad call: it does not."""
+    head = _head(402)
+    with torch.no_grad():
+        A0, _ = head.weights()
+    A1, _ = head.weights()
+    assert A0.grad_fn is None and A1.grad_fn is not None and torch.equal(A0, A1)
+    head = _head(403)
+    A1, _ = head.weights()
+    with torch.no_grad():
+        A0, e0 = head.weights()
+    assert A1.grad_fn is not None and A0.grad_fn is None and not A0.requires_grad and not e0.requires_grad
+
+
+def test_head_weights_follow_load_state_dict():
+    """load_state_dict between two calls writes the logits in place: the second call's weights are the new logits'."""
+    from acfm_video_3d_reconstruction_amd import ops
+    head, src = _head(404), _head(405)
+    with torch.no_grad():
+        A0 = head.weights()[0].clone()
+        head.load_state_dict(src.state_dict())
+        A1, e1 = head.weights()
+        want, want_e = ops.kp_weights(src.vert2kp)
+    assert torch.equal(A1, want) and torch.equal(e1, want_e) and not torch.equal(A1, A0)
+
+
 # ------------------------------------------------------------------------------------------------ step wiring
 def test_multiframe_step_wiring(meshes):
     """MultiframeStep(supervision_kernels=True) against the default on the tiny batch of test_gpu_losses.py's step test,
