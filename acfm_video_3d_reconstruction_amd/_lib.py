@@ -89,6 +89,14 @@ SIGNATURES = {
     "acfm_uv_texels": (_i, [_p8, _pf, _pf, _pf, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _pf, _vp, _vp]),
     "acfm_uv_texels_backward": (_i, [_p8, _pf, _pf, _pf, _pf, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _pf, _pf, _pf, _vp,
                                      _sz, _vp, _vp]),
+    "acfm_vertex_normals": (_i, [_pf, _p8, _p4, _p4, _i, _i, _pf, _pf, _vp]),
+    "acfm_vertex_normals_backward": (_i, [_pf, _p8, _p4, _p4, _pf, _pf, _i, _i, _pf, _vp, _sz, _vp]),
+    "acfm_light_points": (_i, [_pf, _pf, _pf, _p8, _pf, _i, _i, _i, _pf, _vp]),
+    "acfm_light_points_backward": (_i, [_pf, _pf, _pf, _p8, _pf, _i, _pf, _i, _i, _pf, _pf, _pf, _vp]),
+    "acfm_phong_shade": (_i, [_p8, _pf, _pf, _pf, _p8, _pf, _pf, _i, _i, _sz, _i, _i, _i, _i, _i, _pf, _vp, _vp]),
+    "acfm_phong_shade_backward": (_i, [_p8, _pf, _pf, _pf, _p8, _pf, _pf, _i, _i, _pf, _sz, _i, _i, _i, _i, _i, _pf,
+                                       _pf, _pf, _vp, _sz, _vp, _vp]),
+    "acfm_corner_gather": (_i, [_pf, _p4, _p4, _i, _i, _i, _pf, _pf, _vp]),
     "acfm_tex_forward": (_i, [_pf, _p8, _pf, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _p4,
                               _vp, _sz, _i, _f, _i, _vp, _vp]),
     "acfm_vertex_color_forward": (_i, [_pf, _p8, _pf, _pf, _i, _i, _i, _i, _f, _f, _f, _pf, _pf, _p8, _vp, _sz,

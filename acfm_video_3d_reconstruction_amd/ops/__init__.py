@@ -10,7 +10,8 @@ is one or more stream-ordered calls into libacfm_hip.so."""
 #        render       setup / cover / prefill caches, LazyPixToFace, the renders     <- base, pending
 #   3. the leaves, plain "allocate, call, return" bindings, each <- base only:
 #        geometry, flow, fragments, hypotheses, mesh_terms, geodesic, uvatlas, lpips, keypoint_loss, symmetry, surface
-#        and neighbours (knn_points, knn_gather), which takes _lengths from mesh_terms
+#        and neighbours (knn_points, knn_gather), which takes _lengths from mesh_terms, and lighting (vertex_normals,
+#        light_points, phong_shade), which takes the fragment checks from fragments
 #      (geodesic_distances alone looks up pytorch3d_shim's Meshes when called: the shim is built on this package)
 # State is reached through containers that are mutated in place (dicts, one-element lists), never rebound: a
 # re-export below copies the binding, so `ops.X = ...` would not reach the module that reads X.
@@ -54,3 +55,5 @@ from .keypoint_loss import (KP_MAX_K, KP_MAX_N, KP_MAX_V, _CameraLoss, _KpHead, 
 from .symmetry import _Symmetrize, symmetrize, symmetrize_fold
 from .surface import _SurfaceSample, sample_surface, sample_surface_uv
 from .neighbours import KNN_MAX_K, _KnnGather, _KnnPoints, knn_gather, knn_points
+from .lighting import (SHADE_MODES, IncidenceTable, LightConstants, _LightPoints, _PhongShade, _VertexNormals,
+                       incidence_table, light_constants, light_points, phong_shade, vertex_normals)

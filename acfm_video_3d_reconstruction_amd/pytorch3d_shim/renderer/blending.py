@@ -31,5 +31,23 @@ def sigmoid_alpha_blend(colors, fragments, blend_params):
     return _ops.sigmoid_alpha_blend(colors, fragments, blend_params)
 
 
+def softmax_rgb_blend_composition(colors, fragments, blend_params, znear=1.0, zfar=100.0):
+    """softmax_rgb_blend as PyTorch3D 0.3.0 composes it from torch operators: the host path."""
+    eps = 1e-10
+    mask = (fragments.pix_to_face >= 0).to(colors.dtype)
+    prob = torch.sigmoid(-fragments.dists / blend_params.sigma) * mask
+    alpha = torch.prod(1.0 - prob, dim=-1)
+    z_inv = (zfar - fragments.zbuf) / (zfar - znear) * mask
+    z_inv_max = torch.max(z_inv, dim=-1).values[..., None].clamp(min=eps)
+    num = prob * torch.exp((z_inv - z_inv_max) / blend_params.gamma)
+    delta = torch.exp((eps - z_inv_max) / blend_params.gamma).clamp(min=eps)
+    denom = num.sum(dim=-1)[..., None] + delta
+    rgb = ((num[..., None] * colors).sum(dim=-2) + delta * _background(colors, blend_params)) / denom
+    return torch.cat([rgb, (1.0 - alpha)[..., None]], dim=-1)
+
+
 def softmax_rgb_blend(colors, fragments, blend_params, znear=1.0, zfar=100.0):
+    """The HIP kernel on GPU tensors; on host tensors the composition of torch operators."""
+    if torch.is_tensor(colors) and not colors.is_cuda and not fragments.pix_to_face.is_cuda:
+        return softmax_rgb_blend_composition(colors, fragments, blend_params, znear=znear, zfar=zfar)
     return _ops.softmax_rgb_blend(colors, fragments, blend_params, znear=znear, zfar=zfar)

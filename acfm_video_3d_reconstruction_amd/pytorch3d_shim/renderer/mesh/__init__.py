@@ -4,6 +4,7 @@ from . import rasterizer, renderer, shader, shading, textures  # noqa: F401
 from .rasterize_meshes import rasterize_meshes  # noqa: F401
 from .rasterizer import Fragments, MeshRasterizer, RasterizationSettings  # noqa: F401
 from .renderer import MeshRenderer  # noqa: F401
-from .shader import HardPhongShader, SoftPhongShader, SoftSilhouetteShader, TexturedSoftPhongShader  # noqa: F401
-from .shading import phong_shading  # noqa: F401
+from .shader import (HardFlatShader, HardGouraudShader, HardPhongShader, SoftGouraudShader,  # noqa: F401
+                     SoftPhongShader, SoftSilhouetteShader, TexturedSoftPhongShader)
+from .shading import flat_shading, gouraud_shading, phong_shading  # noqa: F401
 from .textures import Textures, TexturesAtlas, TexturesUV, TexturesVertex  # noqa: F401

@@ -1,15 +1,17 @@
 """pytorch3d.renderer.mesh.shader (0.3.0): SoftSilhouetteShader, SoftPhongShader (TexturedSoftPhongShader is its 0.3.0
-alias) and HardPhongShader.  forward(fragments, meshes, **kwargs) accepts cameras= / lights= / materials= /
+alias), HardPhongShader, SoftGouraudShader, HardGouraudShader and HardFlatShader.  forward(fragments, meshes, **kwargs) accepts cameras= / lights= / materials= /
 blend_params= overrides.  SoftPhongShader with ambient-only lights and a TexturesAtlas -- the reference's texture
 configuration -- takes ops.atlas_softmax_blend (texels sampled inside the blend kernel); every other combination
-goes through phong_shading and the dense softmax kernel."""
+goes through phong_shading and the dense softmax kernel.  The Gouraud and flat shaders are restated from memory of
+0.3.0's shader.py (the package is not at hand): Gouraud lights the TexturesVertex colours at the vertices, flat shades
+each fragment at its face's centre and face normal."""
 from torch import nn
 
 from .... import ops as _ops
 from ..blending import BlendParams, hard_rgb_blend, sigmoid_alpha_blend, softmax_rgb_blend
 from ..lighting import PointLights
 from ..materials import Materials
-from .shading import phong_shading
+from .shading import flat_shading, gouraud_shading, phong_shading
 from .textures import TexturesAtlas
 
 
@@ -76,4 +78,31 @@ class HardPhongShader(_Shader):
         texels = meshes.sample_textures(fragments)
         colors = phong_shading(meshes=meshes, fragments=fragments, texels=texels, lights=lights, cameras=cameras,
                                materials=materials, **self._view(kwargs))
+        return hard_rgb_blend(colors, fragments, blend_params)
+
+
+class SoftGouraudShader(_Shader):
+    def forward(self, fragments, meshes, **kwargs):
+        cameras, lights, materials, blend_params = self._parts(kwargs)
+        znear = kwargs.get("znear", getattr(cameras, "znear", 1.0))
+        zfar = kwargs.get("zfar", getattr(cameras, "zfar", 100.0))
+        colors = gouraud_shading(meshes=meshes, fragments=fragments, lights=lights, cameras=cameras,
+                                 materials=materials, **self._view(kwargs))
+        return softmax_rgb_blend(colors, fragments, blend_params, znear=znear, zfar=zfar)
+
+
+class HardGouraudShader(_Shader):
+    def forward(self, fragments, meshes, **kwargs):
+        cameras, lights, materials, blend_params = self._parts(kwargs)
+        colors = gouraud_shading(meshes=meshes, fragments=fragments, lights=lights, cameras=cameras,
+                                 materials=materials, **self._view(kwargs))
+        return hard_rgb_blend(colors, fragments, blend_params)
+
+
+class HardFlatShader(_Shader):
+    def forward(self, fragments, meshes, **kwargs):
+        cameras, lights, materials, blend_params = self._parts(kwargs)
+        texels = meshes.sample_textures(fragments)
+        colors = flat_shading(meshes=meshes, fragments=fragments, texels=texels, lights=lights, cameras=cameras,
+                              materials=materials, **self._view(kwargs))
         return hard_rgb_blend(colors, fragments, blend_params)

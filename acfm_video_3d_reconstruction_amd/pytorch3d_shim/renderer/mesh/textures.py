@@ -1,11 +1,20 @@
 """pytorch3d.renderer.mesh.textures (0.3.0): TexturesAtlas, TexturesVertex, TexturesUV and the `Textures(...)` wrapper.
-TexturesVertex.sample_textures is the HIP interpolate_face_attributes; TexturesAtlas.sample_textures selects texels
-with PyTorch3D's rule -- shaders of ambient-only lights take ops.atlas_softmax_blend instead, which
+TexturesVertex.sample_textures is the HIP interpolate_face_attributes (host tensors: the torch gather);
+TexturesAtlas.sample_textures selects texels with PyTorch3D's rule -- shaders of ambient-only lights take ops.atlas_softmax_blend instead, which
 samples inside the blend kernel.  TexturesUV.sample_textures is ops.uv_texels on GPU tensors -- the
 map is read in place, per fragment -- and PyTorch3D's own composition of torch operators on host tensors."""
 import torch
 
 from .... import ops as _ops
+
+
+def interpolate_face_attributes(pix_to_face, bary_coords, face_attributes):
+    """The HIP kernel on GPU tensors; on host tensors PyTorch3D's gather (0 in empty slots)."""
+    if pix_to_face.is_cuda:
+        return _ops.interpolate_face_attributes(pix_to_face, bary_coords, face_attributes)
+    vals = face_attributes[pix_to_face.clamp(min=0)]                       # [N,H,W,K,3,D]
+    out = (bary_coords[..., None] * vals).sum(dim=-2)
+    return torch.where((pix_to_face < 0)[..., None], torch.zeros_like(out), out)
 
 
 class TexturesAtlas:
@@ -82,7 +91,7 @@ class TexturesVertex:
     def sample_textures(self, fragments, faces_packed=None):
         """-> texels [N,H,W,K,C]: the vertex features interpolated at the barycentrics (HIP kernel)."""
         faces_verts_features = self.verts_features_packed()[faces_packed]
-        return _ops.interpolate_face_attributes(fragments.pix_to_face, fragments.bary_coords, faces_verts_features)
+        return interpolate_face_attributes(fragments.pix_to_face, fragments.bary_coords, faces_verts_features)
 
 
 def uv_texels_composition(pix_to_face, bary_coords, faces_verts_uvs, maps, align_corners=True, padding_mode="border"):

@@ -307,11 +307,30 @@ class Meshes:
         val = torch.cat([val, -torch.ones(V, dtype=torch.float32, device=self.device)])
         return torch.sparse_coo_tensor(idx, val, (V, V)).coalesce()
 
+    def incidence_table_packed(self):
+        """-> ops.IncidenceTable: for every packed vertex the face corners 3 f + i that hold it, ascending (CSR), as
+        acfm_vertex_normals and acfm_corner_gather read it.  Topology only: built once per faces tensor, on the host,
+        outside any graph capture."""
+        def make():
+            from .. import ops
+            t = ops.incidence_table(self.faces_packed(), sum(v.shape[0] for v in self._verts_list))
+            return (t.offsets, t.corners)
+        from .. import ops
+        offsets, corners = self._topo("incidence_table_packed", make)
+        return ops.IncidenceTable(offsets, corners, sum(v.shape[0] for v in self._verts_list),
+                                  sum(f.shape[0] for f in self._faces_list))
+
     # ---- normals (0.3.0's rule: the unnormalised cross product of every face -- twice its area times its normal --
-    # added into each of its vertices, then F.normalize(eps=1e-6)); torch, differentiable
+    # added into each of its vertices, then F.normalize(eps=1e-6)); differentiable.  GPU float32 tensors: the gather
+    # kernels of ops.vertex_normals; host tensors: the torch lines below
     def _compute_normals(self):
         if "verts_normals" not in self._cache:
             verts, faces = self.verts_packed(), self.faces_packed()
+            if verts.is_cuda and verts.dtype == torch.float32 and faces.shape[0] > 0 and verts.shape[0] > 0:
+                from .. import ops
+                vn, fn = ops.vertex_normals(verts, faces, self.incidence_table_packed())
+                self._cache["verts_normals"], self._cache["faces_normals"] = vn, fn
+                return vn, fn
             fv = verts[faces]
             n = torch.zeros_like(verts)
             n = n.index_add(0, faces[:, 1], torch.cross(fv[:, 2] - fv[:, 1], fv[:, 0] - fv[:, 1], dim=1))

@@ -524,6 +524,60 @@ int acfm_uv_texels_backward(const int64_t* pix_to_face, const float* bary, const
                             float* grad_bary, float* grad_faces_verts_uvs, void* ws, size_t ws_bytes,
                             const AcfmRasterTuning* tuning, void* stream);
 
+/* ---- lit shading -------------------------------------------------------------
+ * acfm_vertex_normals: Meshes.verts_normals_packed / faces_normals_packed of PyTorch3D 0.3.0.  verts [V,3] f32 and
+ *   faces [F,3] i64, packed; (offsets [V+1], corners [3F]) i32: for every vertex the corners 3 f + i that hold it,
+ *   ascending (CSR; built once per faces tensor on the host).  verts_normals [V,3] = x / max(|x|, 1e-6) of the sum, in
+ *   table order, of the unnormalised cross products (v[i+1] - v[i]) x (v[i+2] - v[i]) taken at the vertex's own corner;
+ *   faces_normals [F,3] = normalize((v2 - v1) x (v0 - v1)).  Either output may be NULL.  A face with a vertex id outside
+ *   [0, V) contributes nothing.  A gather per vertex: no atomics, no valence cap, the same bits on every run.
+ * acfm_vertex_normals_backward: grad_verts [V,3] from grad_verts_normals and / or grad_faces_normals (either may be
+ *   NULL), again a gather per vertex in two launches; ws: 12 V bytes when grad_verts_normals is given. */
+int acfm_vertex_normals(const float* verts, const int64_t* faces, const int* offsets, const int* corners, int V, int F,
+                        float* verts_normals, float* faces_normals, void* stream);
+int acfm_vertex_normals_backward(const float* verts, const int64_t* faces, const int* offsets, const int* corners,
+                                 const float* grad_verts_normals, const float* grad_faces_normals, int V, int F,
+                                 float* grad_verts, void* ws, size_t ws_bytes, void* stream);
+/* acfm_light_points: the lighting function of pytorch3d.renderer.lighting (DirectionalLights / PointLights .diffuse and
+ *   .specular) at M points: out = (ambient + diffuse relu(n.l)) colour + specular relu(v.r)^shininess [n.l > 0], with
+ *   n, l = (point_light ? L - p : L), v = camera - p normalised as x / max(|x|, 1e-6) and r = 2 (n.l) n - l.  points,
+ *   normals, colours, out [M,3]; mesh_idx [M] i64 (NULL: mesh 0; outside [0, N): zeros); consts [N,16] per mesh = the
+ *   ambient, diffuse and specular products light colour x material colour, the light vector L (direction or location),
+ *   the camera centre (3 floats each) and the shininess.  Lights, materials and camera are constants: no gradient.
+ * acfm_light_points_backward: dense, one thread per point; each of grad_points / grad_normals / grad_colours may be
+ *   NULL.  Where relu(v.r) or the n.l > 0 mask is closed the specular term sends 0 (never inf x 0). */
+int acfm_light_points(const float* points, const float* normals, const float* colours, const int64_t* mesh_idx,
+                      const float* consts, int point_light, int M, int N, float* out, void* stream);
+int acfm_light_points_backward(const float* points, const float* normals, const float* colours,
+                               const int64_t* mesh_idx, const float* consts, int point_light,
+                               const float* grad_out, int M, int N, float* grad_points, float* grad_normals,
+                               float* grad_colours, void* stream);
+/* acfm_phong_shade: pytorch3d.renderer.mesh.shading.phong_shading (flat = 0) / flat_shading (flat = 1) over Fragments,
+ *   one thread per slot: colors [P,K,3] = the lighting function above at the slot's position and normal, with texels
+ *   [P,K,3] as the colour and the constants of mesh p / pix_per_mesh (P = N pix_per_mesh).  flat = 0: position and
+ *   normal are sum_i bary_i verts[faces[f,i]] and sum_i bary_i normals[faces[f,i]] (normals [V_packed,3]), formed in the
+ *   kernel: neither verts[faces], normals[faces] nor the two interpolated tensors exist.  flat = 1: the face's mean
+ *   position and normals[f] (normals [F_packed,3]; bary may be NULL).  A slot with pix_to_face outside [0, F_packed)
+ *   (or a face with a vertex id outside [0, V_packed)) is shaded at position and normal 0, as the composition does.
+ * acfm_phong_shade_backward: grad_texels [P,K,3] and grad_bary [P,K,3] (0 when flat) dense, grad_corners
+ *   [F_packed,3,6] = (position, normal) gradient per face corner (flat: a third of the position gradient per corner,
+ *   the normal gradient in corner 0); each may be NULL.  The corner sums are scattered: runs of equal faces along 64
+ *   consecutive pixels of one slot index are summed inside the wave first, then added with float atomics, or in
+ *   deterministic mode as integer pairs in `ws` (16 bytes per element of grad_corners), bit-reproducible.
+ * acfm_corner_gather: grad_corners -> grad_verts [V,3] (position part, summed over a vertex's corners through the
+ *   incidence table of acfm_vertex_normals) and grad_normals ([V,3] summed likewise, or flat: [F,3] corner 0's). */
+int acfm_phong_shade(const int64_t* pix_to_face, const float* bary, const float* texels, const float* verts,
+                     const int64_t* faces, const float* normals, const float* consts, int point_light, int flat,
+                     size_t P, int K, int pix_per_mesh, int F_packed, int V_packed, int N, float* colors,
+                     const AcfmRasterTuning* tuning, void* stream);
+int acfm_phong_shade_backward(const int64_t* pix_to_face, const float* bary, const float* texels, const float* verts,
+                              const int64_t* faces, const float* normals, const float* consts, int point_light,
+                              int flat, const float* grad_colors, size_t P, int K, int pix_per_mesh, int F_packed,
+                              int V_packed, int N, float* grad_texels, float* grad_bary, float* grad_corners, void* ws,
+                              size_t ws_bytes, const AcfmRasterTuning* tuning, void* stream);
+int acfm_corner_gather(const float* grad_corners, const int* offsets, const int* corners, int V, int F, int flat,
+                       float* grad_verts, float* grad_normals, void* stream);
+
 /* ---- atlas-textured render -----------------------------------------------------------
  * replaces NeuralRenderer.forward, texture branch with atlas=True
  * (multiframe/nnutils/nmr.py:173-200): hard raster K=1, clip_barycentric_coords=True,
