@@ -40,8 +40,10 @@ SIGNATURES = {
     "acfm_symmetrize": (_i, [_pf, _i, _i, _i, _pf, _vp]),
     "acfm_symmetrize_backward": (_i, [_pf, _i, _i, _i, _pf, _vp]),
     "acfm_correlation_forward": (_i, [_pf, _pf, _i, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_correlation_channel_split": (_i, [_i, _i, _i, _i]),
     "acfm_correlation_backward": (_i, [_pf, _pf, _pf, _i, _i, _i, _i, _i, _pf, _pf, _vp]),
     "acfm_deform_conv2d_forward": (_i, [_pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _pf, _vp]),
+    "acfm_deform_conv2d_channel_tile": (_i, [_i, _i, _i, _i]),
     "acfm_deform_conv2d_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "acfm_deform_conv2d_backward": (_i, [_pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _pf, _pf, _pf, _pf, _vp, _sz, _vp]),
     "acfm_of_loss": (_i, [_pf, _pf, _pf, _p1, _i, _i, _i, _i, _i, _i, _i, _pf, _pf, _vp]),

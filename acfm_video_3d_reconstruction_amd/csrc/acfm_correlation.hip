@@ -146,16 +146,29 @@ static void launch_corr(const float* f1, const float* f2, int N, int C, int H, i
     hipLaunchKernelGGL((k_correlation_fwd<MD, false>), grid, dim3(256), 0, st, f1, f2, C, H, W, csplit, out);
 }
 
-extern "C" int acfm_correlation_forward(const float* f1, const float* f2, int N, int C, int H, int W, int md,
-                                        float* out, void* stream) {
-  if (!f1 || !f2 || !out || N <= 0 || N > 4096 || C <= 0 || H <= 0 || W <= 0 || md < 1 || md > 4) return ACFM_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  // enough workgroups for 256 CUs: split the channels when the tiles alone are few
+static bool corr_fwd_args_ok(int N, int C, int H, int W) {
+  return N > 0 && N <= 4096 && C > 0 && H > 0 && W > 0;
+}
+
+// enough workgroups for 256 CUs: split the channels (in whole LDS chunks) when the tiles alone are fewer than 768
+static int corr_channel_split(int N, int C, int H, int W) {
   const long tiles = (long)((W + CT - 1) / CT) * ((H + CT - 1) / CT) * N;
   int csplit = (int)((768 + tiles - 1) / tiles);
   const int max_split = (C + CCH - 1) / CCH;
   if (csplit > max_split) csplit = max_split;
   if (csplit < 1) csplit = 1;
+  return csplit;
+}
+
+extern "C" int acfm_correlation_channel_split(int N, int C, int H, int W) {
+  return corr_fwd_args_ok(N, C, H, W) ? corr_channel_split(N, C, H, W) : 0;
+}
+
+extern "C" int acfm_correlation_forward(const float* f1, const float* f2, int N, int C, int H, int W, int md,
+                                        float* out, void* stream) {
+  if (!f1 || !f2 || !out || !corr_fwd_args_ok(N, C, H, W) || md < 1 || md > 4) return ACFM_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int csplit = corr_channel_split(N, C, H, W);
   if (csplit > 1 &&
       zero_async(out, sizeof(float) * (size_t)N * (2 * md + 1) * (2 * md + 1) * H * W, st) != ACFM_OK)
     return ACFM_E_LAUNCH;

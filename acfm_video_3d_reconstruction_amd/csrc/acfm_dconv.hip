@@ -166,14 +166,34 @@ __global__ __launch_bounds__(256) void k_dconv_fwd(const float* __restrict__ in,
 
 using namespace acfm;
 
+// Refusals of the forward: plane offsets and k are ints; the grid's x is pixel tiles x images, its y channel tiles of at
+// least 16.
+static bool dconv_fwd_args_ok(int N, int Cin, int H, int W, int Cout) {
+  if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return false;
+  if ((size_t)H * W > 0x7fffffffull - DC_TP || (size_t)Cin * 9 > 0x7fffffffull || Cout > 16 * 65535 ||
+      ((size_t)H * W + DC_TP - 1) / DC_TP * (size_t)N > 0x7fffffffull)
+    return false;
+  return true;
+}
+
+// the widest channel tile that still leaves a workgroup per compute unit (256 of them); never wider than Cout needs
+static int dconv_channel_tile(int N, int H, int W, int Cout) {
+  const long px_wgs = (long)((H * W + DC_TP - 1) / DC_TP) * N;
+  int tco = 64;
+  while (tco > 16 && (tco / 2 >= Cout || px_wgs * ((Cout + tco - 1) / tco) < 256)) tco >>= 1;
+  return tco;
+}
+
+extern "C" int acfm_deform_conv2d_channel_tile(int N, int H, int W, int Cout) {
+  return dconv_fwd_args_ok(N, 1, H, W, Cout) ? dconv_channel_tile(N, H, W, Cout) : 0;
+}
+
 template <bool SHARED>
 static void launch_dconv(const float* in, const float* off, const float* wgt, const float* bias, int N, int Cin, int H,
                          int W, int Cout, float* out, hipStream_t st) {
   const int tiles = (H * W + DC_TP - 1) / DC_TP;
   const long px_wgs = (long)tiles * N;
-  // the widest channel tile that still leaves a workgroup per compute unit (256 of them); never wider than Cout needs
-  int tco = 64;
-  while (tco > 16 && (tco / 2 >= Cout || px_wgs * ((Cout + tco - 1) / tco) < 256)) tco >>= 1;
+  const int tco = dconv_channel_tile(N, H, W, Cout);
   const dim3 grid((unsigned)px_wgs, (unsigned)((Cout + tco - 1) / tco));
   if (tco == 64)
     hipLaunchKernelGGL((k_dconv_fwd<SHARED, 4>), grid, dim3(256), 0, st, in, off, wgt, bias, Cin, H, W, Cout, tiles, out);
@@ -186,11 +206,7 @@ static void launch_dconv(const float* in, const float* off, const float* wgt, co
 extern "C" int acfm_deform_conv2d_forward(const float* input, const float* offset, const float* weight,
                                           const float* bias, int N, int Cin, int H, int W, int Cout, int shared_offset,
                                           float* out, void* stream) {
-  if (!input || !offset || !weight || !out || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return ACFM_E_BADARG;
-  // plane offsets and k are ints; the grid's x is pixel tiles x images, its y channel tiles of at least 16
-  if ((size_t)H * W > 0x7fffffffull - DC_TP || (size_t)Cin * 9 > 0x7fffffffull || Cout > 16 * 65535 ||
-      ((size_t)H * W + DC_TP - 1) / DC_TP * (size_t)N > 0x7fffffffull)
-    return ACFM_E_BADARG;
+  if (!input || !offset || !weight || !out || !dconv_fwd_args_ok(N, Cin, H, W, Cout)) return ACFM_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   if (shared_offset) launch_dconv<true>(input, offset, weight, bias, N, Cin, H, W, Cout, out, st);
   else launch_dconv<false>(input, offset, weight, bias, N, Cin, H, W, Cout, out, st);

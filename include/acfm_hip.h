@@ -153,6 +153,10 @@ int acfm_symmetrize_backward(const float* grad_full, int B, int n_indept, int n_
  * fine-tuning it (the reference's CorrelationFunction.backward, correlation.py:38-52). */
 int acfm_correlation_forward(const float* f1, const float* f2, int N, int C, int H, int W, int md, float* out,
                              void* stream);
+/* Host only, launches nothing: the number of workgroups the forward splits the channel range of one 16 x 16 tile over
+ * (whole chunks of 8 channels, so at most ceil(C / 8)).  1: every output element is stored once, bit-reproducible;
+ * > 1 (fewer than 768 tiles in the batch): zero fill and float atomics.  0 for arguments the forward refuses. */
+int acfm_correlation_channel_split(int N, int C, int H, int W);
 /* grad_out [N,(2md+1)^2,H,W] -> grad_f1, grad_f2 [N,C,H,W]; either may be NULL (that side is not computed, and its
  * partner map -- f2 for grad_f1, f1 for grad_f2 -- need not be given).  With d = (tj+md)(2md+1)+(ti+md):
  *   grad_f1[n,c,y,x] = 1/C sum_d grad_out[n,d,y,x]       f2[n,c,y+tj,x+ti]   (0 outside)
@@ -177,6 +181,10 @@ int acfm_correlation_backward(const float* grad_out, const float* f1, const floa
  * are bit-reproducible.  The flow network is frozen in ACFM; the backward below is for fine-tuning it. */
 int acfm_deform_conv2d_forward(const float* input, const float* offset, const float* weight, const float* bias, int N,
                                int Cin, int H, int W, int Cout, int shared_offset, float* out, void* stream);
+/* Host only, launches nothing: the output channels per workgroup the forward picks for this shape -- 64, 32 or 16, the
+ * widest that is not wider than Cout needs and still leaves 256 workgroups (the split is over Cout only: the bits of an
+ * output element do not depend on it).  0 for arguments the forward refuses. */
+int acfm_deform_conv2d_channel_tile(int N, int H, int W, int Cout);
 /* Backward: grad_out [N,Cout,H,W] -> grad_input [N,Cin,H,W], grad_offset [N,18,H,W] (shared_offset: [N,2,H,W], the sum
  * over the nine taps), grad_weight [Cout,Cin,3,3], grad_bias [Cout]; every one of the four may be NULL and is then not
  * computed (no weight-gradient kernel for a frozen weight).  Nothing of the forward is saved: the sampling is recomputed
